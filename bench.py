@@ -2,15 +2,21 @@
 """Headline benchmark: UMNN-MAF log-density evals/s (BASELINE.json metric) on MI355X.
 
   python bench.py [--gpus N --steps K --warmup W --workload bsds300|power|toy|vae|mnist --mode eval|train]
+                  [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus N --steps K --warmup W
 
 A step = one ``UMNNMAFFlow.compute_ll`` pass (MADE conditioner + fused HIP quadrature, all flow blocks) over one
 synthetic batch already resident in HBM.  Default workload: BASELINE config C3 -- BSDS300-shaped (d=63), 8192 rows
 per GPU (65536 rows sharded over 8 GPUs), n_steps=100, 5 blocks, MADE [512,512], E=30, integrand 31-50^4-1, fp32.
-Weak scaling: the per-GPU shard is fixed; no collective on the forward path.  One JSON line on rank 0.  At N=1 the
-line also carries ``full_batch_n1`` (the un-sharded 65536-row C3 batch on one GPU: the strong-scaling anchor of the
-N=8 point), ``exact_fp32`` (same workload, reference arithmetic) and ``cpu_baseline`` (both reference solvers).
+Weak scaling: the per-GPU shard is fixed; no collective on the forward path.  One JSON line on rank 0.
+
+A plain run sets up, warms up, times the K steps and prints the line; its roofline record comes from the timed launches
+and the committed profiles/hbm_traffic.json.  ``--full`` adds every measurement that takes runs of its own: the telemetry
+pass, at N=1 ``full_batch_n1`` (the un-sharded 65536-row C3 batch on one GPU: the strong-scaling anchor of the N=8 point),
+``exact_fp32`` / ``bf16x6`` / ``bf16x3`` (same workload, other arithmetic) and ``cpu_baseline`` (both reference solvers),
+the eager kernel-timing pass of ``--graph`` runs and a live HBM-traffic collection when the committed record is stale.
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (rank 0's shard when N > 1).
 """
 import argparse
 import hashlib
@@ -47,6 +53,7 @@ WORKLOADS = {
 FULL_BATCH_ROWS = 65536            # BASELINE config C3's un-sharded batch
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_16x16x4_f32 dense peak
 PEAK_BF16_MFMA_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense bf16 MFMA peak (the 2:1-sparse figure is never used)
+DUMP_LIMIT_BYTES = 64 << 20        # --dump-outputs: all arrays together
 # sources that define the dominant forward kernel: profiles/hbm_traffic.json is only trusted while their hash matches
 # (the translation unit and the two headers that hold the kernel's code; cc_common.h / cc_bf16.h also carry helpers of the BACKWARD
 # kernels -- hashing them made round 3's record go stale over an unrelated change)
@@ -187,12 +194,28 @@ def _all_cores_probe(sd, cfg, solver, chunk, ncpu, limit_s):
             return {"threads": ncpu, "error": f"{type(e).__name__}: {e}"}
 
 
-def hbm_traffic(workload, live, extra_args):
+def dump_outputs(dirname, arrays):
+    """Write ``arrays`` ({name: tensor or None}) as dirname/<name>.npy, float64 kept, everything else as float32.  Above
+    DUMP_LIMIT_BYTES in all, each keeps a fixed, seeded sample of its rows (leading dimension), the same one for arrays of equal length."""
+    import numpy as np
+    os.makedirs(dirname, exist_ok=True)
+    arrs = {k: (v.detach() if v.dtype == torch.float64 else v.detach().float()).cpu().numpy()
+            for k, v in arrays.items() if v is not None}
+    total = sum(a.nbytes for a in arrs.values())
+    if total > DUMP_LIMIT_BYTES:
+        for k, a in arrs.items():
+            keep = max(1, a.shape[0] * DUMP_LIMIT_BYTES // total)
+            arrs[k] = a[np.sort(np.random.default_rng(0).choice(a.shape[0], keep, replace=False))]
+    for k, a in arrs.items():
+        np.save(os.path.join(dirname, k + ".npy"), a)
+
+
+def hbm_traffic(workload, live, extra_args, collect=True):
     """HBM bytes per launch of the dominant kernel from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE; one counter per
     pass; gfx950 corrections per MI355X_MICROARCH.md).  The committed profiles/hbm_traffic.json is used while the kernel's
     sources hash to what was profiled; when they do not (or with ``live``) the two passes are collected NOW
     (tools/measure_traffic.py: two short child runs of this script under rocprofv3, ~1 min) -- a stale number is never
-    reported, and a missing profiler leaves null with the reason."""
+    reported, and a missing profiler leaves null with the reason.  Without ``collect`` (a plain run) nothing is collected."""
     path = os.path.join(ROOT, "profiles", "hbm_traffic.json")
     why = "--live-traffic"
     if not live:
@@ -203,6 +226,8 @@ def hbm_traffic(workload, live, extra_args):
         if rec.get("source_sha256") == kernel_source_hash():
             return rec.get("hbm_bytes_per_launch"), f"profiles/hbm_traffic.json (kernel sources {rec.get('source_sha256')} = HEAD's)"
         why = "profiles/hbm_traffic.json is for other kernel sources" if rec else "no committed record for this workload"
+        if not collect:
+            return None, f"{why}; bench.py --full collects it"
     if os.environ.get("UMNN_BENCH_CHILD"):          # (a profiling child of this very function)
         return None, "profiling child run"
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:  # (one profiler per node: the in-run collection belongs to the N = 1 line)
@@ -248,7 +273,16 @@ def main():
                          "storage mode -- the kernels load bf16, arithmetic stays fp32; reported in config.embedding_storage)")
     ap.add_argument("--precision", default="", choices=["", "fp32", "bf16x3", "bf16x6", "f16x3"],
                     help="forward arithmetic (default: the library default, f16x3 -- two fp16 pieces, fp32-level, queued bf16x3 overflow fallback)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what takes runs of its own: the telemetry pass, the N = 1 side records (exact_fp32, bf16x6, "
+                         "bf16x3 / f16x3, full_batch_n1), cpu_baseline, the eager kernel-timing pass of --graph runs and a live "
+                         "HBM-traffic collection when profiles/hbm_traffic.json is stale (the --no-* options still apply)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (eval: ll, z; train: ll, z, or loss with --graph) as DIR/<name>.npy, "
+                         f"float32 (float64 kept), at most {DUMP_LIMIT_BYTES >> 20} MB in all (a fixed, seeded row sample beyond)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     from umnn_amd import _lib, sharding
     import torch.distributed as dist
@@ -319,7 +353,7 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(args.steps):
-        ll, _ = step()
+        ll, z = step()
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -328,7 +362,9 @@ def main():
     bwd = _lib.profile_read(_lib.PROF_BACKWARD)
     fin = _lib.profile_read(_lib.PROF_FINISH)
     lib.umnn_profile_enable(0)
-    if args.graph:      # launches inside a replayed graph carry no events: time them in an eager pass of the same step
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"loss": ll} if args.mode == "train" and args.graph else {"ll": ll, "z": z})
+    if args.graph and args.full:    # launches inside a replayed graph carry no events: time them in an eager pass of the same step
         lib.umnn_profile_enable(1)
         for _ in range(max(3, args.steps // 4)):
             eager_step()
@@ -343,7 +379,7 @@ def main():
     # (at least ~0.5 s of them), after the timed region -- the thread never competes with the launches that are timed.  Any failure
     # of the telemetry source leaves null fields, never takes the line down.
     telemetry = None
-    if rank == 0 and world == 1 and args.mode == "eval" and not args.no_telemetry:
+    if args.full and rank == 0 and world == 1 and args.mode == "eval" and not args.no_telemetry:
         try:
             from tools.telemetry import Sampler
             sampler = Sampler(device.index or 0)
@@ -360,7 +396,7 @@ def main():
         except Exception as e:
             telemetry = {"error": f"{type(e).__name__}: {e}"}
 
-    extras = world == 1 and args.mode == "eval" and not args.no_extras and args.scaling == "weak"
+    extras = args.full and world == 1 and args.mode == "eval" and not args.no_extras and args.scaling == "weak"
 
     def side_record(mode, peak, peak_name, conditioner):
         """The same workload, same steps / warm-up, under another arithmetic of the whole path (N = 1 eval only)."""
@@ -437,7 +473,7 @@ def main():
         avg_kernel_ms = dom[0] / max(1, dom[1])
         achieved = dom[2] / max(dom[0], 1e-9) / 1e9                    # TFLOP/s over those launches
         traffic, traffic_src = (None, "eval mode only") if args.mode != "eval" else \
-            hbm_traffic(args.workload, args.live_traffic, ["--precision", precision] if args.precision else [])
+            hbm_traffic(args.workload, args.live_traffic, ["--precision", precision] if args.precision else [], collect=args.full)
         on_bf16 = "bf16" in kernel_name or "f16" in kernel_name
         peak = PEAK_BF16_MFMA_TFLOPS if on_bf16 else PEAK_FP32_MFMA_TFLOPS
         # FLOPs the matrix pipe actually executes per launch in the bf16-split FORWARD kernels: per hidden->hidden layer
@@ -520,7 +556,11 @@ def main():
                 "backward_main": {"ms": bwd[0], "launches": bwd[1], "avg_launch_ms": bwd[0] / max(1, bwd[1])},
                 "backward_finishing": {"ms": fin[0], "launches": fin[1], "avg_ms": fin[0] / max(1, fin[1])},
                 "share_of_step": (fwd[0] + bwd[0] + fin[0]) / (1e3 * elapsed)}
-        if world == 1 and not args.no_cpu_baseline and args.mode == "eval":
+        if args.graph and not args.full:    # replayed launches carry no events, and the eager pass that times them is --full's
+            out["config"]["graph"] = "step replayed as one hipGraph; kernel timings with --full"
+            out["roofline"] = {"bound": "mfma", "kernel": kernel_name, "traffic": traffic, "traffic_source": traffic_src}
+            out.pop("train_kernels", None)
+        if args.full and world == 1 and not args.no_cpu_baseline and args.mode == "eval":
             out["cpu_baseline"] = cpu_baseline(cfg, model)
             out["cpu_baseline"]["gpu_over_cpu"] = value / out["cpu_baseline"]["value"]
             out["cpu_baseline"]["gpu_over_cpu_parallel_solver"] = value / out["cpu_baseline"]["solvers"]["parallel"]["evals_per_s"]

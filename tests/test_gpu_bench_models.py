@@ -236,6 +236,34 @@ def test_block_level_compute_ll_and_bis_on_the_hip_path(dev):
     assert U.rel_err(llb.sum(1).cpu().numpy(), ll_full_ref) < TOL
 
 
+def test_bench_plain_run_dumps_what_its_timed_step_computed(dev, tmp_path):
+    """A plain `bench.py --steps K --warmup W --dump-outputs DIR` line: K timed steps, ms_per_step, none of --full's records, and
+    ll.npy / z.npy equal to compute_ll of bench.py's own model and inputs (build_model seed 0, rank 0's inputs: seed 1000)."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--workload", "toy",
+           "--dump-outputs", str(tmp_path)]
+    r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0 and line["value"] > 0
+    assert line["higher_is_better"] is True and line["metric"] == "umnn_maf_log_density_evals_per_s"
+    assert not {"cpu_baseline", "exact_fp32", "bf16x6", "bf16x3", "f16x3", "full_batch_n1"} & set(line)
+    assert line["roofline"]["telemetry"] is None and line["roofline"]["launches"] > 0
+    cfg = dict(bench.WORKLOADS["toy"])
+    model = bench.build_model(cfg, dev)
+    x, _ = bench.make_inputs(cfg, cfg["rows"], dev, 1000)
+    with torch.no_grad():
+        ll, z = model.compute_ll(x)
+    got_ll, got_z = np.load(tmp_path / "ll.npy"), np.load(tmp_path / "z.npy")
+    assert got_ll.dtype == np.float32 and got_ll.shape == (cfg["rows"],) and got_z.shape == (cfg["rows"], cfg["d"])
+    np.testing.assert_allclose(got_ll, ll.cpu().numpy(), rtol=1e-6, atol=1e-6)
+    np.testing.assert_allclose(got_z, z.cpu().numpy(), rtol=1e-6, atol=1e-6)
+
+
 def test_bench_two_ranks_on_one_gpu_smoke(dev, tmp_path):
     """bench.py's N>1 launch path (torch.distributed.run, barrier + max-over-ranks timing, rank gathering, one JSON line on
     rank 0) on the single GPU of this box: two ranks share cuda:0 over gloo (RCCL refuses two ranks on one device; the

@@ -392,3 +392,23 @@ def test_bench_cpu_baseline_protocol_runs_on_a_small_workload():
         assert s["reps"] >= 3 and s["warmup"] >= 1 and s["chunks"] == 2 and isinstance(s["budget_limited"], bool)
         assert s["min_ms"] <= s["median_ms"] <= s["max_ms"]
     assert rec["value"] == max(s["evals_per_s"] for s in rec["solvers"].values())
+
+
+def test_bench_dump_outputs_keeps_one_seeded_row_sample_under_the_cap(tmp_path):
+    """bench.dump_outputs (`bench.py --dump-outputs DIR`): float32 (float64 kept) .npy files; above the 64 MB cap arrays of equal length
+    keep the SAME seeded sample of rows, in order, and a second call picks the same rows."""
+    import bench
+    rows, d = 300_000, 63                            # ll + z + t: 79 MB, over the cap
+    ll = torch.arange(rows, dtype=torch.float32)
+    z = ll[:, None].repeat(1, d)                     # (row indices < 2^24: exact in float32)
+    t = ll.double()
+    for sub in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / sub), {"ll": ll, "z": z.bfloat16() if sub == "b" else z, "t": t, "none": None})
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("ll", "z", "t")}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("ll", "z", "t")}
+    assert not (tmp_path / "a" / "none.npy").exists()
+    assert a["ll"].dtype == np.float32 and a["z"].dtype == np.float32 and b["z"].dtype == np.float32 and a["t"].dtype == np.float64
+    assert sum(v.nbytes for v in a.values()) <= bench.DUMP_LIMIT_BYTES < rows * (d + 3) * 4
+    assert a["z"].shape[1] == d and 0 < a["ll"].shape[0] == a["z"].shape[0] < rows
+    assert np.all(np.diff(a["ll"]) > 0) and np.array_equal(a["z"][:, 0], a["ll"]) and np.array_equal(a["t"], a["ll"])
+    assert np.array_equal(a["ll"], b["ll"])

@@ -2,7 +2,7 @@
 # One bench.py line per workload and mode -> gpurun_out/bench_lines.jsonl (copied to profiles/rNN/bench_lines.jsonl)
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 O=$R/gpurun_out/bench_lines.jsonl; : > $O
-run() { timeout 400 python $R/bench.py --no-cpu-baseline --no-extras --steps ${STEPS:-20} --warmup ${WARMUP:-5} "$@" 2>/dev/null | tail -1 >> $O; }
+run() { timeout 400 python $R/bench.py --full --no-cpu-baseline --no-extras --steps ${STEPS:-20} --warmup ${WARMUP:-5} "$@" 2>/dev/null | tail -1 >> $O; }
 fast() { STEPS=200 WARMUP=40 run "$@"; }          # the sub-3-ms steps: 200 timed steps
 run --workload bsds300
 run --workload bsds300 --precision fp32

@@ -7,6 +7,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 mkdir -p $R/gpurun_out
 NG=$(python -c "import torch; print(torch.cuda.device_count())")
 export HSA_ENABLE_IPC_MODE_LEGACY=0
+set -- --full "$@"        # the N = 1 line keeps its side records: full_batch_n1 is the anchor of the N = 8 point
 for N in 1 2 4 8; do
   [ "$N" -gt "$NG" ] && { echo "only $NG GPU(s) visible: stopping before N=$N"; break; }
   if [ "$N" -eq 1 ]; then

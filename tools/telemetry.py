@@ -3,7 +3,7 @@
 ``Sampler(device_index).start() ... .stop()`` polls the SMU's gpu_metrics table from a background thread (>= 20 Hz) and
 returns a summary: mean / max socket power, mean shader clock over the XCDs, the power cap, throttle bits.  Sources, first
 one that works: the ``amdsmi`` python bindings (one ``amdsmi_get_gpu_metrics_info`` call per sample), the amdgpu hwmon /
-pp_dpm sysfs files, the ``rocm-smi`` CLI (slow: ~3 Hz).  Used by ``bench.py`` (``roofline.sclk_mhz`` / ``power_w``) and by
+pp_dpm sysfs files, the ``rocm-smi`` CLI (slow: ~3 Hz).  Used by ``bench.py --full`` (``roofline.sclk_mhz`` / ``power_w``) and by
 ``tools/power_probe.py`` (the evidence behind DESIGN's "power-bound" statement).
 """
 import glob
