@@ -27,6 +27,7 @@ from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobi
 from .nets import compute_lipschitz_linear
 from .quadrature import compute_cc_weights
 from .graphs import GraphedLL, GraphedTrainStep
+from . import ops  # noqa: F401  (registers the torch.ops.umnn custom ops; loads no library)
 from ._lib import set_forward_precision, get_forward_precision, set_backward_precision, get_backward_precision
 
 

@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import integral as _I
+from . import ops as _ops
 from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, IntegralWithJacobianParams, _flatten  # noqa: F401
 from .made import MADE, ConditionnalMADE
 from .nets import ELUPlus, IntegrandNetwork, compute_lipschitz_linear, mlp_spec  # noqa: F401  (re-exported)
@@ -105,6 +106,10 @@ class UMNNMAF(nn.Module):
         h = self.net.make_embeding(x, context)
         d = x.shape[1]
         z0 = h.view(h.shape[0], -1, d)[:, 0, :]
+        if _I._graph_mode():
+            gspec = _I._graph_spec(integrand, x)
+            if gspec is not None:                   # (anything else: the generic path below)
+                return self._transform_graph(x, h, z0, gspec, x0, want_jac, reverse_z, log_jac_in)
         spec = mlp_spec(integrand)
         if self.nb_steps < 1:
             raise ValueError("UMNNMAF: nb_steps must be >= 1 when integrating (call set_steps_nb first)")
@@ -143,6 +148,35 @@ class UMNNMAF(nn.Module):
             log_jac = log_jac_in + log_jac
         return z, log_jac
 
+    def _transform_graph(self, x, h, z0, spec, x0, want_jac, reverse_z, log_jac_in):
+        """``_transform`` under torch.compile / export / jit.trace: the same choice of one-node, fused or composed block, with the
+        HIP launches as torch.ops.umnn ops.  No z_2 hand-off (the backward recomputes it: never a different result)."""
+        integrand = self.net.parallel_nets
+        if self.nb_steps < 1:
+            raise ValueError("UMNNMAF: nb_steps must be >= 1 when integrating (call set_steps_nb first)")
+        W, b, ha, oa = _ops.spec_args(spec)
+        no_graph = (not torch.is_grad_enabled()) or not (
+            x.requires_grad or h.requires_grad or (x0 is not None and x0.requires_grad)
+            or any(p.requires_grad for p in integrand.parameters()))
+        if no_graph and x0 is None:                 # (like eager's hip_flow_block call: no gradient for scaling on this path)
+            z, log_jac, _ = torch.ops.umnn.flow_block(x, h, self.scaling.detach(), W, b, ha, oa, self.nb_steps, reverse_z,
+                                                      log_jac_in)
+            return z, log_jac
+        x0 = x0.to(x.device) if x0 is not None else None
+        if (not no_graph and _I.fused_block_ok(x, h, self.scaling, x0, want_jac)
+                and (log_jac_in is None or log_jac_in.dtype == torch.float32)):
+            z, log_jac, _ = torch.ops.umnn.flow_block(x.contiguous(), h.contiguous(), self.scaling, W, b, ha, oa, self.nb_steps,
+                                                      reverse_z, log_jac_in)
+            return z, log_jac
+        F, fx = torch.ops.umnn.cc_forward(x0, x, h, W, b, ha, oa, self.nb_steps, False)
+        z = torch.exp(self.scaling).unsqueeze(0) * (F + z0)
+        log_jac = torch.log(fx + 1e-10) + self.scaling.unsqueeze(0) if want_jac else None
+        if reverse_z:
+            z = torch.flip(z, [1])
+        if log_jac_in is not None and log_jac is not None:
+            log_jac = log_jac_in + log_jac
+        return z, log_jac
+
     # ------------------------------------------------------------------ reference API
     def forward(self, x, method=None, x0=None, context=None):
         return self._transform(x, context, x0, want_jac=False)[0]
@@ -150,8 +184,13 @@ class UMNNMAF(nn.Module):
     def compute_log_jac(self, x, context=None):
         h = self.net.make_embeding(x, context)
         integrand = self.net.parallel_nets
-        spec = mlp_spec(integrand)
-        if _I._use_hip(spec, x):
+        gspec = _I._graph_spec(integrand, x) if _I._graph_mode() else None
+        spec = gspec if gspec is not None else mlp_spec(integrand)
+        if gspec is not None:
+            # graph mode: f(x;h) from a one-step umnn::cc_forward, differentiable through the op in every output
+            W, b, ha, oa = _ops.spec_args(gspec)
+            jac = torch.ops.umnn.cc_forward(None, x, h, W, b, ha, oa, 1, False)[1]
+        elif _I._use_hip(spec, x):
             # f(x;h) is quadrature node 0: a one-step launch of the forward kernel evaluates it (two nodes) without the
             # [B*d, 1+E] row matrix the reference materialises (UMNNMAF.py:136-139, 263-284)
             wants_graph = torch.is_grad_enabled() and (x.requires_grad or h.requires_grad
@@ -217,7 +256,17 @@ class UMNNMAF(nn.Module):
 
     def invert(self, z, iter=10, context=None):
         """Dimension-by-dimension bracket search: 10 candidates per round on [left,right] (starting at +-50), keep
-        the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232)."""
+        the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232).  Eager only:
+        compiled callers get an eager call; under torch.jit.trace it raises."""
+        if torch.jit.is_tracing():
+            raise RuntimeError("umnn_amd: UMNNMAF.invert cannot be traced by torch.jit.trace (data-dependent bracket search); "
+                               "call it eagerly")
+        if torch.compiler.is_compiling():
+            # (applied here, not as a decorator: torch.compiler.disable imports torch._dynamo, ~1 s at every package import)
+            return torch.compiler.disable(UMNNMAF._invert)(self, z, iter, context)
+        return self._invert(z, iter, context)
+
+    def _invert(self, z, iter=10, context=None):
         K = 10
         B, d = z.shape
         dev = z.device
@@ -342,6 +391,14 @@ class UMNNMAFFlow(nn.Module):
         return self._stack(x, context, False)[0]
 
     def invert(self, z, iter=10, context=None):
+        if torch.jit.is_tracing():
+            raise RuntimeError("umnn_amd: UMNNMAFFlow.invert cannot be traced by torch.jit.trace (data-dependent bracket "
+                               "search); call it eagerly")
+        if torch.compiler.is_compiling():           # (an eager call inside compiled code; see UMNNMAF.invert)
+            return torch.compiler.disable(UMNNMAFFlow._invert)(self, z, iter, context)
+        return self._invert(z, iter, context)
+
+    def _invert(self, z, iter=10, context=None):
         z = torch.flip(z, [1])
         for i in range(len(self.nets) - 1, -1, -1):
             z = self.nets[i].invert(torch.flip(z, [1]), iter, context=context)
@@ -367,7 +424,35 @@ class UMNNMAFFlow(nn.Module):
             return True
         return not (x.requires_grad or any(p.requires_grad for p in self.parameters()))
 
+    def _compute_ll_graph(self, x, context):
+        """``compute_ll`` under torch.compile / export / jit.trace: one-pass, fused or composed as in eager, through the ops."""
+        nb = len(self.nets)
+        specs = [_I._graph_spec(net.net.parallel_nets, x) for net in self.nets]
+        one_pass = (nb > 0 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and not torch.is_autocast_enabled()
+                    and all(net.solver in _SOLVERS and net.nb_steps >= 1 and spec is not None
+                            and net.net.embedding_dtype in (None, torch.float32) for net, spec in zip(self.nets, specs))
+                    and (not torch.is_grad_enabled() or not (x.requires_grad or any(p.requires_grad for p in self.parameters()))))
+        if one_pass:
+            with torch.no_grad():
+                x = x.contiguous()
+                ll = None
+                for i, (net, spec) in enumerate(zip(self.nets, specs)):
+                    h = net.net.make_embeding(x, context)
+                    W, b, ha, oa = _ops.spec_args(spec)
+                    x, ll = torch.ops.umnn.flow_ll_block(x, h.contiguous(), net.scaling, W, b, ha, oa, net.nb_steps, i + 1 < nb,
+                                                         i == 0, i + 1 == nb, ll)
+            return ll, x
+        z, log_jac = self._stack(x, context, True)
+        if (z.is_cuda and z.dtype == torch.float32 and log_jac.dtype == torch.float32 and z.dim() == 2 and torch.is_grad_enabled()
+                and (z.requires_grad or log_jac.requires_grad) and not torch.is_autocast_enabled()
+                and os.environ.get("UMNN_FUSED_TRAIN", "1") != "0"):
+            return torch.ops.umnn.flow_ll(z.contiguous(), log_jac.contiguous()), z
+        log_prob_gauss = -.5 * (torch.log(self.pi * 2) + z ** 2).sum(1)
+        return log_jac.sum(1) + log_prob_gauss, z
+
     def compute_ll(self, x, context=None):
+        if _I._graph_mode():
+            return self._compute_ll_graph(x, context)
         if self._one_pass_ok(x):
             # nb_flow x (conditioner + ONE launch): z, the running per-sample log-likelihood and the Gaussian term all
             # leave the quadrature kernel; no [B,d] log_jac accumulation, no elementwise epilogue (UMNNMAFFlow.py:109-119)

@@ -30,7 +30,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
-from .nets import mlp_spec
+from .nets import graph_spec, mlp_spec
 from .quadrature import compute_cc_weights, device_tables
 
 _state = threading.local()           # per-thread: last path taken, force_generic nesting
@@ -78,8 +78,28 @@ def _flatten(sequence):
 # ----------------------------------------------------------------------------------------------
 # HIP path
 # ----------------------------------------------------------------------------------------------
+def _graph_mode():
+    """True while torch.compile / torch.export trace a call (Dynamo) or torch.jit.trace records one: the HIP launches then
+    go through the ``torch.ops.umnn`` ops (ops.py), which the graph records, instead of ctypes calls it cannot see."""
+    return torch.compiler.is_compiling() or torch.jit.is_tracing()
+
+
+def traced_native_call():
+    """The error for a native pointer taken while torch.jit.trace records: the tracer would keep the output allocation and
+    drop the launch, so the traced graph would return uninitialised memory.  Names the function that took the pointer."""
+    import sys
+    fn = sys._getframe(2).f_code.co_name
+    return RuntimeError(f"umnn_amd: {fn}() passed a tensor to a native call while torch.jit.trace was recording; the trace "
+                        "would not contain that launch.  Traced code has to reach the HIP kernels through torch.ops.umnn "
+                        "(umnn_amd.ops).")
+
+
 def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+    if t is None:
+        return None
+    if torch._C._is_tracing():
+        raise traced_native_call()
+    return ctypes.c_void_p(t.data_ptr())
 
 
 _desc_cache = {}      # id(spec.linears[0]) -> (key, MlpDesc, keep-alive tensors)
@@ -98,7 +118,7 @@ def _desc(spec):
     d.n_linear = len(lins)
     d.widths[0] = lins[0].in_features
     keep = []
-    cacheable = True
+    cacheable = isinstance(lins[0], torch.nn.Module)     # (specs built from bare tensors, ops.py: rebuilt per call)
     for l, lin in enumerate(lins):
         w, b = lin.weight.detach(), lin.bias.detach()
         if not w.is_contiguous():
@@ -497,6 +517,37 @@ def aten_backward(integrand, x0, x, h, g, nb_steps, inv_f=False):
     return (_flatten(g_params) if params else None), g_h
 
 
+def _graph_spec(integrand, x):
+    """Graph mode: the MlpSpec when the HIP kernels apply (same rule as ``_use_hip``, without its thread-local switches), else None."""
+    spec = graph_spec(integrand)
+    if spec is None or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
+        return None
+    if spec.linears[0].weight.device != x.device:
+        raise RuntimeError("umnn_amd: integrand weights and inputs are on different devices")
+    return spec
+
+
+def _graph_forward(ctx, spec, x0, x, h, nb_steps, inv_f, jac):
+    """Forward of the autograd Functions below in graph mode: ``umnn::cc_forward``, and for the backward only tensors and
+    plain values on ``ctx`` (Dynamo traces both methods; they may call nothing but torch.ops.umnn and ATen).  -> (F, f_x)"""
+    W, b = [l.weight for l in spec.linears], [l.bias for l in spec.linears]
+    ctx.graph = (spec.hidden_act, spec.out_act, int(nb_steps), bool(inv_f), bool(jac), len(W), x0 is None)
+    ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
+    return torch.ops.umnn.cc_forward(x0, x, h, W, b, spec.hidden_act, spec.out_act, int(nb_steps), bool(inv_f))
+
+
+def _graph_backward(ctx, gF, gfx, need):
+    """-> (dx0, dx, dh, dtheta_flat) through ``umnn::cc_backward`` (which picks the HIP or the ATen backward when it runs);
+    None where need[...] is False.  ``gfx`` is dropped for operators whose f_x output is not theirs (jac False)."""
+    ha, oa, nb_steps, inv_f, jac, L, x0_none = ctx.graph
+    saved = ctx.saved_tensors
+    x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
+    x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
+    need = [bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3])]
+    out = torch.ops.umnn.cc_backward(x0, x, h, gF, gfx if jac else None, W, b, ha, oa, nb_steps, need, inv_f)
+    return tuple(t if n else None for t, n in zip(out, need))
+
+
 class IntegralWithJacobianParams(torch.autograd.Function):
     """IntegralWithJacobian with the integrand's parameters passed one by one instead of as one flat tensor: no
     ``torch.cat`` in the forward and no cat-backward (a narrow + copy per parameter) in the backward -- the gradients are
@@ -505,6 +556,11 @@ class IntegralWithJacobianParams(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x, integrand, h, nb_steps, *params):
+        if _graph_mode():
+            spec = _graph_spec(integrand, x)
+            if spec is None:
+                raise RuntimeError("IntegralWithJacobianParams needs an MLP integrand on a GPU")
+            return _graph_forward(ctx, spec, x0, x, h, nb_steps, False, True)
         spec = mlp_spec(integrand)
         if not _use_hip(spec, x):
             raise RuntimeError("IntegralWithJacobianParams needs an MLP integrand on a GPU")
@@ -521,6 +577,10 @@ class IntegralWithJacobianParams(torch.autograd.Function):
     @staticmethod
     @once_differentiable        # double backward (create_graph=True through the quadrature) raises instead of silently detaching
     def backward(ctx, gF, gfx):
+        if getattr(ctx, "graph", None) is not None:
+            nig = ctx.needs_input_grad
+            dx0, dx, dh, dtheta = _graph_backward(ctx, gF, gfx, (nig[0], nig[1], nig[3], any(nig[5:])))
+            return (dx0, dx, None, dh, None, *_split(dtheta, ctx.graph[5], ctx.saved_tensors[-2 * ctx.graph[5]:], nig[5:]))
         if ctx.x0_none:
             (x, h), x0 = ctx.saved_tensors, None
         else:
@@ -542,6 +602,40 @@ class IntegralWithJacobianParams(torch.autograd.Function):
 
 def _stream(device):
     return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
+def hip_flow_block_cotangents(gz, glj, fx, scaling, reverse_z):
+    """Cotangents of F and f_x of a flow block from those of z and log_jac (umnn_flow_block_cotangents) -> (gF, gfx or None)."""
+    B, d = fx.shape
+    gF, gfx = torch.empty_like(fx), (torch.empty_like(fx) if glj is not None else None)
+    with torch.cuda.device(fx.device):
+        rc = _lib.lib().umnn_flow_block_cotangents(_ptr(gz), _ptr(glj), _ptr(fx), _ptr(scaling), B, d, 1 if reverse_z else 0,
+                                                   _ptr(gF), _ptr(gfx), _stream(fx.device))
+    _lib.check(rc, "umnn_flow_block_cotangents")
+    return gF, gfx
+
+
+def hip_flow_ll(z, log_jac):
+    """ll [B] fp32 of a flow from its z and summed log_jac (umnn_flow_ll_forward)."""
+    z, log_jac = z.contiguous(), log_jac.contiguous()
+    B, d = z.shape
+    ll = torch.empty(B, device=z.device, dtype=torch.float32)
+    with torch.cuda.device(z.device):
+        rc = _lib.lib().umnn_flow_ll_forward(_ptr(z), _ptr(log_jac), B, d, _ptr(ll), _stream(z.device))
+    _lib.check(rc, "umnn_flow_ll_forward")
+    return ll
+
+
+def hip_flow_ll_backward(z, g_ll, need_z, need_lj):
+    """-> (gz, glj) of hip_flow_ll for the cotangent g_ll (umnn_flow_ll_backward); None where not needed."""
+    B, d = z.shape
+    g_ll = g_ll.contiguous()
+    gz = torch.empty_like(z) if need_z else None
+    glj = torch.empty_like(z) if need_lj else None
+    with torch.cuda.device(z.device):
+        rc = _lib.lib().umnn_flow_ll_backward(_ptr(z), _ptr(g_ll), B, d, _ptr(gz), _ptr(glj), _stream(z.device))
+    _lib.check(rc, "umnn_flow_ll_backward")
+    return gz, glj
 
 
 class FlowBlockTransform(torch.autograd.Function):
@@ -572,15 +666,10 @@ class FlowBlockTransform(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gz, glj):
         x, h, fx, scaling = ctx.saved_tensors
-        lib = _lib.lib()
         B, d = x.shape
         gz = None if gz is None else gz.contiguous()
         glj = None if glj is None else glj.contiguous()
-        gF, gfx = torch.empty_like(x), (torch.empty_like(x) if glj is not None else None)
-        with torch.cuda.device(x.device):
-            rc = lib.umnn_flow_block_cotangents(_ptr(gz), _ptr(glj), _ptr(fx), _ptr(scaling), B, d, 1 if ctx.reverse_z else 0,
-                                                _ptr(gF), _ptr(gfx), _stream(x.device))
-        _lib.check(rc, "umnn_flow_block_cotangents")
+        gF, gfx = hip_flow_block_cotangents(gz, glj, fx, scaling, ctx.reverse_z)
         if not _hip_backward_ok(ctx.spec, x, h):
             _, dx, dh, dtheta = aten_backward_jac(ctx.integrand, torch.zeros_like(x), x, h, gF, gfx, ctx.nb_steps)
         else:
@@ -602,27 +691,15 @@ class FlowLogLikelihood(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, z, log_jac):
-        z, log_jac = z.contiguous(), log_jac.contiguous()
-        B, d = z.shape
-        ll = torch.empty(B, device=z.device, dtype=torch.float32)
-        with torch.cuda.device(z.device):
-            rc = _lib.lib().umnn_flow_ll_forward(_ptr(z), _ptr(log_jac), B, d, _ptr(ll), _stream(z.device))
-        _lib.check(rc, "umnn_flow_ll_forward")
-        ctx.save_for_backward(z)
+        ll = hip_flow_ll(z, log_jac)
+        ctx.save_for_backward(z.contiguous())
         return ll
 
     @staticmethod
     @once_differentiable
     def backward(ctx, g_ll):
         (z,) = ctx.saved_tensors
-        B, d = z.shape
-        g_ll = g_ll.contiguous()
-        gz = torch.empty_like(z) if ctx.needs_input_grad[0] else None
-        glj = torch.empty_like(z) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(z.device):
-            rc = _lib.lib().umnn_flow_ll_backward(_ptr(z), _ptr(g_ll), B, d, _ptr(gz), _ptr(glj), _stream(z.device))
-        _lib.check(rc, "umnn_flow_ll_backward")
-        return gz, glj
+        return hip_flow_ll_backward(z, g_ll, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
 
 
 def fused_block_ok(x, h, scaling, x0, want_jac):
@@ -643,6 +720,19 @@ def integrate(x0, nb_steps, step_sizes, integrand, h, compute_grad=False, x_tot=
     (what the reference's backward consumes).  ``cc_weights``/``steps`` are accepted for signature parity; the
     tables are a pure function of nb_steps and come from the per-device cache."""
     x = x0 + nb_steps * step_sizes
+    gspec = _graph_spec(integrand, x) if _graph_mode() else None
+    if gspec is not None:
+        # graph mode: the same choices as below, with the launches as torch.ops.umnn ops (ParallelNeuralIntegral routes itself)
+        W, b = [l.weight for l in gspec.linears], [l.bias for l in gspec.linears]
+        if not compute_grad:
+            if torch.is_grad_enabled() and (x.requires_grad or (h is not None and h.requires_grad)
+                                            or any(p.requires_grad for p in integrand.parameters())):
+                return ParallelNeuralIntegral.apply(x0, x, integrand, _flatten(integrand.parameters()), h, nb_steps, inv_f)
+            return torch.ops.umnn.cc_forward(x0, x, h, W, b, gspec.hidden_act, gspec.out_act, int(nb_steps), bool(inv_f))[0]
+        with torch.no_grad():                       # (like the eager call: the gradients themselves are not differentiated)
+            _, _, dh, dtheta = torch.ops.umnn.cc_backward(x0, x, h, x_tot, None, W, b, gspec.hidden_act, gspec.out_act,
+                                                          int(nb_steps), [False, False, True, True], bool(inv_f))
+        return dtheta, dh
     spec = mlp_spec(integrand)
     if not compute_grad:
         # The reference's direct integration is plain ATen, hence differentiable by ordinary autograd
@@ -664,7 +754,21 @@ def integrate(x0, nb_steps, step_sizes, integrand, h, compute_grad=False, x_tot=
     return aten_backward(integrand, x0, x, h, x_tot, nb_steps, inv_f)
 
 
+def _split(dtheta, L, Wb, needed):
+    """Graph mode: flat d_theta -> per-parameter views, in parameters() order (W_0, b_0, W_1, ...); ``Wb`` the saved W[] + b[]."""
+    params = [p for pair in zip(Wb[:L], Wb[L:]) for p in pair]
+    grads, o = [], 0
+    for p, n in zip(params, needed):
+        grads.append(dtheta[o:o + p.numel()].view(p.shape) if (n and dtheta is not None) else None)
+        o += p.numel()
+    return grads
+
+
 def _op_forward(ctx, x0, x, integrand, h, nb_steps, inv_f):
+    if _graph_mode():
+        spec = _graph_spec(integrand, x)
+        if spec is not None:
+            return _graph_forward(ctx, spec, x0, x, h, nb_steps, inv_f, False)[0]
     ctx.integrand, ctx.nb_steps, ctx.inv_f = integrand, nb_steps, inv_f
     spec = mlp_spec(integrand)
     ctx.spec = spec
@@ -677,6 +781,10 @@ def _op_forward(ctx, x0, x, integrand, h, nb_steps, inv_f):
 
 
 def _op_backward(ctx, grad_output):
+    if getattr(ctx, "graph", None) is not None:
+        nig = ctx.needs_input_grad
+        dx0, dx, dh, dtheta = _graph_backward(ctx, grad_output, None, (nig[0], nig[1], nig[4], nig[3]))
+        return dx0, dx, dtheta, dh
     x0, x, h = ctx.saved_tensors
     integrand, nb_steps, inv_f, spec = ctx.integrand, ctx.nb_steps, ctx.inv_f, ctx.spec
     if ctx.use_hip and _hip_backward_ok(spec, x, h):
@@ -722,6 +830,11 @@ class IntegralWithJacobian(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x, integrand, flat_params, h, nb_steps):
+        if _graph_mode():
+            spec = _graph_spec(integrand, x)
+            if spec is None:
+                raise RuntimeError("IntegralWithJacobian needs an MLP integrand on a GPU")
+            return _graph_forward(ctx, spec, x0, x, h, nb_steps, False, True)
         spec = mlp_spec(integrand)
         if not _use_hip(spec, x):
             raise RuntimeError("IntegralWithJacobian needs an MLP integrand on a GPU")
@@ -733,6 +846,10 @@ class IntegralWithJacobian(torch.autograd.Function):
     @staticmethod
     @once_differentiable        # double backward (create_graph=True through the quadrature) raises instead of silently detaching
     def backward(ctx, gF, gfx):
+        if getattr(ctx, "graph", None) is not None:
+            nig = ctx.needs_input_grad
+            dx0, dx, dh, dtheta = _graph_backward(ctx, gF, gfx, (nig[0], nig[1], nig[4], nig[3]))
+            return dx0, dx, None, dtheta, dh, None
         x0, x, h = ctx.saved_tensors
         if not _hip_backward_ok(ctx.spec, x, h):
             dx0, dx, dh, dtheta = aten_backward_jac(ctx.integrand, x0, x, h, gF, gfx, ctx.nb_steps)

@@ -25,6 +25,18 @@ import torch.nn as nn
 import torch.nn.functional as F
 
 
+def _graph_mode():
+    return torch.compiler.is_compiling() or torch.jit.is_tracing()
+
+
+def _ptr(t):
+    """data_ptr() for a native call; raises under torch.jit.trace, which would record the output allocation and drop the launch."""
+    if torch._C._is_tracing():
+        from .integral import traced_native_call
+        raise traced_native_call()
+    return t.data_ptr()
+
+
 _capture_state = threading.local()      # .cache_ok: a capture on THIS thread that tracks weight versions itself (GraphedLL)
 
 
@@ -134,6 +146,8 @@ class MaskedLinear(nn.Linear):
         return self._frags[1]
 
     def forward(self, input):
+        if _graph_mode():           # the reference's composition (made.py:26-27): no cache keyed on versions or pointers
+            return F.linear(input, self.mask * self.weight, self.bias)
         return F.linear(input, self.masked_weight(), self.bias)
 
 
@@ -224,8 +238,8 @@ def _fast_chain(a, layers, last_rows=None, out_dtype=None):
             last = i == len(layers) - 1
             packed = layer.packed_bf16(last_rows if last else None)
             op = torch.empty(raw.shape[0], packed.shape[1], dtype=torch.bfloat16, device=a.device)
-            _lib.check(lib.umnn_made_split3(raw.data_ptr(), raw.shape[0], raw.shape[1], 1 if i > 0 else 0,
-                                            op.data_ptr(), op.shape[1], stream), "made_split3")
+            _lib.check(lib.umnn_made_split3(_ptr(raw), raw.shape[0], raw.shape[1], 1 if i > 0 else 0,
+                                            _ptr(op), op.shape[1], stream), "made_split3")
             if last and out_dtype == torch.bfloat16:
                 raw = torch.mm(op, packed.t())                       # bf16 out, fp32 accumulate inside the GEMM
             else:
@@ -292,18 +306,18 @@ def _fused_chain(a, layers, last_rows=None, out_dtype=None, mode=1):
         frags, bias = layer.packed_fragments(last_rows if (mode == 1 and i == len(inner) - 1) else None)
         keep += [frags, bias]
         net.widths[i + 1] = bias.shape[0]
-        net.W[i], net.b[i] = frags.data_ptr(), bias.data_ptr()
+        net.W[i], net.b[i] = _ptr(frags), _ptr(bias)
     bf16 = out_dtype == torch.bfloat16
     with torch.cuda.device(a.device):
         stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
         if mode == 1:
             out = torch.empty(a.shape[0], net.widths[len(inner)], device=a.device, dtype=torch.bfloat16 if bf16 else torch.float32)
-            _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), a.data_ptr(), a.shape[0], out.data_ptr(), 1 if bf16 else 0, 0,
+            _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), _ptr(a), a.shape[0], _ptr(out), 1 if bf16 else 0, 0,
                                                     stream), "umnn_made_mlp_forward")
             return out
         packed = layers[-1].packed_bf16(last_rows)                      # [N, pad8(3K+2)]: the per-layer path's weight operand
         op = torch.empty(a.shape[0], packed.shape[1], dtype=torch.bfloat16, device=a.device)
-        _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), a.data_ptr(), a.shape[0], op.data_ptr(), 2, op.shape[1], stream),
+        _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), _ptr(a), a.shape[0], _ptr(op), 2, op.shape[1], stream),
                    "umnn_made_mlp_forward")
     if bf16:
         return torch.mm(op, packed.t())                                  # bf16 out, fp32 accumulate inside the GEMM
@@ -334,14 +348,14 @@ def _layered_chain(a, layers, last_rows=None, out_dtype=None, a2=None):
             if last and i > 0 and B > _LAYERED_LIB_OUT_ROWS and layer.out_features > 512:
                 packed = layer.packed_bf16(last_rows)                   # [N, pad8(3K+2)]: the library route's weight operand
                 op = torch.empty(B, packed.shape[1], dtype=torch.bfloat16, device=a.device)
-                _lib.check(lib.umnn_made_split3(cur.data_ptr(), B, cur.shape[1], 1, op.data_ptr(), op.shape[1], stream), "made_split3")
+                _lib.check(lib.umnn_made_split3(_ptr(cur), B, cur.shape[1], 1, _ptr(op), op.shape[1], stream), "made_split3")
                 return torch.mm(op, packed.t()) if bf16 else torch.mm(op, packed.t(), out_dtype=torch.float32)
             frags, bias = layer.packed_fragments(last_rows if last else None)
             out = torch.empty(B, bias.shape[0], device=a.device, dtype=torch.bfloat16 if bf16 else torch.float32)
             K = cur.shape[1] + (0 if cur2 is None else cur2.shape[1])
-            _lib.check(lib.umnn_made_linear_forward(frags.data_ptr(), bias.data_ptr(), K, bias.shape[0], cur.data_ptr(),
-                                                    None if cur2 is None else cur2.data_ptr(), cur.shape[1], B, 1 if i > 0 else 0,
-                                                    out.data_ptr(), 1 if bf16 else 0, rt, fg, stream), "umnn_made_linear_forward")
+            _lib.check(lib.umnn_made_linear_forward(_ptr(frags), _ptr(bias), K, bias.shape[0], _ptr(cur),
+                                                    None if cur2 is None else _ptr(cur2), cur.shape[1], B, 1 if i > 0 else 0,
+                                                    _ptr(out), 1 if bf16 else 0, rt, fg, stream), "umnn_made_linear_forward")
             cur, cur2 = out, None
     return cur
 
@@ -415,8 +429,8 @@ class _MadeTrainChain(torch.autograd.Function):
                     rb = int(lib.umnn_made_relu_bwd_bias_row_blocks(B, N))
                     partial = torch.empty(rb * N, device=g.device, dtype=torch.float32)
                     gb = torch.empty(N, device=g.device, dtype=torch.float32)
-                    _lib.check(lib.umnn_made_relu_bwd_bias(g.data_ptr(), None if relu_out is None else relu_out.data_ptr(), B, N,
-                                                           partial.data_ptr(), rb, gb.data_ptr(), stream), "umnn_made_relu_bwd_bias")
+                    _lib.check(lib.umnn_made_relu_bwd_bias(_ptr(g), None if relu_out is None else _ptr(relu_out), B, N,
+                                                           _ptr(partial), rb, _ptr(gb), stream), "umnn_made_relu_bwd_bias")
                     if need_b:
                         if last and keep is not None:
                             full = torch.zeros_like(layer.bias)
@@ -501,6 +515,9 @@ class MADE(nn.Module):
     def raw(self, x, out_dtype=None):
         """The masked MLP itself (what the flow's EmbeddingNetwork needs, whatever nout is)."""
         x = _to_weight_dtype(x, self.net[0])
+        if _graph_mode():           # torch.compile / export / jit.trace: fp32 F.linear + ReLU, as the reference composes it
+            out = self.net(x)
+            return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
         if _fast_path_ok(x):
             layers = [l for l in self.net if isinstance(l, MaskedLinear)]
             mode = _fused_ok(x, layers)
@@ -535,8 +552,8 @@ class MADE(nn.Module):
                 if last:
                     packed = packed.index_select(0, rows)
                 op = torch.empty(raw.shape[0], packed.shape[1], dtype=torch.bfloat16, device=x.device)
-                _lib.check(lib.umnn_made_split3(raw.data_ptr(), raw.shape[0], raw.shape[1], 1 if i > 0 else 0,
-                                                op.data_ptr(), op.shape[1], stream), "made_split3")
+                _lib.check(lib.umnn_made_split3(_ptr(raw), raw.shape[0], raw.shape[1], 1 if i > 0 else 0,
+                                                _ptr(op), op.shape[1], stream), "made_split3")
                 raw = torch.mm(op, packed.t(), out_dtype=torch.float32)
         return raw
 
@@ -589,6 +606,10 @@ class ConditionnalMADE(MADE):
     def raw(self, x, context, out_dtype=None):
         if context.dtype != x.dtype:
             context = context.to(x.dtype)
+        if _graph_mode():           # the reference's ConditionnalMADE.forward (made.py:165-168) on the fp32 F.linear chain
+            out = self.net(_to_weight_dtype(torch.cat((context, x), 1), self.net[0]))
+            out = out.view(x.shape[0], out.shape[1] // self.nin, self.nin)[:, :, self.cond_in:].reshape(x.shape[0], -1)
+            return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
         if x.dtype == context.dtype == torch.float32 == self.net[0].weight.dtype and _fast_path_ok(x):
             layers = [l for l in self.net if isinstance(l, MaskedLinear)]
             if _fused_ok(x, layers, self.nin_non_cond * (self.nout // self.nin)) == 3:    # the kernel reads both blocks: no cat

@@ -18,6 +18,20 @@ from . import _lib
 MlpSpec = namedtuple("MlpSpec", "linears hidden_act out_act")
 
 
+class TensorLinear:
+    """Stands in for an ``nn.Linear`` in an MlpSpec built from bare tensors (the ``torch.ops.umnn`` ops get W[] and b[],
+    never a module)."""
+    __slots__ = ("weight", "bias", "in_features", "out_features")
+
+    def __init__(self, weight, bias):
+        self.weight, self.bias = weight, bias
+        self.out_features, self.in_features = weight.shape
+
+
+def spec_from_tensors(W, b, hidden_act, out_act):
+    return MlpSpec([TensorLinear(w, bb) for w, bb in zip(W, b)], int(hidden_act), int(out_act))
+
+
 class ELUPlus(nn.Module):
     """ELU(x) + 1  (UMNNMAF.py:11-16); the submodule name ``elu`` is part of the reference's module tree."""
 
@@ -174,6 +188,12 @@ def mlp_spec(integrand):
     if isinstance(net, nn.Sequential):
         integrand.__dict__["_umnn_spec_cache"] = (net, _spec_key(net), spec)
     return spec
+
+
+def graph_spec(integrand):
+    """``mlp_spec`` without its cache, for traced code (torch.compile / export / jit.trace): pure attribute reads, no write to
+    the module."""
+    return _mlp_spec_uncached(integrand) if isinstance(integrand, nn.Module) else None
 
 
 def _spec_key(net):

@@ -1,0 +1,415 @@
+"""The HIP entry points as ``torch.library`` custom ops (namespace ``umnn``): what torch.compile, torch.export and
+torch.jit.trace record instead of the ctypes calls they cannot see.
+
+    umnn::cc_forward(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)
+    umnn::cc_backward(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
+    umnn::flow_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, log_jac_in?) -> (z, log_jac, f_x)
+    umnn::flow_block_backward(x, h, scaling, f_x, gz, glj, W[], b[], hidden_act, out_act, nb_steps, reverse_z, need[3])
+        -> (dx, dh, dtheta)
+    umnn::flow_ll(z, log_jac) -> ll
+    umnn::flow_ll_backward(z, g_ll) -> (gz, glj)
+    umnn::flow_ll_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, first, last, ll_in?) -> (z, ll)
+
+The integrand crosses the op boundary as tensors and plain values -- the fields of ``nets.MlpSpec`` -- never as a module.  Every
+implementation calls the eager path's own ``integral.hip_*`` function (same arithmetic mode, overflow fallback and
+``path_taken()`` bookkeeping); every output is a fresh tensor and no op writes an input.  Outputs an op is told it need not
+compute (``need``) come back as empty tensors.  cc_forward, flow_block and flow_ll are differentiable (their backward is the
+matching op; flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
+flow_ll_block are not.  Registration loads no library and touches no GPU.
+
+The ops are public, so every real and fake implementation first checks what it was given (``_check_*``): one CUDA device for
+every tensor, an integrand the kernels take (fp32 weights, the widths ``nets.mlp_spec`` accepts), x [B,d] / h [B,E*d] and the
+shapes of the other operands against them, and fp32 where the entry point is fp32-only.  Anything else raises a RuntimeError --
+at trace time through the fakes -- before a pointer reaches the kernels.
+"""
+from typing import List, Optional
+
+import torch
+import torch.nn.functional as F
+from torch import Tensor
+
+from . import _lib
+from . import integral as _I
+from .nets import spec_from_tensors
+from .quadrature import device_tables
+
+_FLOATS = (torch.float32, torch.bfloat16, torch.float16)
+_F32 = (torch.float32,)
+
+
+# ---------------------------------------------------------------------------------------------------------- argument checks
+def _req(op, cond, msg):
+    torch._check(cond, lambda: f"umnn::{op}: {msg}")
+
+
+def _check_tensor(op, name, t, x, shape, dtypes):
+    """``t`` on x's device, of ``shape`` (a tuple that may hold x's symbolic sizes) and one of ``dtypes``."""
+    _req(op, t.device == x.device, f"{name} is on {t.device}, x on {x.device}")
+    _req(op, t.dtype in dtypes, f"{name} has dtype {t.dtype}; expected {' or '.join(str(d) for d in dtypes)}")
+    _req(op, t.dim() == len(shape), f"{name} has {t.dim()} dimensions; expected {len(shape)}")
+    for i, n in enumerate(shape):
+        _req(op, t.shape[i] == n, f"{name} has shape {tuple(t.shape)}; expected {tuple(shape)}")
+
+
+def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS):
+    """x [B,d] and h [B,E*d] on one CUDA device, W[] / b[] an integrand MLP the kernels take (the rules of
+    nets._spec_from_sequential) on that device.  -> (B, d)."""
+    _req(op, x.device.type == "cuda", f"x is on {x.device}; the HIP kernels need CUDA tensors")
+    _req(op, x.dim() == 2, f"x has shape {tuple(x.shape)}; expected [B, d]")
+    _req(op, x.dtype in x_dtypes, f"x has dtype {x.dtype}; expected {' or '.join(str(d) for d in x_dtypes)}")
+    _req(op, len(W) == len(b) and 2 <= len(W) <= _lib.MAX_LINEAR,
+         f"the integrand needs 2 to {_lib.MAX_LINEAR} layers with one bias each (got {len(W)} weights, {len(b)} biases)")
+    _req(op, hidden_act in (_lib.ACT_LEAKY_RELU, _lib.ACT_RELU), f"unknown hidden_act {hidden_act}")
+    _req(op, out_act in (_lib.OUT_ELU_PLUS_ONE, _lib.OUT_SIGMOID), f"unknown out_act {out_act}")
+    for l, (w, bb) in enumerate(zip(W, b)):
+        _req(op, w.dim() == 2 and bb.dim() == 1 and bb.shape[0] == w.shape[0],
+             f"layer {l}: W {tuple(w.shape)} and b {tuple(bb.shape)} are not [out, in] and [out]")
+        for name, t in ((f"W[{l}]", w), (f"b[{l}]", bb)):
+            _req(op, t.device == x.device, f"{name} is on {t.device}, x on {x.device}")
+            _req(op, t.dtype == torch.float32, f"{name} has dtype {t.dtype}; the integrand weights must be fp32")
+        if l > 0:
+            _req(op, w.shape[1] == W[l - 1].shape[0], f"layer {l} takes {w.shape[1]} inputs, layer {l - 1} gives {W[l - 1].shape[0]}")
+        if l + 1 < len(W):
+            _req(op, w.shape[0] <= 127, f"hidden layer {l} has {w.shape[0]} units; the kernels take at most 127")
+    _req(op, W[-1].shape[0] == 1, f"the integrand's last layer has {W[-1].shape[0]} outputs; expected 1")
+    E = W[0].shape[1] - 1
+    _req(op, E >= 1, "the integrand's first layer takes fewer than 2 inputs")
+    B, d = x.shape
+    _check_tensor(op, "h", h, x, (B, E * d), h_dtypes)
+    return B, d
+
+
+def _check_need(op, need, n):
+    _req(op, len(need) == n, f"need has {len(need)} entries; expected {n}")
+
+
+def _check_cc(op, x0, x, h, W, b, hidden_act, out_act, g=None, g_fx=None):
+    B, d = _check_net(op, x, h, W, b, hidden_act, out_act)
+    for name, t in (("x0", x0), ("g", g), ("g_fx", g_fx)):
+        if t is not None:
+            _check_tensor(op, name, t, x, (B, d), _FLOATS)
+
+
+def _check_block(op, x, h, scaling, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS, s_dtypes=_FLOATS):
+    B, d = _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes, h_dtypes)
+    _check_tensor(op, "scaling", scaling, x, (d,), s_dtypes)
+    return B, d
+
+
+def _check_cc_forward(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
+    _check_cc("cc_forward", x0, x, h, W, b, hidden_act, out_act)
+
+
+def _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc("cc_backward", x0, x, h, W, b, hidden_act, out_act, g, g_fx)
+    _check_need("cc_backward", need, 4)
+
+
+def _check_flow_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, log_jac_in):
+    B, d = _check_block("flow_block", x, h, scaling, W, b, hidden_act, out_act)
+    if log_jac_in is not None:
+        _check_tensor("flow_block", "log_jac_in", log_jac_in, x, (B, d), _FLOATS)
+
+
+def _check_flow_block_backward(x, h, scaling, fx, gz, glj, W, b, hidden_act, out_act, nb_steps, reverse_z, need):
+    # (umnn_flow_block_cotangents is fp32-only: f_x, the cotangents and scaling; the training block stores x in fp32)
+    op = "flow_block_backward"
+    B, d = _check_block(op, x, h, scaling, W, b, hidden_act, out_act, _F32, (torch.float32, torch.bfloat16), _F32)
+    for name, t in (("fx", fx), ("gz", gz), ("glj", glj)):
+        _check_tensor(op, name, t, x, (B, d), _F32)
+    _check_need(op, need, 3)
+
+
+def _check_z(op, z):
+    # (umnn_flow_ll_forward / _backward are fp32-only)
+    _req(op, z.device.type == "cuda", f"z is on {z.device}; the HIP kernels need CUDA tensors")
+    _req(op, z.dim() == 2, f"z has shape {tuple(z.shape)}; expected [B, d]")
+    _check_tensor(op, "z", z, z, tuple(z.shape), _F32)
+
+
+def _check_flow_ll(z, log_jac):
+    _check_z("flow_ll", z)
+    _check_tensor("flow_ll", "log_jac", log_jac, z, tuple(z.shape), _F32)
+
+
+def _check_flow_ll_backward(z, g_ll):
+    _check_z("flow_ll_backward", z)
+    _check_tensor("flow_ll_backward", "g_ll", g_ll, z, (z.shape[0],), _F32)
+
+
+def _check_flow_ll_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last, ll_in):
+    # (umnn_flow_ll_block_forward is fp32-only: x, h, scaling and ll)
+    B, d = _check_block("flow_ll_block", x, h, scaling, W, b, hidden_act, out_act, _F32, _F32, _F32)
+    _req("flow_ll_block", first == (ll_in is None), "ll_in must be given exactly when first is False")
+    if ll_in is not None:
+        _check_tensor("flow_ll_block", "ll_in", ll_in, x, (B,), _F32)
+
+
+# ---------------------------------------------------------------------------------------------------------- helpers
+def _n_params(W, b):
+    return sum(w.numel() for w in W) + sum(bb.numel() for bb in b)
+
+
+def _empty(like, dtype=None):
+    return like.new_empty((0,), dtype=dtype)
+
+
+def _param_grads(dtheta, W, b, need_W, need_b):
+    """Flat d_theta -> ([dW_l], [db_l]) views (integral._split), None where not needed."""
+    grads = _I._split(dtheta, len(W), list(W) + list(b), [n for pair in zip(need_W, need_b) for n in pair])
+    return grads[0::2], grads[1::2]
+
+
+# ---------------------------------------------------------------------------------------------------------- quadrature
+@torch.library.custom_op("umnn::cc_forward", mutates_args=(), device_types="cuda")
+def cc_forward(x0: Optional[Tensor], x: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
+               nb_steps: int, inv_f: bool) -> tuple[Tensor, Tensor]:
+    _check_cc_forward(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f)
+    F_, fx, _ = _I.hip_forward(spec_from_tensors(W, b, hidden_act, out_act), x0, x, h, nb_steps, inv_f)
+    return F_, fx
+
+
+@cc_forward.register_fake
+def _(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
+    _check_cc_forward(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f)
+    return x.new_empty(x.shape), x.new_empty(x.shape)
+
+
+def _cc_forward_setup(ctx, inputs, output):
+    x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f = inputs
+    ctx.meta = (hidden_act, out_act, nb_steps, inv_f, len(W), x0 is None)
+    ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
+
+
+def _cc_forward_backward(ctx, gF, gfx):
+    hidden_act, out_act, nb_steps, inv_f, L, x0_none = ctx.meta
+    saved = ctx.saved_tensors
+    x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
+    x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
+    nig = ctx.needs_input_grad
+    need = [bool(nig[0]) and not x0_none, bool(nig[1]), bool(nig[2]), any(nig[3]) or any(nig[4])]
+    dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward(x0, x, h, gF, gfx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[3], nig[4])
+    return (dx0 if need[0] else None, dx if need[1] else None, dh if need[2] else None, gW, gb,
+            None, None, None, None)
+
+
+cc_forward.register_autograd(_cc_forward_backward, setup_context=_cc_forward_setup)
+
+
+def _mlp(params, hidden_act, out_act, rows):
+    a = rows
+    L = len(params) // 2
+    for l in range(L):
+        a = F.linear(a, params[2 * l], params[2 * l + 1])
+        if l + 1 < L:
+            a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
+    return F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)
+
+
+def _integrand(params, hidden_act, out_act, x, h):
+    """f(x; h) [B,d] of the integrand MLP on the rows [x_i, h_{0,i}, ..., h_{E-1,i}] (nets.IntegrandNetwork.rows)."""
+    B, d = x.shape
+    rows = torch.cat((x, h), 1).view(B, -1, d).transpose(1, 2).reshape(B * d, -1)
+    return _mlp(params, hidden_act, out_act, rows).view(B, d)
+
+
+def aten_backward(W, b, hidden_act, out_act, x0, x, h, g, g_fx, nb_steps, inv_f):
+    """The ATen backward for nets the HIP backward turns away, for an integrand given as tensors: the same quadrature VJP and
+    Leibniz terms as integral.py's ``aten_backward`` / ``_op_backward`` and, with ``g_fx``, the f(x;h) term of
+    ``aten_backward_jac``.  A second implementation of that arithmetic, because it runs inside an op kernel, below autograd,
+    where torch.autograd.grad records nothing: the VJPs are torch.func.vjp.  (tests/test_torch_ops.py holds the two to the
+    same values.)  -> (dx0, dx, dh, dtheta_flat)."""
+    params = [p.detach() for pair in zip(W, b) for p in pair]
+    x0 = torch.zeros_like(x) if x0 is None else x0
+    w, s = device_tables(nb_steps, x.device)
+    w, u = w.to(x.dtype), s.to(x.dtype) + 1
+    span = x - x0
+    cot = g * span / 2
+    B = x.shape[0]
+    g_params = [torch.zeros_like(p) for p in params]
+    dh = torch.zeros_like(h)
+    for a, e in _I._node_chunks(nb_steps, B, h.shape[1] + x.shape[1]):
+        t, h_rep = _I._eval_chunk(None, x0, span, h, u[a:e])
+
+        def f_nodes(ps, hr, t=t):
+            f = _integrand(ps, hidden_act, out_act, t, hr)
+            return 1 / f if inv_f else f
+
+        f, vjp = torch.func.vjp(f_nodes, params, h_rep)
+        gp, gh = vjp((cot.unsqueeze(0) * w[a:e].view(-1, 1, 1)).reshape(f.shape))
+        for acc, gr in zip(g_params, gp):
+            acc += gr
+        dh += gh.view(e - a, B, -1).sum(0)
+    fx, vjp = torch.func.vjp(lambda ps, xx, hh: _integrand(ps, hidden_act, out_act, xx, hh), params, x, h)
+    dx = fx * g
+    if g_fx is not None:
+        gp, gx, gh = vjp(g_fx)
+        dx, dh = dx + gx, dh + gh
+        g_params = [a + c for a, c in zip(g_params, gp)]
+    dx0 = -_integrand(params, hidden_act, out_act, x0, h) * g
+    _I._state.path = _I._last_backward["path"] = "aten"
+    return dx0, dx, dh, torch.cat([p.reshape(-1) for p in g_params])
+
+
+def _backward(spec, W, b, x0, x, h, g, g_fx, nb_steps, need, inv_f):
+    if _I._hip_backward_ok(spec, x, h):
+        return _I.hip_backward(spec, x0, x, h, g, g_fx, nb_steps, tuple(need), inv_f=inv_f)
+    return aten_backward(W, b, spec.hidden_act, spec.out_act, x0, x, h, g, g_fx, nb_steps, inv_f)
+
+
+@torch.library.custom_op("umnn::cc_backward", mutates_args=(), device_types="cuda")
+def cc_backward(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, g_fx: Optional[Tensor], W: List[Tensor], b: List[Tensor],
+                hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """HIP backward, or -- for the nets ``integral._hip_backward_ok`` turns away, decided here at run time -- the ATen one."""
+    _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
+    out = _backward(spec_from_tensors(W, b, hidden_act, out_act), W, b, x0, x, h, g, g_fx, nb_steps, need, inv_f)
+    like = (x, x, h, W[0])
+    return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
+                 for i, (t, n, l) in enumerate(zip(out, need, like)))
+
+
+@cc_backward.register_fake
+def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return (x.new_empty(x.shape) if (need[0] and x0 is not None) else _empty(x),
+            x.new_empty(x.shape) if need[1] else _empty(x),
+            h.new_empty(h.shape) if need[2] else _empty(h),
+            W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------- flow block
+@torch.library.custom_op("umnn::flow_block", mutates_args=(), device_types="cuda")
+def flow_block(x: Tensor, h: Tensor, scaling: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
+               nb_steps: int, reverse_z: bool, log_jac_in: Optional[Tensor]) -> tuple[Tensor, Tensor, Tensor]:
+    """One UMNN-MAF block: the fused-epilogue launch of ``hip_flow_block`` (no z_2 hand-off: a training backward recomputes it).
+    f_x is returned for the backward and is not differentiable."""
+    _check_flow_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, log_jac_in)
+    z, lj, fx, _ = _I.hip_flow_block(spec_from_tensors(W, b, hidden_act, out_act), x, h, scaling, nb_steps, reverse_z, log_jac_in)
+    return z, lj, fx
+
+
+@flow_block.register_fake
+def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, log_jac_in):
+    _check_flow_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, log_jac_in)
+    return x.new_empty(x.shape), x.new_empty(x.shape), x.new_empty(x.shape)
+
+
+def _flow_block_setup(ctx, inputs, output):
+    x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, log_jac_in = inputs
+    # (the terms of the backward below are those of a frozen scaling on fp32 storage: integral.fused_block_ok's conditions)
+    if scaling.requires_grad:
+        raise RuntimeError("umnn::flow_block: no gradient for a trainable scaling (UMNNMAF freezes it); use the composed path")
+    if x.dtype != torch.float32:
+        raise RuntimeError(f"umnn::flow_block: differentiable for fp32 x only (got {x.dtype})")
+    ctx.mark_non_differentiable(output[2])
+    ctx.meta = (hidden_act, out_act, nb_steps, reverse_z, len(W))
+    ctx.save_for_backward(x, h, scaling, output[2], *W, *b)
+
+
+def _flow_block_backward(ctx, gz, glj, _gfx):
+    hidden_act, out_act, nb_steps, reverse_z, L = ctx.meta
+    x, h, scaling, fx, *Wb = ctx.saved_tensors
+    W, b = Wb[:L], Wb[L:]
+    nig = ctx.needs_input_grad
+    need = [bool(nig[0]), bool(nig[1]), any(nig[3]) or any(nig[4])]
+    dx, dh, dtheta = torch.ops.umnn.flow_block_backward(x, h, scaling, fx, gz, glj, W, b, hidden_act, out_act, nb_steps,
+                                                        reverse_z, need)
+    gW, gb = _param_grads(dtheta if need[2] else None, W, b, nig[3], nig[4])
+    return (dx if need[0] else None, dh if need[1] else None, None, gW, gb, None, None, None, None,
+            glj if nig[9] else None)
+
+
+flow_block.register_autograd(_flow_block_backward, setup_context=_flow_block_setup)
+
+
+@torch.library.custom_op("umnn::flow_block_backward", mutates_args=(), device_types="cuda")
+def flow_block_backward(x: Tensor, h: Tensor, scaling: Tensor, fx: Tensor, gz: Tensor, glj: Tensor, W: List[Tensor],
+                        b: List[Tensor], hidden_act: int, out_act: int, nb_steps: int, reverse_z: bool,
+                        need: List[bool]) -> tuple[Tensor, Tensor, Tensor]:
+    """``FlowBlockTransform.backward``: cotangents of F and f_x (one launch), the quadrature backward, the h_0 term in d_h."""
+    _check_flow_block_backward(x, h, scaling, fx, gz, glj, W, b, hidden_act, out_act, nb_steps, reverse_z, need)
+    B, d = x.shape
+    gF, gfx = _I.hip_flow_block_cotangents(gz.contiguous(), glj.contiguous(), fx.contiguous(), scaling.contiguous(), reverse_z)
+    _, dx, dh, dtheta = _backward(spec_from_tensors(W, b, hidden_act, out_act), W, b, None, x, h, gF, gfx, nb_steps,
+                                  [False, bool(need[0]), bool(need[1]), bool(need[2])], False)
+    if need[1]:
+        dh.view(B, -1, d)[:, 0, :].add_(gF)            # z carries h_0 = embedding row 0 (UMNNMAF.py:80)
+    like = (x, h, W[0])
+    return tuple(t.contiguous() if n else _empty(l, torch.float32 if i == 2 else None)
+                 for i, (t, n, l) in enumerate(zip((dx, dh, dtheta), need, like)))
+
+
+@flow_block_backward.register_fake
+def _(x, h, scaling, fx, gz, glj, W, b, hidden_act, out_act, nb_steps, reverse_z, need):
+    _check_flow_block_backward(x, h, scaling, fx, gz, glj, W, b, hidden_act, out_act, nb_steps, reverse_z, need)
+    return (x.new_empty(x.shape) if need[0] else _empty(x), h.new_empty(h.shape) if need[1] else _empty(h),
+            W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[2] else _empty(W[0], torch.float32))
+
+
+# ---------------------------------------------------------------------------------------------------------- log-likelihood
+@torch.library.custom_op("umnn::flow_ll", mutates_args=(), device_types="cuda")
+def flow_ll(z: Tensor, log_jac: Tensor) -> Tensor:
+    """ll[b] = sum_i log_jac[b,i] - 1/2 sum_i (log 2 pi + z[b,i]^2): ``FlowLogLikelihood``'s launch (fp32 z and log_jac)."""
+    _check_flow_ll(z, log_jac)
+    return _I.hip_flow_ll(z, log_jac)
+
+
+@flow_ll.register_fake
+def _(z, log_jac):
+    _check_flow_ll(z, log_jac)
+    return z.new_empty((z.shape[0],), dtype=torch.float32)
+
+
+@torch.library.custom_op("umnn::flow_ll_backward", mutates_args=(), device_types="cuda")
+def flow_ll_backward(z: Tensor, g_ll: Tensor) -> tuple[Tensor, Tensor]:
+    _check_flow_ll_backward(z, g_ll)
+    return _I.hip_flow_ll_backward(z.contiguous(), g_ll, True, True)
+
+
+@flow_ll_backward.register_fake
+def _(z, g_ll):
+    _check_flow_ll_backward(z, g_ll)
+    return z.new_empty(z.shape), z.new_empty(z.shape)
+
+
+def _flow_ll_setup(ctx, inputs, output):
+    ctx.save_for_backward(inputs[0])
+
+
+def _flow_ll_backward(ctx, g_ll):
+    (z,) = ctx.saved_tensors
+    gz, glj = torch.ops.umnn.flow_ll_backward(z, g_ll)
+    return (gz if ctx.needs_input_grad[0] else None, glj if ctx.needs_input_grad[1] else None)
+
+
+flow_ll.register_autograd(_flow_ll_backward, setup_context=_flow_ll_setup)
+
+
+@torch.library.custom_op("umnn::flow_ll_block", mutates_args=(), device_types="cuda")
+def flow_ll_block(x: Tensor, h: Tensor, scaling: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
+                  nb_steps: int, reverse_z: bool, first: bool, last: bool, ll_in: Optional[Tensor]) -> tuple[Tensor, Tensor]:
+    """One link of the one-pass log-likelihood (``hip_flow_ll_block``, inference): -> (z, ll); ``ll_in`` the running ll of the
+    previous links (None for the first).  The [B,d] scratch is the op's own; the row counters are the shared zeroed buffer of
+    the current stream (``integral.ll_counters``, which every launch leaves zero)."""
+    _check_flow_ll_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last, ll_in)
+    x = x.contiguous()
+    ll = torch.empty(x.shape[0], device=x.device, dtype=torch.float32) if ll_in is None else ll_in.clone()
+    z = _I.hip_flow_ll_block(spec_from_tensors(W, b, hidden_act, out_act), x, h.contiguous(), scaling.contiguous(), nb_steps,
+                             reverse_z, first, last, ll, torch.empty_like(x))
+    return z, ll
+
+
+@flow_ll_block.register_fake
+def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last, ll_in):
+    _check_flow_ll_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last, ll_in)
+    return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
+
+
+OPS = ("cc_forward", "cc_backward", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+
+
+def spec_args(spec):
+    """MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it."""
+    return [l.weight for l in spec.linears], [l.bias for l in spec.linears], spec.hidden_act, spec.out_act
