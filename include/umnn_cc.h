@@ -147,6 +147,32 @@ int umnn_flow_invert_dim(const umnn_mlp* net, const float* h, const float* z, co
                          const float* cc_w, const float* cc_s, int nb_steps,
                          long long B, int d, int E, int j, int iters, float* x_inv, void* stream);
 
+/* Inverse of the monotone map, one dimension per call, for all B rows in ONE launch: solves
+ *     scale_b * (off_b + int_0^{x_b} f(t; h[b, :, j]) dt) = target_b        for x_b in [lo, hi]
+ * by a safeguarded Newton iteration.  Every quadrature also yields f(x) = dF/dx (node 0 is x), so an iteration is one integral:
+ * the residual r tightens the bracket by its sign, the next iterate is x - r / (scale f(x)), replaced -- when it leaves the
+ * bracket or is not finite -- by the endpoint it overshot (each endpoint once) or by the bracket's midpoint.  A row stops when
+ * |r| <= tol * max(1, |target|), when its bracket has collapsed to adjacent floats or x has stopped changing; a target beyond
+ * G(lo) / G(hi) ends on that endpoint with UMNN_SOLVE_CLAMPED.  The launch ends when every row has stopped or after max_iter
+ * iterations (rows still running then carry UMNN_SOLVE_CAPPED and their last evaluated x).
+ *   h        [B, E*d]  embedding in the flow's stride-d layout; d = 1, j = 0 is the plain h [B, E] of MonotonicNN
+ *   target   column j of rows of t_stride floats (a [B, d] z: t_stride = d; a [B] vector: t_stride = 1, j = 0 with d = 1)
+ *   scale    scale_row [B] when non-null, else exp(scaling[j]) when scaling [d] is non-null, else 1
+ *   off      off_row [B] when non-null, else h[b, 0*d + j] (embedding row 0, the flow's offset) when off_h0 != 0, else 0
+ *   x        column j of rows of x_stride floats is WRITTEN (x_inv[:, j] of a [B, d] tensor in place); must not alias h / target
+ *   f_x      nullable [B]: f(x_b; h_b) at the returned x       status  nullable [B]: evaluations used | UMNN_SOLVE_* flags
+ * Arithmetic modes, the fp16-piece overflow protocol (an overflowing row is redone by the queued BF16X3 build; in the other modes
+ * it returns NaN with UMNN_SOLVE_NONFINITE) and net coverage are those of umnn_flow_invert_dim; UMNN_EUNSUPPORTED otherwise. */
+#define UMNN_SOLVE_EVALS_MASK 0xffff
+#define UMNN_SOLVE_CLAMPED (1 << 16)
+#define UMNN_SOLVE_CAPPED (1 << 17)
+#define UMNN_SOLVE_NONFINITE (1 << 18)
+int umnn_cc_solve(const umnn_mlp* net, const float* h, const float* target, long long t_stride,
+                  const float* scale_row, const float* scaling, const float* off_row, int off_h0,
+                  const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int j,
+                  float lo, float hi, float tol, int max_iter,
+                  float* x, long long x_stride, float* f_x, int* status, void* stream);
+
 /* Replaces integrate(..., compute_grad=True) + the Leibniz terms -- ParallelNeuralIntegral.py:66-94,
  * 110-123 (NeuralIntegral.py:47-58,69-75,90-99).  g is grad_output [B,d] (cotangent of F).
  *   g_fx    nullable [B,d]: cotangent of the f_x output of umnn_cc_forward.  The reference gets this

@@ -1,0 +1,116 @@
+#!/usr/bin/env python
+"""Times the sampling direction: one block's ``invert(iter=10)`` (the bracket search) against ``invert(method="newton")`` at the
+C3 block (8192 x 63, 31-50^4-1, n = 100) and the MNIST-shaped block (100 x 784, 31-100-50^4-1, n = 100), and
+``MonotonicNN.inverse`` at 65 536 x 1 with the 3-100^3-1 net of the g5 fixtures.
+
+    python tools/invert_bench.py [--repeats 5] [--warmup 1] [--root TREE] [--out FILE.json] [--only c3,mnist,monotonic]
+
+Device-synchronised wall time of whole calls (conditioner passes included), ``--warmup`` untimed calls of every method first, then
+``--repeats`` rounds that alternate the methods, so drift hits both alike; every figure comes with its min / max / standard
+deviation.  ``--root`` imports the package from another checkout (a tree without the Newton method -- the parent of this change --
+times the bracket search only), which is how the same-box comparison against an older build is taken.  Per-launch kernel time is
+a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/invert_bench.py --repeats 1 --only c3
+"""
+import argparse
+import inspect
+import json
+import os
+import statistics
+import sys
+import time
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--repeats", type=int, default=5)
+    ap.add_argument("--warmup", type=int, default=1)
+    ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    ap.add_argument("--out", default=None)
+    ap.add_argument("--only", default="c3,mnist,monotonic")
+    ap.add_argument("--label", default="")
+    args = ap.parse_args()
+    sys.path.insert(0, os.path.abspath(args.root))
+    import torch
+    import umnn_amd
+    from umnn_amd import _lib
+
+    dev = torch.device("cuda:0")
+    has_newton = "method" in inspect.signature(umnn_amd.UMNNMAF.invert).parameters
+    only = set(args.only.split(","))
+
+    def sync_time(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        out = fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3, out
+
+    def measure(case, fns, extra):
+        """fns: {method: callable}; alternates them every round."""
+        for _ in range(args.warmup):
+            for fn in fns.values():
+                sync_time(fn)
+        ms = {k: [] for k in fns}
+        launches, kernels, outs = {}, {}, {}
+        for _ in range(args.repeats):
+            for k, fn in fns.items():
+                n0 = _lib.lib().umnn_launch_count()
+                t, outs[k] = sync_time(fn)
+                ms[k].append(t)
+                launches[k] = _lib.lib().umnn_launch_count() - n0
+                kernels[k] = _lib.lib().umnn_last_kernel_name().decode()
+        rows = []
+        for k, v in ms.items():
+            rows.append(dict(case=case, method=k, label=args.label, mean_ms=statistics.mean(v), min_ms=min(v), max_ms=max(v),
+                             std_ms=statistics.pstdev(v), repeats=len(v), launches=launches[k], kernel=kernels[k], **extra(k, outs)))
+            print(json.dumps(rows[-1]), flush=True)
+        return rows
+
+    results = []
+    shapes = {"c3": dict(d=63, hd=[50] * 4, he=[512, 512], E=30, n=100, B=8192),
+              "mnist": dict(d=784, hd=[100, 50, 50, 50, 50], he=[1024] * 3, E=30, n=100, B=100)}
+    with torch.no_grad():
+        for case, c in shapes.items():
+            if case not in only:
+                continue
+            torch.manual_seed(0)
+            flow = umnn_amd.UMNNMAFFlow(nb_flow=1, nb_in=c["d"], hidden_derivative=c["hd"], hidden_embedding=c["he"],
+                                        embedding_s=c["E"], nb_steps=c["n"], solver="CCParallel").to(dev).eval()
+            blk = flow.nets[0]
+            x = torch.randn(c["B"], c["d"], device=dev)
+            z = blk(x)
+            fns = {"bracket": lambda: blk.invert(z, iter=10)}
+            if has_newton:
+                fns["newton"] = lambda: blk.invert(z, method="newton")
+
+            def extra(k, outs, x=x):
+                return dict(max_abs_err_x=float((outs[k] - x).abs().max()))
+            results += measure(case, fns, extra)
+        if "monotonic" in only and hasattr(umnn_amd.MonotonicNN, "inverse"):
+            torch.manual_seed(0)
+            m = umnn_amd.MonotonicNN(3, [100, 100, 100], nb_steps=50).to(dev)
+            B = 65536
+            x, h = torch.randn(B, 1, device=dev) * 2, torch.randn(B, 2, device=dev)
+            y = m(x, h)
+            state = {}
+
+            def inverse():
+                xi, _, status = m.inverse(y, h, return_info=True)
+                state["evals"] = status
+                return xi
+
+            def extra(k, outs):
+                if k != "inverse":
+                    return {}
+                ev = (state["evals"] & umnn_amd.SOLVE_EVALS_MASK).float()
+                return dict(max_abs_err_x=float((outs[k] - x).abs().max()), mean_evals=float(ev.mean()), max_evals=int(ev.max()))
+            results += measure("monotonic_65536", {"forward": lambda: m(x, h), "inverse": inverse}, extra)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            json.dump(dict(device=torch.cuda.get_device_name(0), precision=umnn_amd.get_forward_precision(), label=args.label,
+                           has_newton=has_newton, results=results), f, indent=1)
+
+
+if __name__ == "__main__":
+    main()

@@ -23,12 +23,13 @@ if "HSA_ENABLE_IPC_MODE_LEGACY" not in _os.environ:
 from .flow import UMNNMAFFlow, UMNNMAF, EmbeddingNetwork, IntegrandNetwork, ListModule
 from .monotonic import MonotonicNN, IntegrandNN
 from .made import MADE, ConditionnalMADE, MaskedLinear, invalidate_caches, set_made_fast_path, get_made_fast_path, set_made_fused
-from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, integrate, path_taken, backward_path_taken, set_backward_wide
+from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, InverseNeuralIntegral, integrate, path_taken, backward_path_taken, set_backward_wide
 from .nets import compute_lipschitz_linear
 from .quadrature import compute_cc_weights
 from .graphs import GraphedLL, GraphedTrainStep
 from . import ops  # noqa: F401  (registers the torch.ops.umnn custom ops; loads no library)
 from ._lib import set_forward_precision, get_forward_precision, set_backward_precision, get_backward_precision
+from ._lib import SOLVE_EVALS_MASK, SOLVE_CLAMPED, SOLVE_CAPPED, SOLVE_NONFINITE
 
 
 
@@ -64,4 +65,5 @@ __all__ = ["UMNNMAFFlow", "UMNNMAF", "EmbeddingNetwork", "IntegrandNetwork", "Li
            "IntegrandNN", "MADE", "ConditionnalMADE", "MaskedLinear", "NeuralIntegral", "ParallelNeuralIntegral",
            "IntegralWithJacobian", "integrate", "compute_cc_weights", "path_taken", "GraphedLL", "GraphedTrainStep",
            "set_precision", "invalidate_caches", "set_made_fast_path", "get_made_fast_path", "set_forward_precision", "get_forward_precision", "set_backward_precision", "get_backward_precision",
-           "set_backward_wide", "compute_lipschitz_linear", "backward_path_taken", "set_made_fused"]
+           "set_backward_wide", "compute_lipschitz_linear", "backward_path_taken", "set_made_fused",
+           "InverseNeuralIntegral", "SOLVE_EVALS_MASK", "SOLVE_CLAMPED", "SOLVE_CAPPED", "SOLVE_NONFINITE"]

@@ -59,6 +59,9 @@ SIGNATURES = {
                                                   _fp, _fp, _fp, _fp, _fp]),
     "umnn_flow_invert_dim": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                             _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp]),
+    "umnn_cc_solve": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _ll, _fp, _fp, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int,
+                                     _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                     ctypes.c_int, _fp, _ll, _fp, _fp, _fp]),
     "umnn_cc_backward": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                         _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),
@@ -121,6 +124,8 @@ class MadeNet(ctypes.Structure):
 
 PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3}
 PROF_FORWARD, PROF_BACKWARD, PROF_FINISH = 0, 1, 2
+# status word of umnn_cc_solve: evaluations used in the low 16 bits, flags above (UMNN_SOLVE_* of include/umnn_cc.h)
+SOLVE_EVALS_MASK, SOLVE_CLAMPED, SOLVE_CAPPED, SOLVE_NONFINITE = 0xffff, 1 << 16, 1 << 17, 1 << 18
 
 
 def profile_read(tag=None):

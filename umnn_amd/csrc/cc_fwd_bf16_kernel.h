@@ -210,9 +210,23 @@ struct Bf16Plan {
     int scratch_off_floats;        // float offset of the NS-reduction scratch (after the images)
 };
 
+// In-kernel Newton solve (cc_solve.hip, INV = 2 variants): scale_b (off_b + int_0^x f(t; h_b) dt) = target_b for x in [lo, hi].
+// The other operands travel in FwdArgs: inv_z = target, inv_x = x, inv_j = the dimension, inv_iters = max_iter, fx = f(x) out,
+// scaling = the flow's log-scales (scale = exp(scaling[inv_j]) unless scale_row is given; null and no scale_row: scale = 1).
+struct SolveArgs {
+    long long t_stride = 0, x_stride = 0;     // row strides (floats) of target / x; column inv_j of each row is used
+    const float* scale_row = nullptr;         // [B] per-row scale, nullable
+    const float* off_row = nullptr;           // [B] per-row offset, nullable
+    int off_h0 = 0;                           // no off_row: 1 = embedding row 0 of dimension inv_j (the flow's offset), 0 = none
+    int* status = nullptr;                    // [B] evaluations | UMNN_SOLVE_* flags, nullable
+    float lo = 0.f, hi = 0.f, tol = 0.f;
+};
+constexpr int SOLVE_CLAMPED = 1 << 16, SOLVE_CAPPED = 1 << 17, SOLVE_NONFINITE = 1 << 18;      // = UMNN_SOLVE_* of umnn_cc.h
+
 struct FwdBf16Args {
     FwdArgs f;
     Bf16Plan pl;
+    SolveArgs sv;      // (behind the plan: the offsets the forward and bracket-search kernels read do not move)
 };
 
 // ---- software-pipelined node loop (PIPE variants: four tiles, two bf16 pieces, two point tiles per wave) -----------
@@ -235,15 +249,21 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&&
 // wave-uniform guards (and the accumulator copies they force at every basic-block boundary) disappear.
 // NRL (EXACT only): live registers per lane = ceil((H+1)/4) for the common hidden width H; 0 = all 4*TMAX.
 // PIPE (EXACT, TMAX = 4, at least two hidden layers): the node loop is software-pipelined, see pipe_layer.
-// INV (plain loop, P = 1): the sampling direction.  A tile is one sample of one flow dimension j, its lanes p = 0..9 are the
+// INV = 1 (plain loop, P = 1): the sampling direction.  A tile is one sample of one flow dimension j, its lanes p = 0..9 are the
 // ten candidates x = left + p/9 (right - left) of the reference's bracket search (UMNNMAF.invert, UMNNMAF.py:182-232: [-50, 50]
 // to start with, `iter` rounds, the new bracket is the pair of candidates around the one whose image is closest to the
 // target); every round integrates all ten candidates with the node loop below, the search itself is a 16-lane butterfly.
 // The hoisted first-layer term depends on the sample only and is computed once for all rounds.
+// INV = 2 (plain loop, P = 1): the safeguarded Newton solve of cc_solve.hip.  The forward's mapping -- lane p of the tile is row
+// 16 tile + p -- and per lane an iterate x, a bracket [lo, hi] and a done flag in registers.  One iteration is the node loop below with
+// dxv = x, which yields F and (node 0 is x itself) f(x) = dF/dx; then r = scale (off + F) - target tightens the bracket by its sign and
+// the next iterate is x - r / (scale f(x)), or -- when that leaves (lo, hi) or is not finite -- the endpoint it overshot (once per
+// endpoint: a target beyond G(lo) / G(hi) ends there after one more quadrature) or the midpoint.  The tile leaves the loop on a
+// wave-uniform vote.  The hoisted term depends on h only: computed once for all iterations.
 // WPB: waves per workgroup.  Eight for the shapes whose weight images leave room for ONE workgroup per CU (uniform 6..8-tile nets, deep
 // 5-tile ones: 100-wide toy / MonotonicNN integrands stage 98-147 KB): the second wave of every SIMD then comes from the same
 // workgroup and shares its images, instead of the SIMD running one wave with nothing to overlap its vector phases with.
-template <int TMAX, int NPARTS, int P, bool EXACT, int NRL, bool PIPE = false, bool INV = false, int TREST = 0, int WPB = UMNN_WAVES_PER_BLOCK>
+template <int TMAX, int NPARTS, int P, bool EXACT, int NRL, bool PIPE = false, int INV = 0, int TREST = 0, int WPB = UMNN_WAVES_PER_BLOCK>
 __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args args) {
     static_assert(TREST == 0 || (EXACT && !PIPE && TREST < TMAX && (TREST & 1) == 0), "wide-first-layer variants: exact, plain loop");
     static_assert(!INV || (P == 1 && !PIPE), "inversion variants: plain loop, one tile per wave");
@@ -276,7 +296,12 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
     const unsigned grp = xcd_remap(blockIdx.x, gridDim.x) * gpb + sub;
     bool live = grp < a.ngroups;
     if (a.ovf_mode == 2 && live) {                                                                    // ... and then only the deferred groups
-        if constexpr (INV) { const float v = a.inv_x[(long long)grp * d + a.inv_j]; live = v != v; }   // (tile = sample: its slot of x_inv[:, j])
+        if constexpr (INV == 2) {                                                                      // (any row of the tile left a NaN)
+            long long q = (long long)grp * 16 + p;
+            if (q >= a.NI) q = a.NI - 1;
+            const float v = a.inv_x[q * args.sv.x_stride + a.inv_j];
+            live = __any(v != v);
+        } else if constexpr (INV) { const float v = a.inv_x[(long long)grp * d + a.inv_j]; live = v != v; }   // (tile = sample: its slot of x_inv[:, j])
         else live = fwd_group_marked<P>(a, grp, p);
     }
     const int k_lo = (int)(((long long)part * (n + 1)) / ns);
@@ -292,7 +317,13 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
         IoView hb[P];
 #pragma unroll
         for (int pt = 0; pt < P; ++pt) {
-            if constexpr (INV) {
+            if constexpr (INV == 2) {
+                const long long q = (long long)grp * 16 + p;             // lane p's row
+                ok[pt] = q < a.NI;
+                qv[pt] = ok[pt] ? q : a.NI - 1;
+                xv[pt] = 0.f; x0v[pt] = 0.f; dxv[pt] = 0.f;              // set per iteration
+                hb[pt] = IoView{a.h, a.h_bf16} + (qv[pt] * ((long long)E * d) + a.inv_j);
+            } else if constexpr (INV) {
                 const long long b = (long long)grp * P + pt;             // the tile's sample
                 ok[pt] = b < a.NI;
                 qv[pt] = ok[pt] ? b : a.NI - 1;
@@ -613,19 +644,39 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
         } else {
         // ---- bracket search state (INV): one sample per tile, candidate p on lane p ----
         float br_left = -50.f, br_right = 50.f, br_best = 0.f, inv_target = 0.f, inv_off = 0.f, inv_scale = 1.f, frac = 1.f;
-        if constexpr (INV) {
+        if constexpr (INV == 1) {
             frac = p < 10 ? (float)((double)p / 9.0) : 1.f;            // x_range of the reference: k * (1/9) in double, cast
 
             inv_target = a.inv_z[qv[0] * d + a.inv_j];
             inv_off = hb[0][0];                                        // embedding row 0 of dimension j: the offset
             inv_scale = __expf(a.scaling[a.inv_j]);
         }
+        // ---- Newton state (INV = 2): lane p's row; every lane group g holds the same values ----
+        float sv_x = 0.f, sv_a = 0.f, sv_b = 0.f, sv_fx = 0.f, sv_target = 0.f, sv_off = 0.f, sv_scale = 1.f;
+        bool sv_done = true, sv_aopen = true, sv_bopen = true, sv_mine = false, sv_bad = false;
+        int sv_stat = 0;
+        if constexpr (INV == 2) {
+            const SolveArgs& sv = args.sv;
+            sv_target = a.inv_z[qv[0] * sv.t_stride + a.inv_j];
+            sv_off = sv.off_row ? sv.off_row[qv[0]] : (sv.off_h0 ? hb[0][0] : 0.f);
+            sv_scale = sv.scale_row ? sv.scale_row[qv[0]] : (a.scaling ? __expf(a.scaling[a.inv_j]) : 1.f);
+            sv_a = sv.lo; sv_b = sv.hi;
+            sv_x = fminf(fmaxf(0.f, sv.lo), sv.hi);
+            // (queued fallback: only the rows the fp16 build left a NaN for are solved again and written)
+            sv_mine = ok[0];
+            if (a.ovf_mode == 2) { const float v = a.inv_x[qv[0] * sv.x_stride + a.inv_j]; sv_mine = sv_mine && v != v; }
+            sv_done = !sv_mine;
+        }
         const int rounds = INV ? a.inv_iters : 1;
         bool inv_bad = false;            // (fp16 pieces: some candidate integral of some round was not finite -- an overflowed piece)
         for (int round = 0; round < rounds; ++round) {
-        if constexpr (INV) {
+        if constexpr (INV == 1) {
             xv[0] = __fadd_rn(__fmul_rn(frac, br_right - br_left), br_left);      // x_range * (right - left) + left
             dxv[0] = xv[0];
+            Facc[0] = 0.f;
+        }
+        if constexpr (INV == 2) {
+            xv[0] = sv_x; dxv[0] = sv_x;
             Facc[0] = 0.f;
         }
         for (int k = k_lo; k < k_hi; ++k) {
@@ -787,7 +838,57 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 if (k == n) fx0v[pt] = f;
             }
         }
-        if constexpr (INV) {
+        if constexpr (INV == 2) {
+            if (ns > 1) {
+                // small batches (cc_solve.hip): the node range of the tile's sixteen integrals is split over all waves of the workgroup
+                // (one tile per workgroup, so the barriers are uniform); partial sums and node 0's f(x) meet in LDS once per iteration,
+                // summed in a fixed order: every wave sees the same totals, takes the same steps and casts the same vote
+                float* red = lds + m.lds_off[L];
+                if (g == 0) { red[wid * 16 + p] = Facc[0]; red[(WPB + wid) * 16 + p] = fxv[0]; }
+                __syncthreads();
+                float tot = 0.f;
+                for (int jj = 0; jj < ns; ++jj) tot += red[(sub * ns + jj) * 16 + p];
+                const float f0 = red[(WPB + sub * ns) * 16 + p];
+                __syncthreads();
+                Facc[0] = tot; fxv[0] = f0;
+            }
+            if (!sv_done) {
+                const SolveArgs& sv = args.sv;
+                ++sv_stat;
+                sv_fx = fxv[0];
+                const float r = sv_scale * (sv_off + Facc[0] * dxv[0] * 0.5f) - sv_target;
+                if (!(__builtin_fabsf(Facc[0]) < __builtin_inff()) || r != r) {
+                    sv_bad = true; sv_done = true;                   // an overflowed piece (fp16 build: left to the queued build) or a NaN target
+                } else if (fabsf(r) <= sv.tol * fmaxf(1.f, fabsf(sv_target))) {
+                    sv_done = true;
+                } else {
+                    if (r > 0.f) {
+                        if (sv_x <= sv.lo) { sv_stat |= SOLVE_CLAMPED; sv_done = true; }      // target below G(lo)
+                        sv_b = sv_x; sv_bopen = false;
+                    } else {
+                        if (sv_x >= sv.hi) { sv_stat |= SOLVE_CLAMPED; sv_done = true; }      // target above G(hi)
+                        sv_a = sv_x; sv_aopen = false;
+                    }
+                    if (!sv_done) {
+                        float xn = sv_x - r / (sv_scale * sv_fx);
+                        if (!(xn > sv_a && xn < sv_b)) {
+                            if (xn >= sv_b && sv_bopen) { xn = sv_b; sv_bopen = false; }       // overshot an endpoint not yet evaluated: try it
+                            else if (xn <= sv_a && sv_aopen) { xn = sv_a; sv_aopen = false; }
+                            else {
+                                xn = 0.5f * (sv_a + sv_b);
+                                if (!(xn > sv_a && xn < sv_b)) sv_done = true;                 // bracket collapsed to adjacent floats
+                            }
+                        }
+                        if (!sv_done) {
+                            if (xn == sv_x) sv_done = true;                                    // x has stopped changing
+                            else if (round + 1 < rounds) sv_x = xn;                            // (the last evaluated point is what leaves)
+                        }
+                    }
+                }
+            }
+            if (__all(sv_done)) break;
+        }
+        if constexpr (INV == 1) {
             if (ns > 1) {
                 // small batches (cc_invert.hip): the node range of this sample's ten integrals is split over ALL waves of the workgroup
                 // (ns = waves per workgroup, one sample per workgroup: every wave of a live workgroup gets here, the barriers are
@@ -822,7 +923,22 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             br_right = below ? hi : br_best;
         }
         }   // rounds
-        if constexpr (INV) {
+        if constexpr (INV == 2) {
+            // overflow protocol (cc_solve.hip): a row whose iterate overflowed an fp16 piece is left to the queued bf16 build, its slot
+            // marked with a NaN; in the other builds such a row (and a NaN target) returns NaN with UMNN_SOLVE_NONFINITE set
+            const bool defer = a.ovf_mode == 1 && sv_bad;
+            if (sv_mine && g == 0 && part == 0) {
+                if (!sv_done) sv_stat |= SOLVE_CAPPED;
+                if (sv_bad) sv_stat |= SOLVE_NONFINITE;
+                a.inv_x[qv[0] * args.sv.x_stride + a.inv_j] = sv_bad ? __builtin_nanf("") : sv_x;
+                if (!defer) {
+                    if (a.fx) a.fx[qv[0]] = sv_fx;
+                    if (args.sv.status) args.sv.status[qv[0]] = sv_stat;
+                }
+            }
+            if (__any(defer) && lane == 0 && part == 0) atomicMax(a.ovf_flag, a.ovf_gen);
+        }
+        if constexpr (INV == 1) {
             // overflow protocol (cc_invert.hip): the sample is left to the queued bf16 build, its slot marked with a NaN
             const bool defer = a.ovf_mode == 1 && __any(inv_bad);
             if (ok[0] && lane == 0 && part == 0) {

@@ -254,17 +254,75 @@ class UMNNMAF(nn.Module):
             return _I.aten_forward(lambda t, hh: integrand.independant_forward(torch.cat((t, hh), 1)),
                                    torch.zeros_like(cand), cand, h_j, self.nb_steps)
 
-    def invert(self, z, iter=10, context=None):
+    def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64):
         """Dimension-by-dimension bracket search: 10 candidates per round on [left,right] (starting at +-50), keep
         the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232).  Eager only:
-        compiled callers get an eager call; under torch.jit.trace it raises."""
+        compiled callers get an eager call; under torch.jit.trace it raises.
+        ``method="newton"`` (an extension; ``iter`` is ignored): the same dimension-by-dimension structure with the safeguarded Newton
+        solve of ``umnn_cc_solve`` on [-50, 50] in place of the search -- residual to ``tol * max(1, |z_j|)``, at most ``max_iter``
+        quadratures per dimension, typically four."""
+        if method not in ("bracket", "newton"):
+            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket' or 'newton'")
         if torch.jit.is_tracing():
             raise RuntimeError("umnn_amd: UMNNMAF.invert cannot be traced by torch.jit.trace (data-dependent bracket search); "
                                "call it eagerly")
+        if method == "newton":
+            if torch.compiler.is_compiling():
+                return torch.compiler.disable(UMNNMAF._invert_newton)(self, z, context, tol, max_iter)
+            return self._invert_newton(z, context, tol, max_iter)
         if torch.compiler.is_compiling():
             # (applied here, not as a decorator: torch.compiler.disable imports torch._dynamo, ~1 s at every package import)
             return torch.compiler.disable(UMNNMAF._invert)(self, z, iter, context)
         return self._invert(z, iter, context)
+
+    def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
+        """``invert(method="newton")``.  HIP path: d x (conditioner + ONE launch), the whole solve of a dimension inside the kernel,
+        writing x_inv[:, j] in place; nets the solve kernels do not cover, host tensors and other dtypes run the same iteration
+        from the host (``integral.newton_solve``), one quadrature launch (or ATen quadrature) per iteration."""
+        B, d = z.shape
+        dev = z.device
+        integrand = self.net.parallel_nets
+        spec = mlp_spec(integrand)
+        in_kernel = (_I._use_hip(spec, z) and z.dtype == torch.float32 and self.nb_steps >= 1 and B > 0 and self.solver in _SOLVERS)
+        with torch.no_grad():
+            z = z.contiguous()
+            x_inv = torch.zeros(B, d, device=dev, dtype=z.dtype)
+            scaling = self.scaling.detach().float().contiguous()
+            made = self.net.made
+            E = made.nout // made.nin
+            # (the conditioner pass of one dimension: as in _invert -- only the E columns dimension j reads, where MADE.raw_rows applies)
+            restrict = (in_kernel and context is None and not isinstance(made, ConditionnalMADE)
+                        and self.net.embedding_dtype in (None, torch.float32) and os.environ.get("UMNN_INVERT_ROWS", "1") != "0")
+            rows_all = (torch.arange(E, device=dev) * d).view(1, E) + torch.arange(d, device=dev).view(d, 1) if restrict else None
+            h_buf = None
+            for j in range(self.input_size):
+                hj = made.raw_rows(x_inv, rows_all[j]) if restrict else None
+                if hj is not None:
+                    if h_buf is None:
+                        h_buf = torch.zeros(B, E * d, device=dev)
+                    h_buf.view(B, E, d)[:, :, j] = hj
+                    h = h_buf
+                else:
+                    restrict = False
+                    h = self.net.make_embeding(x_inv, context)
+                    if in_kernel:
+                        h = h.float().contiguous()      # (umnn_cc_solve reads an fp32 embedding; widening bf16 is exact)
+                if in_kernel:
+                    if _I.hip_solve(spec, h, z, self.nb_steps, j=j, scaling=scaling, off_h0=True, lo=-50., hi=50., tol=tol,
+                                    max_iter=max_iter, x_out=x_inv, want_info=False) is not None:
+                        continue
+                    in_kernel = False
+                h_j = h.view(B, -1, d)[:, :, j].to(z.dtype).contiguous()          # [B,E]; row 0 doubles as the offset
+
+                def eval_fn(xc, h_j=h_j):
+                    if _I._use_hip(spec, xc):
+                        F, fx, _ = _I.hip_forward(spec, None, xc, h_j, self.nb_steps)
+                        return F, fx
+                    return self._conditional_integral(xc, h_j), integrand.independant_forward(torch.cat((xc, h_j), 1))
+
+                x_j, _, _ = _I.newton_solve(eval_fn, z[:, [j]], torch.exp(self.scaling[j]).to(z.dtype), h_j[:, [0]], -50., 50., tol, max_iter)
+                x_inv[:, j] = x_j[:, 0]
+        return x_inv
 
     def _invert(self, z, iter=10, context=None):
         K = 10
@@ -390,13 +448,27 @@ class UMNNMAFFlow(nn.Module):
     def forward(self, x, context=None):
         return self._stack(x, context, False)[0]
 
-    def invert(self, z, iter=10, context=None):
+    def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64):
+        """Sampling direction, block by block.  ``method="bracket"`` (default): the reference's search, ``iter`` rounds.
+        ``method="newton"``: the in-kernel Newton solve (``UMNNMAF.invert``), exactly nb_flow x d solve launches; ``iter`` is ignored."""
+        if method not in ("bracket", "newton"):
+            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket' or 'newton'")
         if torch.jit.is_tracing():
             raise RuntimeError("umnn_amd: UMNNMAFFlow.invert cannot be traced by torch.jit.trace (data-dependent bracket "
                                "search); call it eagerly")
+        if method == "newton":
+            if torch.compiler.is_compiling():
+                return torch.compiler.disable(UMNNMAFFlow._invert_newton)(self, z, context, tol, max_iter)
+            return self._invert_newton(z, context, tol, max_iter)
         if torch.compiler.is_compiling():           # (an eager call inside compiled code; see UMNNMAF.invert)
             return torch.compiler.disable(UMNNMAFFlow._invert)(self, z, iter, context)
         return self._invert(z, iter, context)
+
+    def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
+        z = torch.flip(z, [1])
+        for i in range(len(self.nets) - 1, -1, -1):
+            z = self.nets[i].invert(torch.flip(z, [1]), context=context, method="newton", tol=tol, max_iter=max_iter)
+        return z
 
     def _invert(self, z, iter=10, context=None):
         z = torch.flip(z, [1])

@@ -362,6 +362,134 @@ def hip_invert_dim(spec, h, z, scaling, nb_steps, j, iters, x_inv):
     return True
 
 
+def hip_solve(spec, h, target, nb_steps, j=0, scale_row=None, scaling=None, off_row=None, off_h0=False, lo=-50., hi=50., tol=1e-6,
+              max_iter=64, x_out=None, want_info=True):
+    """Newton solve of dimension j for every row in ONE launch (umnn_cc_solve), the counterpart of ``hip_invert_dim``:
+    scale (off + int_0^x f(t; h[:, :, j]) dt) = target[:, j].  ``target`` [B,d] fp32 contiguous, ``h`` [B,E*d] fp32 contiguous;
+    scale = ``scale_row`` [B], else exp(``scaling``[j]), else 1; off = ``off_row`` [B], else embedding row 0 (``off_h0``), else 0.
+    Writes ``x_out``[:, j] ([B,d] fp32 contiguous; allocated when None) -> (x_out, f_x [B], status [B] int32), the last two None
+    unless ``want_info``.  Returns None when the library has no kernel for this net: the caller runs ``host_solve``."""
+    lib = _lib.lib()
+    B, d = target.shape
+    E = h.shape[1] // d
+    if E * d != h.shape[1] or spec.linears[0].in_features != 1 + E:
+        raise RuntimeError("umnn_amd: embedding width does not match the integrand")
+    w, s = device_tables(nb_steps, target.device)
+    if x_out is None:
+        x_out = torch.empty(B, d, device=target.device, dtype=torch.float32)
+    fx = torch.empty(B, device=target.device, dtype=torch.float32) if want_info else None
+    status = torch.empty(B, device=target.device, dtype=torch.int32) if want_info else None
+    desc, keep = _desc(spec)
+    with torch.cuda.device(target.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(target.device).cuda_stream)
+        rc = lib.umnn_cc_solve(ctypes.byref(desc), _ptr(h), _ptr(target), d, _ptr(scale_row), _ptr(scaling), _ptr(off_row),
+                               1 if off_h0 else 0, _ptr(w), _ptr(s), int(nb_steps), B, d, E, int(j), float(lo), float(hi),
+                               float(tol), int(max_iter), _ptr(x_out), d, _ptr(fx), _ptr(status), stream)
+    if rc == _lib.EUNSUPPORTED:
+        _warn_once(("solve-host", tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
+                   "umnn_amd: no in-kernel Newton solve for this integrand / arithmetic mode "
+                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): the inverse runs the host-driven Newton loop "
+                   "(one forward launch per iteration).")
+        return None
+    _lib.check(rc, "umnn_cc_solve")
+    _state.path = "hip"
+    return x_out, fx, status
+
+
+def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter):
+    """The safeguarded Newton iteration of umnn_cc_solve (include/umnn_cc.h) in torch ops, elementwise on tensors of any shape:
+    solves scale (off + F(x)) = target on [lo, hi], where ``eval_fn(x) -> (F(x), f(x))`` with f = dF/dx > 0.  The host-driven
+    loop over ``hip_forward`` and the generic ATen path are this function.  -> (x, f(x), status int32)."""
+    lo, hi = float(lo), float(hi)
+    x = torch.full_like(target, min(max(0., lo), hi))
+    a, b = torch.full_like(target, lo), torch.full_like(target, hi)
+    a_open = torch.ones_like(target, dtype=torch.bool)
+    b_open, done, bad = a_open.clone(), ~a_open, ~a_open
+    evals = torch.zeros_like(target, dtype=torch.int32)
+    flags = torch.zeros_like(evals)
+    fx = torch.zeros_like(target)
+    bound = tol * target.abs().clamp(min=1.)
+    for it in range(int(max_iter)):
+        F, f = eval_fn(x)
+        act = ~done
+        evals += act
+        fx = torch.where(act, f, fx)
+        r = scale * (off + F) - target
+        nonfinite = act & (~torch.isfinite(F) | torch.isnan(r))
+        bad |= nonfinite
+        done = done | nonfinite | (act & (r.abs() <= bound))
+        act = ~done
+        pos = r > 0
+        clamped = act & ((pos & (x <= lo)) | (~pos & (x >= hi)))       # the target lies beyond G(lo) / G(hi)
+        flags |= clamped.to(torch.int32) * _lib.SOLVE_CLAMPED
+        b = torch.where(act & pos, x, b)
+        a = torch.where(act & ~pos, x, a)
+        b_open &= ~(act & pos)
+        a_open &= ~(act & ~pos)
+        done = done | clamped
+        act = ~done
+        xn = x - r / (scale * f)
+        inside = (xn > a) & (xn < b)
+        to_b = ~inside & (xn >= b) & b_open                           # overshot an endpoint not yet evaluated: try it
+        to_a = ~inside & ~to_b & (xn <= a) & a_open
+        use_mid = ~inside & ~to_b & ~to_a
+        mid = 0.5 * (a + b)
+        collapsed = use_mid & ~((mid > a) & (mid < b))                # adjacent floats
+        xn = torch.where(to_b, b, torch.where(to_a, a, torch.where(use_mid, mid, xn)))
+        b_open &= ~(act & to_b)
+        a_open &= ~(act & to_a)
+        done = done | (act & collapsed)
+        done = done | (~done & (xn == x))                             # x has stopped changing
+        if bool(done.all()):
+            break
+        if it + 1 < max_iter:
+            x = torch.where(done, x, xn)                              # (the last evaluated point is what leaves)
+    flags |= (~done).to(torch.int32) * _lib.SOLVE_CAPPED
+    flags |= bad.to(torch.int32) * _lib.SOLVE_NONFINITE
+    x = torch.where(bad, torch.full_like(x, float("nan")), x)
+    return x, fx, evals | flags
+
+
+def host_solve(spec, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0.):
+    """Host-driven Newton loop over ``hip_forward`` (F and f_x in one launch per iteration): what runs when the library
+    answers UMNN_EUNSUPPORTED for the in-kernel solve.  ``target`` [B,d], ``h`` [B,E*d] -> (x, f_x, status), each [B,d]."""
+    def eval_fn(x):
+        F, fx, _ = hip_forward(spec, None, x, h, nb_steps)
+        return F, fx
+    with torch.no_grad():
+        return newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter)
+
+
+def aten_solve(integrand, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0.):
+    """Generic ATen path of the inverse (CPU tensors, float64, integrands ``mlp_spec`` does not recognise): the same
+    algorithm on ``aten_forward``."""
+    def eval_fn(x):
+        return aten_forward(integrand, torch.zeros_like(x), x, h, nb_steps), integrand(x, h)
+    with torch.no_grad():
+        out = newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter)
+    _state.path = "aten"
+    return out
+
+
+def solve_integral(spec, t, h, nb_steps, lo, hi, tol, max_iter):
+    """x with int_0^x f(s; h) ds = t on the HIP path: one in-kernel solve per dimension, or the host-driven loop for nets the
+    solve kernels do not cover.  ``t`` [B,d], ``h`` [B,E*d] -> (x, f_x, status), each [B,d] (x, f_x in t's dtype)."""
+    B, d = t.shape
+    t32, h32 = _f32c(t), _f32c(h)
+    with torch.no_grad():
+        x = torch.empty_like(t32)
+        fx = torch.empty_like(t32)
+        status = torch.empty(B, d, device=t.device, dtype=torch.int32)
+        for j in range(d):
+            out = hip_solve(spec, h32, t32, nb_steps, j=j, lo=lo, hi=hi, tol=tol, max_iter=max_iter, x_out=x) if B > 0 else (x, fx, status)
+            if out is None:
+                x, fx, status = host_solve(spec, h32, t32, nb_steps, lo, hi, tol, max_iter)
+                break
+            if B > 0:
+                fx[:, j], status[:, j] = out[1], out[2]
+    return x.to(t.dtype), fx.to(t.dtype), status
+
+
 _row_counters = {}     # (device index, stream handle) -> zeroed uint32 [>= B] arrival counters (kernel leaves them zero)
 
 
@@ -857,3 +985,68 @@ class IntegralWithJacobian(torch.autograd.Function):
         need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4], ctx.needs_input_grad[3])
         dx0, dx, dh, dtheta = hip_backward(ctx.spec, x0, x, h, gF, gfx, ctx.nb_steps, need)
         return dx0, dx, None, dtheta, dh, None
+
+
+class InverseNeuralIntegral(torch.autograd.Function):
+    """x [B,d] with int_0^x f(s; h) ds = t: the inverse of ``ParallelNeuralIntegral.apply(0, x, ...)`` in x, by the safeguarded
+    Newton iteration of ``umnn_cc_solve`` (one launch per dimension on the HIP path; ``newton_solve`` on ATen otherwise).
+
+        InverseNeuralIntegral.apply(t, integrand, flat_params, h, nb_steps=20, x_range=(-50., 50.), tol=1e-6, max_iter=64,
+                                    return_info=False)  ->  x   or   (x, f(x), status)
+
+    The gradient is the implicit one: dx/dt = 1 / f(x), and (d_theta, d_h) are those of the forward integral with upper limit x for
+    the cotangent -g_x / f(x) -- one launch of the existing backward kernels, no backward kernel of its own."""
+
+    @staticmethod
+    def forward(ctx, t, integrand, flat_params, h, nb_steps=20, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False):
+        lo, hi = float(x_range[0]), float(x_range[1])
+        if _graph_mode():
+            spec = _graph_spec(integrand, t)
+            if spec is not None:
+                W, b = [l.weight for l in spec.linears], [l.bias for l in spec.linears]
+                x, fx, status = torch.ops.umnn.cc_solve(t, h, W, b, spec.hidden_act, spec.out_act, int(nb_steps), lo, hi,
+                                                        float(tol), int(max_iter))
+                ctx.graph = (spec.hidden_act, spec.out_act, int(nb_steps), len(W))
+                ctx.save_for_backward(x, h, fx, *W, *b)
+                if not return_info:
+                    return x
+                ctx.mark_non_differentiable(fx, status)
+                return x, fx, status
+        spec = mlp_spec(integrand)
+        ctx.integrand, ctx.nb_steps, ctx.spec = integrand, nb_steps, spec
+        ctx.use_hip = _use_hip(spec, t)
+        if ctx.use_hip:
+            x, fx, status = solve_integral(spec, t, h, nb_steps, lo, hi, tol, max_iter)
+        else:
+            x, fx, status = aten_solve(integrand, h.detach(), t.detach(), nb_steps, lo, hi, tol, max_iter)
+        ctx.save_for_backward(x, h, fx)
+        if not return_info:
+            return x
+        ctx.mark_non_differentiable(fx, status)
+        return x, fx, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, *_unused):
+        nig = ctx.needs_input_grad
+        if getattr(ctx, "graph", None) is not None:
+            ha, oa, nb_steps, L = ctx.graph
+            saved = ctx.saved_tensors
+            x, h, fx, W, b = saved[0], saved[1], saved[2], list(saved[3:3 + L]), list(saved[3 + L:])
+            g_t = g_x / fx
+            need = [False, False, bool(nig[3]), bool(nig[2])]
+            dh = dtheta = None
+            if need[2] or need[3]:
+                _, _, dh, dtheta = torch.ops.umnn.cc_backward(None, x, h, -g_t, None, W, b, ha, oa, nb_steps, need, False)
+            return (g_t if nig[0] else None, None, dtheta if need[3] else None, dh if need[2] else None,
+                    None, None, None, None, None)
+        x, h, fx = ctx.saved_tensors
+        g_t = g_x / fx
+        dh = dtheta = None
+        if nig[2] or nig[3]:
+            if ctx.use_hip and _hip_backward_ok(ctx.spec, x, h):
+                _, _, dh, dtheta = hip_backward(ctx.spec, None, x, h, -g_t, None, ctx.nb_steps, (False, False, nig[3], nig[2]))
+            else:
+                dtheta, dh = aten_backward(ctx.integrand, torch.zeros_like(x), x, h, -g_t, ctx.nb_steps)
+                dh = dh.view(h.shape)
+        return (g_t if nig[0] else None, None, dtheta if nig[2] else None, dh if nig[3] else None, None, None, None, None, None)

@@ -3,6 +3,7 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
 
     umnn::cc_forward(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)
     umnn::cc_backward(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
+    umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::flow_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, log_jac_in?) -> (z, log_jac, f_x)
     umnn::flow_block_backward(x, h, scaling, f_x, gz, glj, W[], b[], hidden_act, out_act, nb_steps, reverse_z, need[3])
         -> (dx, dh, dtheta)
@@ -14,7 +15,8 @@ The integrand crosses the op boundary as tensors and plain values -- the fields 
 implementation calls the eager path's own ``integral.hip_*`` function (same arithmetic mode, overflow fallback and
 ``path_taken()`` bookkeeping); every output is a fresh tensor and no op writes an input.  Outputs an op is told it need not
 compute (``need``) come back as empty tensors.  cc_forward, flow_block and flow_ll are differentiable (their backward is the
-matching op; flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
+matching op; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` -- is differentiable in its x output through cc_backward,
+by the implicit-function theorem; flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
 flow_ll_block are not.  Registration loads no library and touches no GPU.
 
 The ops are public, so every real and fake implementation first checks what it was given (``_check_*``): one CUDA device for
@@ -279,6 +281,56 @@ def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
             W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
 
 
+
+# ---------------------------------------------------------------------------------------------------------- inverse (Newton solve)
+def _check_cc_solve(t, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
+    op = "cc_solve"
+    _check_net(op, t, h, W, b, hidden_act, out_act)
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+    _req(op, lo < hi, f"empty bracket [{lo}, {hi}]")
+    _req(op, tol >= 0, f"tol is {tol}; expected >= 0")
+    _req(op, 1 <= max_iter <= _lib.SOLVE_EVALS_MASK, f"max_iter is {max_iter}; expected 1..{_lib.SOLVE_EVALS_MASK}")
+
+
+@torch.library.custom_op("umnn::cc_solve", mutates_args=(), device_types="cuda")
+def cc_solve(t: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int, nb_steps: int,
+             lo: float, hi: float, tol: float, max_iter: int) -> tuple[Tensor, Tensor, Tensor]:
+    """x [B,d] in [lo, hi] with int_0^x f(s; h) ds = t (``integral.solve_integral``: the in-kernel Newton solve, one launch per
+    dimension), f(x; h) and the int32 status word per element.  The iteration count is data-dependent only inside the launch."""
+    _check_cc_solve(t, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter)
+    return _I.solve_integral(spec_from_tensors(W, b, hidden_act, out_act), t, h, nb_steps, lo, hi, tol, max_iter)
+
+
+@cc_solve.register_fake
+def _(t, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
+    _check_cc_solve(t, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter)
+    return t.new_empty(t.shape), t.new_empty(t.shape), t.new_empty(t.shape, dtype=torch.int32)
+
+
+def _cc_solve_setup(ctx, inputs, output):
+    t, h, W, b, hidden_act, out_act, nb_steps = inputs[:7]
+    ctx.mark_non_differentiable(output[1], output[2])
+    ctx.meta = (hidden_act, out_act, nb_steps, len(W))
+    ctx.save_for_backward(output[0], h, output[1], *W, *b)
+
+
+def _cc_solve_backward(ctx, g_x, _gfx, _gstatus):
+    """Implicit backward: g_t = g_x / f(x); (d_theta, d_h) of the integral up to x for the cotangent -g_x / f(x)."""
+    hidden_act, out_act, nb_steps, L = ctx.meta
+    x, h, fx, *Wb = ctx.saved_tensors
+    W, b = Wb[:L], Wb[L:]
+    nig = ctx.needs_input_grad
+    need = [False, False, bool(nig[1]), any(nig[2]) or any(nig[3])]
+    g_t = g_x / fx
+    dh = dtheta = None
+    if need[2] or need[3]:
+        _, _, dh, dtheta = torch.ops.umnn.cc_backward(None, x, h, -g_t, None, W, b, hidden_act, out_act, nb_steps, need, False)
+    gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[2], nig[3])
+    return (g_t if nig[0] else None, dh if need[2] else None, gW, gb, None, None, None, None, None, None, None)
+
+
+cc_solve.register_autograd(_cc_solve_backward, setup_context=_cc_solve_setup)
+
 # ---------------------------------------------------------------------------------------------------------- flow block
 @torch.library.custom_op("umnn::flow_block", mutates_args=(), device_types="cuda")
 def flow_block(x: Tensor, h: Tensor, scaling: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
@@ -407,7 +459,7 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
     return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
 
 
-OPS = ("cc_forward", "cc_backward", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+OPS = ("cc_forward", "cc_backward", "cc_solve", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
 def spec_args(spec):
