@@ -153,7 +153,7 @@ int umnn_flow_invert_dim(const umnn_mlp* net, const float* h, const float* z, co
  * the residual r tightens the bracket by its sign, the next iterate is x - r / (scale f(x)), replaced -- when it leaves the
  * bracket or is not finite -- by the endpoint it overshot (each endpoint once) or by the bracket's midpoint.  A row stops when
  * |r| <= tol * max(1, |target|), when its bracket has collapsed to adjacent floats or x has stopped changing; a target beyond
- * G(lo) / G(hi) ends on that endpoint with UMNN_SOLVE_CLAMPED.  The launch ends when every row has stopped or after max_iter
+ * G(lo) / G(hi) -- an infinite one included -- ends on that endpoint with UMNN_SOLVE_CLAMPED.  The launch ends when every row has stopped or after max_iter
  * iterations (rows still running then carry UMNN_SOLVE_CAPPED and their last evaluated x).
  *   h        [B, E*d]  embedding in the flow's stride-d layout; d = 1, j = 0 is the plain h [B, E] of MonotonicNN
  *   target   column j of rows of t_stride floats (a [B, d] z: t_stride = d; a [B] vector: t_stride = 1, j = 0 with d = 1)

@@ -33,6 +33,73 @@ def solve64(G, y, lo=-50., hi=50., max_iter=200):
     return np.where(below, lo, np.where(above, hi, x))
 
 
+def newton64(G, target, lo=-50., hi=50., tol=1e-6, max_iter=64):
+    """The iteration ``include/umnn_cc.h`` describes for umnn_cc_solve, restated in float64 row by row (no code shared with
+    ``umnn_amd.integral.newton_solve``): start at 0 clamped into [lo, hi]; every evaluation G(x) -> (value, derivative) gives the
+    residual r, whose sign moves one end of the bracket to x; the next point is x - r / G'(x), replaced -- when it is not strictly
+    inside the bracket -- by the endpoint it overshot (each endpoint once, and only while no evaluation has replaced it) or by the
+    bracket's midpoint.  A row stops when |r| <= tol max(1, |target|), when x sits on the endpoint the target lies beyond (clamped),
+    when the midpoint no longer separates the ends or when the next point equals x; a row still running after ``max_iter``
+    evaluations keeps its last evaluated x (capped).  -> (x, evaluations, clamped, capped), each shaped like ``target``."""
+    t = np.asarray(target, np.float64)
+    shape = t.shape
+    t = t.reshape(-1)
+    N = t.size
+    x = np.full(N, min(max(0., lo), hi))
+    a, b = np.full(N, float(lo)), np.full(N, float(hi))
+    a_fresh, b_fresh = np.ones(N, bool), np.ones(N, bool)
+    running = np.ones(N, bool)
+    evals = np.zeros(N, np.int64)
+    clamped = np.zeros(N, bool)
+    for it in range(int(max_iter)):
+        if not running.any():
+            break
+        g, dg = G(x.reshape(shape))
+        g, dg = np.asarray(g, np.float64).reshape(-1), np.asarray(dg, np.float64).reshape(-1)
+        for i in np.flatnonzero(running):
+            evals[i] += 1
+            r = g[i] - t[i]
+            if abs(r) <= tol * max(1., abs(t[i])) and np.isfinite(r):      # (no x meets an infinite target)
+                running[i] = False
+                continue
+            if r > 0:
+                if x[i] <= lo:
+                    clamped[i], running[i] = True, False
+                b[i], b_fresh[i] = x[i], False
+            else:
+                if x[i] >= hi:
+                    clamped[i], running[i] = True, False
+                a[i], a_fresh[i] = x[i], False
+            if not running[i]:
+                continue
+            nxt = x[i] - r / dg[i]
+            if not (a[i] < nxt < b[i]):
+                if nxt >= b[i] and b_fresh[i]:
+                    nxt, b_fresh[i] = b[i], False
+                elif nxt <= a[i] and a_fresh[i]:
+                    nxt, a_fresh[i] = a[i], False
+                else:
+                    nxt = 0.5 * (a[i] + b[i])
+                    if not (a[i] < nxt < b[i]):
+                        running[i] = False
+                        continue
+            if nxt == x[i]:
+                running[i] = False
+            elif it + 1 < max_iter:
+                x[i] = nxt
+    return x.reshape(shape), evals.reshape(shape), clamped.reshape(shape), running.reshape(shape)
+
+
+def integral_map(net, h, n, scale=1., off=0.):
+    """G(x) -> (scale (off + int_0^x f), scale f(x)) in float64 for the rows of ``h`` (d = 1): the map umnn_cc_solve inverts."""
+    h = np.asarray(h, np.float64)
+
+    def G(x):
+        x = np.asarray(x, np.float64)
+        return scale * (off + O.integrate_parallel(net, np.zeros_like(x), x, h, n)), scale * O.integrand(net, x, h)
+    return G
+
+
 # ---- MonotonicNN -------------------------------------------------------------------------------------------------
 def monotonic_parts(G):
     """float64 (integrand Net, conditioner Ws, bs) of a g5_monotonic fixture."""

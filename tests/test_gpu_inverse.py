@@ -227,8 +227,10 @@ def test_newton_round_trip(d, hid, E, n, nb_flow, B, precision, dev):
 # ---- 5. the small-batch split plan ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("hid,E,n", [([100] * 4, 10, 50), ([100, 50, 50, 50, 50], 30, 100)])
 def test_small_batch_split_plan_equals_the_unsplit_one(hid, E, n, dev):
-    """B <= 6 rows are one tile whose node range is split over the workgroup's waves; the same rows at the head of a batch too large
-    for that plan run on one wave each.  Same numbers up to the summation order."""
+    """The split plan (one tile per workgroup, its node range split over the workgroup's waves) is taken while tiles x waves per
+    workgroup <= 8 per CU -- up to 8192 rows at four waves on 256 CUs --, so the B = 1 and B = 6 batches here run it; the same rows at
+    the head of a batch too large for that plan run one tile per wave.  Same numbers up to the summation order.  (Every row of such
+    a batch against the truth: tests/test_gpu_solve_coverage.py.)"""
     torch.manual_seed(5)
     net = umnn_amd.IntegrandNetwork(1, 1 + E, hid, 1).to(dev)
     onet = _oracle_net(net)

@@ -105,6 +105,19 @@ def test_targets_outside_the_range_end_on_the_endpoint():
         assert np.all(x_hat.numpy() == -1.)
 
 
+def test_infinite_targets_end_on_the_endpoint():
+    """tol * max(1, |y|) is infinite for an infinite y: the residual test must not take that for convergence at the start point."""
+    G, m = _monotonic(50)
+    y = torch.from_numpy(G["y"][:8]).clone()
+    y[1], y[6] = float("inf"), float("-inf")
+    with torch.no_grad():
+        for lo, hi in ((-50., 50.), (0.5, 8.)):
+            x_hat, _, status = m.inverse(y, torch.from_numpy(G["h"][:8]), x_range=(lo, hi), return_info=True)
+            evals, clamped, capped = _status(status)
+            assert float(x_hat[1]) == hi and float(x_hat[6]) == lo and clamped[1] and clamped[6] and not capped.any()
+            assert evals.max() <= MAX_EVALS and torch.isfinite(x_hat).all()
+
+
 def test_max_iter_caps_and_flags():
     G, m = _monotonic(50)
     with torch.no_grad():

@@ -859,7 +859,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 const float r = sv_scale * (sv_off + Facc[0] * dxv[0] * 0.5f) - sv_target;
                 if (!(__builtin_fabsf(Facc[0]) < __builtin_inff()) || r != r) {
                     sv_bad = true; sv_done = true;                   // an overflowed piece (fp16 build: left to the queued build) or a NaN target
-                } else if (fabsf(r) <= sv.tol * fmaxf(1.f, fabsf(sv_target))) {
+                } else if (fabsf(r) <= sv.tol * fmaxf(1.f, fabsf(sv_target)) && fabsf(r) < __builtin_inff()) {   // (no x meets an infinite target: the bound is infinite too)
                     sv_done = true;
                 } else {
                     if (r > 0.f) {

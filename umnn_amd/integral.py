@@ -417,7 +417,7 @@ def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter):
         r = scale * (off + F) - target
         nonfinite = act & (~torch.isfinite(F) | torch.isnan(r))
         bad |= nonfinite
-        done = done | nonfinite | (act & (r.abs() <= bound))
+        done = done | nonfinite | (act & (r.abs() <= bound) & torch.isfinite(r))    # (no x meets an infinite target: its bound is infinite too)
         act = ~done
         pos = r > 0
         clamped = act & ((pos & (x <= lo)) | (~pos & (x >= hi)))       # the target lies beyond G(lo) / G(hi)
