@@ -141,7 +141,13 @@ int umnn_flow_ll_block_forward(const umnn_mlp* net, const float* x, const float*
  * exp(scaling_j) * (h[b, 0*d+j] + int_0^cand f(t; h[b, :, j]) dt) -- for all B samples in ONE launch.
  *   h      [B, E*d]  conditioner output for the current x_inv (dimensions < j already final; MADE is autoregressive,
  *                    so the caller runs it once per dimension, exactly like the reference :198)
- *   z      [B, d]    targets (column j is read);   x_inv [B, d]: column j is WRITTEN (the round's best candidate)
+ *   z      [B, d]    targets (column j is read);   x_inv [B, d]: column j is WRITTEN (the last round's best candidate)
+ * The bracket after k rounds is one candidate step wide, [cand_m, cand_m+1] or [cand_m-1, cand_m]: the returned candidate lies within
+ * 100 / 9^iters of the solution, up to what the forward error of the images can move a decision by.  A target beyond G(-50) / G(50)
+ * ends on that end exactly -- while the ten fp32 distances |G - z| still differ: for a target so large that they all round to the same
+ * value (+-inf included) the tie goes to candidate 0, as in the reference's argmin, and the search ends near -50 (umnn_cc_solve handles
+ * such targets).  A sample whose target z[b, j] or whose embedding h[b, :, j] holds a NaN returns NaN in x_inv[b, j] (in
+ * every arithmetic mode, after the queued bf16 pass of the fp16-piece mode as well); every other sample is unaffected.
  * UMNN_EUNSUPPORTED for nets with a single hidden layer or images beyond 160 KiB of LDS (callers keep their own loop). */
 int umnn_flow_invert_dim(const umnn_mlp* net, const float* h, const float* z, const float* scaling,
                          const float* cc_w, const float* cc_s, int nb_steps,

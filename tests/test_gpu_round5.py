@@ -566,7 +566,7 @@ def test_sampling_computes_only_the_embedding_columns_it_reads(dev, monkeypatch)
             n0 = _lib.lib().umnn_launch_count()
             out[flag] = model.invert(z, iter=8)
             assert _lib.lib().umnn_launch_count() - n0 == 160
-        tol = 4 * 100.0 * (2.0 / 9.0) ** 8
+        tol = 4 * 100.0 * (2.0 / 9.0) ** 8        # (loose: the search resolves 100 / 9^8 ~ 2e-6)
         assert float((out["1"] - out["0"]).abs().max()) < tol
         assert float((model(out["1"]) - z).abs().max()) < 1e-2
 
@@ -585,7 +585,7 @@ def test_small_batch_sampling_splits_the_node_range_over_the_workgroup(hid, dev)
     z_small = torch.randn(37, 3, device=dev)
     z_big = torch.cat([z_small, torch.randn(3000, 3, device=dev)])
     iters = 9
-    tol = 4 * 100.0 * (2.0 / 9.0) ** iters
+    tol = 4 * 100.0 * (2.0 / 9.0) ** iters        # (loose: the search resolves 100 / 9^iters)
     with torch.no_grad():
         n0 = _lib.lib().umnn_launch_count()
         x_small = model.invert(z_small, iter=iters)

@@ -669,6 +669,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
         }
         const int rounds = INV ? a.inv_iters : 1;
         bool inv_bad = false;            // (fp16 pieces: some candidate integral of some round was not finite -- an overflowed piece)
+        bool inv_nan = false;            // (bracket search: some candidate's distance to the target was not a number in some round)
         for (int round = 0; round < rounds; ++round) {
         if constexpr (INV == 1) {
             xv[0] = __fadd_rn(__fmul_rn(frac, br_right - br_left), br_left);      // x_range * (right - left) + left
@@ -905,6 +906,9 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             // image of every candidate, then argmin_p |z_est - target| over the ten candidate lanes (ties: lower p)
             const float z_est = inv_scale * (inv_off + Facc[0] * dxv[0] * 0.5f);
             float dist = p < 10 ? fabsf(z_est - inv_target) : __builtin_inff();
+            // a distance that is not a number (NaN target, NaN in the embedding) loses every comparison below and would leave lane 0
+            // with its own candidate, a finite value near -50: such a sample returns NaN instead (every lane group holds the same ten)
+            inv_nan = inv_nan || ((__ballot(dist != dist) >> (16 * g)) & 0xffffull) != 0;
             float zm = z_est;
             int m = p;
 #pragma unroll
@@ -942,7 +946,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             // overflow protocol (cc_invert.hip): the sample is left to the queued bf16 build, its slot marked with a NaN
             const bool defer = a.ovf_mode == 1 && __any(inv_bad);
             if (ok[0] && lane == 0 && part == 0) {
-                a.inv_x[qv[0] * d + a.inv_j] = defer ? __builtin_nanf("") : br_best;
+                a.inv_x[qv[0] * d + a.inv_j] = (defer || inv_nan) ? __builtin_nanf("") : br_best;
                 if (defer) atomicMax(a.ovf_flag, a.ovf_gen);
             }
         }

@@ -4,11 +4,13 @@
 // dimension and round, a ParallelNeuralIntegral over [10*B, 1] rows (plus a MADE pass per dimension); here one dimension is
 // the MADE pass + ONE launch of an INV variant of cc_fwd_bf16_kernel (cc_fwd_bf16_kernel.h): tile = sample, lane p = candidate
 // p, the hoisted first-layer term computed once per sample, the argmin / new bracket a 16-lane butterfly between rounds.
-// Arithmetic: bf16x3 split products by default (F to ~6e-6 relative), orders of magnitude inside the search's own resolution
-// (100 * (2/9)^iter).  Under fwd_precision = fp32 / bf16x6 ("the reference's arithmetic everywhere") nets of up to four tiles per
-// layer run the same search with THREE bf16 pieces and six cross terms (PARTS=3: fp32-level products, ~4e-7 on F -- the
-// matrix-core arithmetic of the bf16x6 forward mode; there is no fp32-MFMA form of this kernel); wider nets keep the host-driven
-// search on the forward kernels of that mode (8 tiles x 3 pieces do not fit the register file).
+// Arithmetic: bf16x3 split products in this build (F to ~6e-6 relative), orders of magnitude inside the search's own resolution:
+// the bracket after k rounds is one candidate step wide, [cand_m, cand_m+1] or [cand_m-1, cand_m], i.e. 100 / 9^k.  A sample whose
+// target or embedding is not a number returns NaN (its distances lose every comparison of the argmin: cc_fwd_bf16_kernel.h).
+// Under fwd_precision = fp32 / bf16x6 ("the reference's arithmetic everywhere") nets of up to four tiles per layer run the same
+// search with THREE bf16 pieces and six cross terms (PARTS=3: fp32-level products, ~4e-7 on F -- the matrix-core arithmetic of the
+// bf16x6 forward mode; there is no fp32-MFMA form of this kernel); wider nets, whose three-piece form does not fit the register
+// file (8 tiles x 3 pieces), run the two-fp16-piece search of the f16x3 mode instead (umnn_flow_invert_dim below).
 // This file is compiled twice, like cc_forward_bf16.hip: as is (bf16 pieces; exports umnn_flow_invert_dim) and through cc_invert_f16.hip
 // with -DUMNN_FWD_PIECE_F16 (fp16 pieces: the search of the library's default arithmetic, f16x3).  The fp16 build follows the
 // forward's overflow protocol (cc_forward_bf16.hip): a sample for which any candidate integral of any round was not finite gets a NaN
@@ -51,7 +53,7 @@ static const InvVariant kInvVariants[] = {
     INV_VARIANT(7, 1, 26), INV_VARIANT(7, 1, 0),       // 100-wide toy nets
     INV_VARIANT(5, 1, 0), INV_VARIANT(6, 1, 0), INV_VARIANT(8, 1, 0),
     INV_VARIANT_W8(7, 26), INV_VARIANT_W8(7, 0), INV_VARIANT_W8(5, 0), INV_VARIANT_W8(6, 0), INV_VARIANT_W8(8, 0),
-    INV_VARIANT(2, 0, 0), INV_VARIANT(4, 0, 0), INV_VARIANT(8, 0, 0),   // generic (runtime tile counts): mixed widths, e.g. 100-50-50-50-50
+    INV_VARIANT(2, 0, 0), INV_VARIANT(4, 0, 0), INV_VARIANT(8, 0, 0),   // generic (runtime tile counts): e.g. 20-20, mixed wide 70-90
 #ifndef UMNN_FWD_PIECE_F16
     // three pieces / six cross terms (fwd_precision = fp32 | bf16x6): nets of up to four tiles per layer
     INV_VARIANT3(4, 1, 13), INV_VARIANT3(4, 1, 0), INV_VARIANT3(2, 0, 0), INV_VARIANT3(4, 0, 0),
@@ -207,8 +209,8 @@ extern "C" int umnn_flow_invert_dim(const umnn_mlp* net, const float* h, const f
         const int nparts = prec == UMNN_PRECISION_BF16X3 ? 2 : 3;
         // (8 tiles x 3 bf16 pieces do not fit the register file: nets above four tiles per layer get their fp32-level products from
         // the two-fp16-piece search instead -- the same accuracy class, ~5e-7 on F; a sample whose candidates overflow fp16 is redone
-        // on two bf16 pieces, ~6e-6 on F, three orders of magnitude inside the search's own resolution 100 (2/9)^iter.  Until round 4
-        // this case returned UMNN_EUNSUPPORTED and the caller drove d x iter forward launches from the host)
+        // on two bf16 pieces, ~6e-6 on F, orders of magnitude inside the search's own resolution 100 / 9^iter for all but the last
+        // rounds.  Until round 4 this case returned UMNN_EUNSUPPORTED and the caller drove d x iter forward launches from the host)
         if (nparts == 3 && tmax > 4)
             return umnn_invert_impl_f16(net, h, z, scaling, cc_w, cc_s, nb_steps, B, d, E, j, iters, x_inv, stream, 2, nullptr);
         return umnn_invert_impl_bf16(net, h, z, scaling, cc_w, cc_s, nb_steps, B, d, E, j, iters, x_inv, stream, nparts, nullptr);
