@@ -179,6 +179,23 @@ int umnn_cc_solve(const umnn_mlp* net, const float* h, const float* target, long
                   float lo, float hi, float tol, int max_iter,
                   float* x, long long x_stride, float* f_x, int* status, void* stream);
 
+/* The same solve for every (row, dimension) pair of a flow block in ONE launch -- the inverse of a block under a GIVEN embedding, the
+ * step of the Jacobi iteration behind invert(method="jacobi"): for every (b, i)
+ *     scale_i * (off_bi + int_0^{x_bi} f(t; h[b, :, i]) dt) = target[b, i]        for x_bi in [lo, hi],
+ * scale_i = exp(scaling[i]) (1 when scaling is null), off_bi = h[b, 0*d + i] when off_h0 != 0, else 0.  The iteration, the stop rules,
+ * the status word, the arithmetic modes with the fp16-piece overflow protocol, the net coverage (UMNN_EUNSUPPORTED otherwise) and the
+ * launch count (an fp16-piece launch and its queued pass count as one) are those of umnn_cc_solve.
+ *   h        [B, E*d]  embedding in the flow's stride-d layout        target, x, f_x (nullable), status (nullable)   [B, d]
+ *   rows     the forward kernels' mapping: lane p of tile k holds the flat index q = 16 k + p over B*d, b = q / d, i = q - b d (a tile
+ *            straddles samples and dimensions; scale and offset are per lane).  Both launch plans apply with ceil(B d / 16) tiles.
+ *   x_init   nullable [B, d]: a row's first iterate is x_init[b, i] clamped into [lo, hi] instead of 0 clamped; a non-finite entry means
+ *            a cold start (0) for that row.  May alias x.  When it does, a row the fp16-piece launch defers to the queued bf16 pass has
+ *            lost its start value to the NaN marker and restarts cold there (same solution, more evaluations). */
+int umnn_cc_solve_block(const umnn_mlp* net, const float* h, const float* target, const float* scaling, int off_h0,
+                        const float* x_init, const float* cc_w, const float* cc_s, int nb_steps,
+                        long long B, int d, int E, float lo, float hi, float tol, int max_iter,
+                        float* x, float* f_x, int* status, void* stream);
+
 /* Replaces integrate(..., compute_grad=True) + the Leibniz terms -- ParallelNeuralIntegral.py:66-94,
  * 110-123 (NeuralIntegral.py:47-58,69-75,90-99).  g is grad_output [B,d] (cotangent of F).
  *   g_fx    nullable [B,d]: cotangent of the f_x output of umnn_cc_forward.  The reference gets this

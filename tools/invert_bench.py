@@ -1,9 +1,12 @@
 #!/usr/bin/env python
-"""Times the sampling direction: one block's ``invert(iter=10)`` (the bracket search) against ``invert(method="newton")`` at the
-C3 block (8192 x 63, 31-50^4-1, n = 100) and the MNIST-shaped block (100 x 784, 31-100-50^4-1, n = 100), and
-``MonotonicNN.inverse`` at 65 536 x 1 with the 3-100^3-1 net of the g5 fixtures.
+"""Times the sampling direction: one block's ``invert(iter=10)`` (the bracket search) against ``invert(method="newton")`` and
+``invert(method="jacobi")`` at the C3 block (8192 x 63, 31-50^4-1, n = 100) and the MNIST-shaped block (100 x 784, 31-100-50^4-1,
+n = 100) -- each with default-initialised weights and again with the MADE weights times 3 (cases ``c3_made3`` / ``mnist_made3``:
+stronger coupling between the dimensions, more Jacobi sweeps) --, and ``MonotonicNN.inverse`` at 65 536 x 1 with the 3-100^3-1 net
+of the g5 fixtures.  The jacobi rows carry the sweep count and the largest evaluation count of every sweep.
 
-    python tools/invert_bench.py [--repeats 5] [--warmup 1] [--root TREE] [--out FILE.json] [--only c3,mnist,monotonic]
+    python tools/invert_bench.py [--repeats 5] [--warmup 1] [--root TREE] [--out FILE.json] [--only c3,mnist,c3_made3,mnist_made3,monotonic]
+                                 [--methods bracket,newton,jacobi]
 
 Device-synchronised wall time of whole calls (conditioner passes included), ``--warmup`` untimed calls of every method first, then
 ``--repeats`` rounds that alternate the methods, so drift hits both alike; every figure comes with its min / max / standard
@@ -26,7 +29,8 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default="c3,mnist,monotonic")
+    ap.add_argument("--only", default="c3,mnist,c3_made3,mnist_made3,monotonic")
+    ap.add_argument("--methods", default="bracket,newton,jacobi")
     ap.add_argument("--label", default="")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
@@ -36,7 +40,9 @@ def main():
 
     dev = torch.device("cuda:0")
     has_newton = "method" in inspect.signature(umnn_amd.UMNNMAF.invert).parameters
+    has_jacobi = "sweep_tol" in inspect.signature(umnn_amd.UMNNMAF.invert).parameters
     only = set(args.only.split(","))
+    methods = set(args.methods.split(","))
 
     def sync_time(fn):
         torch.cuda.synchronize()
@@ -70,21 +76,37 @@ def main():
     shapes = {"c3": dict(d=63, hd=[50] * 4, he=[512, 512], E=30, n=100, B=8192),
               "mnist": dict(d=784, hd=[100, 50, 50, 50, 50], he=[1024] * 3, E=30, n=100, B=100)}
     with torch.no_grad():
-        for case, c in shapes.items():
+        for case, c in [(name + tag, dict(c, made_gain=gain)) for name, c in shapes.items() for tag, gain in (("", 1.), ("_made3", 3.))]:
             if case not in only:
                 continue
             torch.manual_seed(0)
             flow = umnn_amd.UMNNMAFFlow(nb_flow=1, nb_in=c["d"], hidden_derivative=c["hd"], hidden_embedding=c["he"],
                                         embedding_s=c["E"], nb_steps=c["n"], solver="CCParallel").to(dev).eval()
             blk = flow.nets[0]
+            if c["made_gain"] != 1.:
+                for mod in blk.net.made.net:
+                    if hasattr(mod, "weight"):
+                        mod.weight.mul_(c["made_gain"])
+                umnn_amd.invalidate_caches(flow)
             x = torch.randn(c["B"], c["d"], device=dev)
             z = blk(x)
-            fns = {"bracket": lambda: blk.invert(z, iter=10)}
-            if has_newton:
+            fns, state = {}, {}
+            if "bracket" in methods:
+                fns["bracket"] = lambda: blk.invert(z, iter=10)
+            if has_newton and "newton" in methods:
                 fns["newton"] = lambda: blk.invert(z, method="newton")
+            if has_jacobi and "jacobi" in methods:
+                def jacobi():
+                    xi, state["info"] = blk.invert(z, method="jacobi", return_info=True)
+                    return xi
+                fns["jacobi"] = jacobi
 
-            def extra(k, outs, x=x):
-                return dict(max_abs_err_x=float((outs[k] - x).abs().max()))
+            def extra(k, outs, x=x, state=state):
+                out = dict(max_abs_err_x=float((outs[k] - x).abs().max()))
+                if k == "jacobi":
+                    info = state["info"]
+                    out.update(sweeps=info["sweeps"], converged=info["converged"], max_evals_per_sweep=info["max_evals"])
+                return out
             results += measure(case, fns, extra)
         if "monotonic" in only and hasattr(umnn_amd.MonotonicNN, "inverse"):
             torch.manual_seed(0)

@@ -62,6 +62,9 @@ SIGNATURES = {
     "umnn_cc_solve": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _ll, _fp, _fp, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int,
                                      _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                      ctypes.c_int, _fp, _ll, _fp, _fp, _fp]),
+    "umnn_cc_solve_block": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int,
+                                           _ll, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                           ctypes.c_int, _fp, _fp, _fp, _fp]),
     "umnn_cc_backward": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                         _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),

@@ -212,7 +212,8 @@ struct Bf16Plan {
 
 // In-kernel Newton solve (cc_solve.hip, INV = 2 variants): scale_b (off_b + int_0^x f(t; h_b) dt) = target_b for x in [lo, hi].
 // The other operands travel in FwdArgs: inv_z = target, inv_x = x, inv_j = the dimension, inv_iters = max_iter, fx = f(x) out,
-// scaling = the flow's log-scales (scale = exp(scaling[inv_j]) unless scale_row is given; null and no scale_row: scale = 1).
+// scaling = the flow's log-scales (scale = exp(scaling[inv_j]) unless scale_row is given; null and no scale_row: scale = 1),
+// x = the first iterate of every row (umnn_cc_solve_block's x_init: indexed like inv_x, may alias it; null = start at 0).
 struct SolveArgs {
     long long t_stride = 0, x_stride = 0;     // row strides (floats) of target / x; column inv_j of each row is used
     const float* scale_row = nullptr;         // [B] per-row scale, nullable
@@ -220,6 +221,10 @@ struct SolveArgs {
     int off_h0 = 0;                           // no off_row: 1 = embedding row 0 of dimension inv_j (the flow's offset), 0 = none
     int* status = nullptr;                    // [B] evaluations | UMNN_SOLVE_* flags, nullable
     float lo = 0.f, hi = 0.f, tol = 0.f;
+    // umnn_cc_solve_block: the rows are the flat [B, d] index q (strides 1, inv_j = 0); row q reads the embedding of sample q / d,
+    // dimension q - (q / d) d, and scaling of that dimension -- the forward kernel's mapping.  Read in the per-tile setup only.
+    // (an int in the struct's tail padding: the kernel arguments keep their size, so nothing the other kernels read moves)
+    int block = 0;
 };
 constexpr int SOLVE_CLAMPED = 1 << 16, SOLVE_CAPPED = 1 << 17, SOLVE_NONFINITE = 1 << 18;      // = UMNN_SOLVE_* of umnn_cc.h
 
@@ -260,6 +265,8 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&&
 // the next iterate is x - r / (scale f(x)), or -- when that leaves (lo, hi) or is not finite -- the endpoint it overshot (once per
 // endpoint: a target beyond G(lo) / G(hi) ends there after one more quadrature) or the midpoint.  The tile leaves the loop on a
 // wave-uniform vote.  The hoisted term depends on h only: computed once for all iterations.
+// umnn_cc_solve_block (SolveArgs::block): the same kernels over every (sample, dimension) of a block -- the rows are the forward's flat
+// index q = b d + i, so lane p reads the embedding of sample q / d at dimension q - (q / d) d; only the per-tile setup differs.
 // WPB: waves per workgroup.  Eight for the shapes whose weight images leave room for ONE workgroup per CU (uniform 6..8-tile nets, deep
 // 5-tile ones: 100-wide toy / MonotonicNN integrands stage 98-147 KB): the second wave of every SIMD then comes from the same
 // workgroup and shares its images, instead of the SIMD running one wave with nothing to overlap its vector phases with.
@@ -315,6 +322,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
 
     if (live) {
         IoView hb[P];
+        int sv_col = a.inv_j;            // (INV = 2) the flow dimension of lane p's row
 #pragma unroll
         for (int pt = 0; pt < P; ++pt) {
             if constexpr (INV == 2) {
@@ -322,7 +330,9 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 ok[pt] = q < a.NI;
                 qv[pt] = ok[pt] ? q : a.NI - 1;
                 xv[pt] = 0.f; x0v[pt] = 0.f; dxv[pt] = 0.f;              // set per iteration
-                hb[pt] = IoView{a.h, a.h_bf16} + (qv[pt] * ((long long)E * d) + a.inv_j);
+                long long bi = qv[pt];
+                if (args.sv.block) { bi = qv[pt] / d; sv_col = (int)(qv[pt] - bi * d); }      // (a tile straddles samples and dimensions)
+                hb[pt] = IoView{a.h, a.h_bf16} + (bi * ((long long)E * d) + sv_col);
             } else if constexpr (INV) {
                 const long long b = (long long)grp * P + pt;             // the tile's sample
                 ok[pt] = b < a.NI;
@@ -659,9 +669,13 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             const SolveArgs& sv = args.sv;
             sv_target = a.inv_z[qv[0] * sv.t_stride + a.inv_j];
             sv_off = sv.off_row ? sv.off_row[qv[0]] : (sv.off_h0 ? hb[0][0] : 0.f);
-            sv_scale = sv.scale_row ? sv.scale_row[qv[0]] : (a.scaling ? __expf(a.scaling[a.inv_j]) : 1.f);
+            sv_scale = sv.scale_row ? sv.scale_row[qv[0]] : (a.scaling ? __expf(a.scaling[sv_col]) : 1.f);
             sv_a = sv.lo; sv_b = sv.hi;
-            sv_x = fminf(fmaxf(0.f, sv.lo), sv.hi);
+            // warm start: the caller's first iterate, when finite (aliasing x: a row the fp16 build deferred reads its NaN marker here
+            // in the queued build and starts cold)
+            float sv_start = 0.f;
+            if (a.x) { const float v = a.x[qv[0] * sv.x_stride + a.inv_j]; if (fabsf(v) < __builtin_inff()) sv_start = v; }
+            sv_x = fminf(fmaxf(sv_start, sv.lo), sv.hi);
             // (queued fallback: only the rows the fp16 build left a NaN for are solved again and written)
             sv_mine = ok[0];
             if (a.ovf_mode == 2) { const float v = a.inv_x[qv[0] * sv.x_stride + a.inv_j]; sv_mine = sv_mine && v != v; }

@@ -10,6 +10,8 @@
 // and otherwise redoes the tiles that hold a NaN, writing only those rows.
 // Small batches: one tile per WORKGROUP, its node range split over the workgroup's waves; partial sums and f(x) meet in LDS once per
 // iteration in a fixed order, so every wave sees the same totals and takes the same branch (100 x 784 image sampling lives here).
+// umnn_cc_solve_block runs the same launch over all B d (sample, dimension) pairs of a block under one embedding, optionally warm-started
+// (one sweep of invert(method="jacobi")): the rows become the flat [B, d] index, everything else here is shared.
 #ifndef UMNN_ASM_TIED
 #define UMNN_ASM_TIED 1      // cc_common.h: inline-assembly outputs tied to inputs in the forward translation units
 #endif
@@ -24,13 +26,15 @@ using namespace UMNN_FWD_NS;
 #endif
 struct InvOvfPlan { int mode; unsigned long long* flag; unsigned long long gen; };
 int umnn_ovf_slot(unsigned long long** flag, unsigned long long* gen);                                  // cc_api.hip
-struct SolveCall {      // the operands of umnn_cc_solve
+struct SolveCall {      // the operands of umnn_cc_solve; umnn_cc_solve_block (block != 0): B = the B d flat rows, strides 1, j = 0
     const float *h, *target, *scale_row, *scaling, *off_row, *cc_w, *cc_s;
     long long t_stride, x_stride, B;
     int off_h0, nb_steps, d, E, j, max_iter;
     float lo, hi, tol;
     float *x, *f_x;
     int* status;
+    int block;
+    const float* x_init;
 };
 int umnn_solve_impl_bf16(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int nparts, const InvOvfPlan* ovf);
 int umnn_solve_impl_f16(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int nparts, const InvOvfPlan* ovf);
@@ -95,12 +99,13 @@ int INV_IMPL(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int np
     auto split_over = [&](int wpb) -> int {
         return (ntiles * (long long)wpb <= (long long)umnn_num_cus() * 8 && wpb <= nb_steps + 1) ? wpb : 1;
     };
-    a.x0 = nullptr; a.x = nullptr; a.h = c.h; a.ccw = c.cc_w; a.ccs = c.cc_s;
+    a.x0 = nullptr; a.x = c.x_init; a.h = c.h; a.ccw = c.cc_w; a.ccs = c.cc_s;
     a.F = a.fx0 = nullptr; a.fx = c.f_x; a.scaling = c.scaling; a.z = nullptr; a.logjac = nullptr; a.logjac_in = nullptr;
     a.reverse_z = 0; a.ll = nullptr; a.row_cnt = nullptr; a.ll_first = a.ll_last = 0;
     a.inv_z = c.target; a.inv_x = c.x; a.inv_j = c.j; a.inv_iters = c.max_iter;
     args.sv.t_stride = c.t_stride; args.sv.x_stride = c.x_stride; args.sv.scale_row = c.scale_row; args.sv.off_row = c.off_row;
     args.sv.off_h0 = c.off_h0; args.sv.status = c.status; args.sv.lo = c.lo; args.sv.hi = c.hi; args.sv.tol = c.tol;
+    args.sv.block = c.block;
     a.NI = B; a.d = d; a.E = E; a.n = nb_steps; a.inv_f = 0; a.ns = 1; a.x_bf16 = 0; a.h_bf16 = 0; a.z2_save = nullptr; a.z2_nl2 = 0;
 
     // ---- wide first hidden layer, every other layer at most four tiles: shape-exact family (as in cc_forward_bf16.hip)
@@ -204,10 +209,36 @@ extern "C" int umnn_cc_solve(const umnn_mlp* net, const float* h, const float* t
     if (!h || !target || !cc_w || !cc_s || !x) return umnn_fail(UMNN_EINVAL, "solve: null pointer");
     if (m.n_linear - 1 < 2) return umnn_fail(UMNN_EUNSUPPORTED, "solve: the matrix-core kernels need at least two hidden layers");
     const SolveCall c{h, target, scale_row, scaling, off_row, cc_w, cc_s, t_stride, x_stride, B, off_h0, nb_steps, d, E, j, max_iter,
-                      lo, hi, tol, x, f_x, status};
+                      lo, hi, tol, x, f_x, status, 0, nullptr};
     // arithmetic modes as in umnn_flow_invert_dim (cc_invert.hip): f16x3 = two fp16 pieces with the queued bf16x3 fallback; bf16x3 = two
     // bf16 pieces; fp32 / bf16x6 = three bf16 pieces up to four tiles per layer, two fp16 pieces (the same accuracy class) above
     const int prec = umnn_options().fwd_precision;
+    if (prec == UMNN_PRECISION_F16X3) return umnn_solve_impl_f16(net, c, stream, 2, nullptr);
+    const int nparts = prec == UMNN_PRECISION_BF16X3 ? 2 : 3;
+    if (nparts == 3 && tmax > 4) return umnn_solve_impl_f16(net, c, stream, 2, nullptr);
+    return umnn_solve_impl_bf16(net, c, stream, nparts, nullptr);
+}
+
+// The same solve for every (row, dimension) of a block in ONE launch (include/umnn_cc.h): the rows of the launch are the flat index
+// q = b d + i over [B, d], sixteen to a tile as in the forward kernels; everything else -- variants, plans, modes -- is umnn_cc_solve's.
+extern "C" int umnn_cc_solve_block(const umnn_mlp* net, const float* h, const float* target, const float* scaling, int off_h0,
+                                   const float* x_init, const float* cc_w, const float* cc_s, int nb_steps,
+                                   long long B, int d, int E, float lo, float hi, float tol, int max_iter,
+                                   float* x, float* f_x, int* status, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!net) return umnn_fail(UMNN_EINVAL, "net is null");
+    if (nb_steps < 1 || max_iter < 1 || max_iter > UMNN_SOLVE_EVALS_MASK)
+        return umnn_fail(UMNN_EINVAL, "solve: nb_steps >= 1 and 1 <= max_iter <= 65535");
+    if (B < 0 || d < 1) return umnn_fail(UMNN_EINVAL, "solve: B >= 0, d >= 1");
+    if (!(lo < hi) || !(tol >= 0.f)) return umnn_fail(UMNN_EINVAL, "solve: lo < hi and tol >= 0");
+    MlpDev m; int tmax = 0, ksu = 0;
+    if (int rc = umnn_prepare_mlp(net, E, &m, &tmax, &ksu)) return rc;
+    if (B == 0) return 0;
+    if (!h || !target || !cc_w || !cc_s || !x) return umnn_fail(UMNN_EINVAL, "solve: null pointer");
+    if (m.n_linear - 1 < 2) return umnn_fail(UMNN_EUNSUPPORTED, "solve: the matrix-core kernels need at least two hidden layers");
+    const SolveCall c{h, target, nullptr, scaling, nullptr, cc_w, cc_s, 1, 1, B * (long long)d, off_h0, nb_steps, d, E, 0, max_iter,
+                      lo, hi, tol, x, f_x, status, 1, x_init};
+    const int prec = umnn_options().fwd_precision;                 // (modes as in umnn_cc_solve)
     if (prec == UMNN_PRECISION_F16X3) return umnn_solve_impl_f16(net, c, stream, 2, nullptr);
     const int nparts = prec == UMNN_PRECISION_BF16X3 ? 2 : 3;
     if (nparts == 3 && tmax > 4) return umnn_solve_impl_f16(net, c, stream, 2, nullptr);

@@ -254,18 +254,29 @@ class UMNNMAF(nn.Module):
             return _I.aten_forward(lambda t, hh: integrand.independant_forward(torch.cat((t, hh), 1)),
                                    torch.zeros_like(cand), cand, h_j, self.nb_steps)
 
-    def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64):
+    def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None,
+               return_info=False):
         """Dimension-by-dimension bracket search: 10 candidates per round on [left,right] (starting at +-50), keep
         the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232).  Eager only:
         compiled callers get an eager call; under torch.jit.trace it raises.
         ``method="newton"`` (an extension; ``iter`` is ignored): the same dimension-by-dimension structure with the safeguarded Newton
         solve of ``umnn_cc_solve`` on [-50, 50] in place of the search -- residual to ``tol * max(1, |z_j|)``, at most ``max_iter``
-        quadratures per dimension, typically four."""
-        if method not in ("bracket", "newton"):
-            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket' or 'newton'")
+        quadratures per dimension, typically four.
+        ``method="jacobi"`` (an extension; ``iter`` is ignored): the Jacobi iteration of ``_invert_jacobi`` -- every sweep is one full
+        conditioner pass and ONE solve of all d dimensions under that embedding (``umnn_cc_solve_block``), warm-started from the previous
+        sweep; stops when no entry moved by more than ``sweep_tol * max(1, |x|)`` or after ``max_sweeps`` sweeps (default d, where the
+        result is the sequential one by construction).  ``return_info=True`` (jacobi only) -> (x, info)."""
+        if method not in ("bracket", "newton", "jacobi"):
+            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
         if torch.jit.is_tracing():
             raise RuntimeError("umnn_amd: UMNNMAF.invert cannot be traced by torch.jit.trace (data-dependent bracket search); "
                                "call it eagerly")
+        if method == "jacobi":
+            fn = torch.compiler.disable(UMNNMAF._invert_jacobi) if torch.compiler.is_compiling() else UMNNMAF._invert_jacobi
+            x, info = fn(self, z, context, tol, max_iter, sweep_tol, max_sweeps, return_info)
+            return (x, info) if return_info else x
+        if return_info:
+            raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
         if method == "newton":
             if torch.compiler.is_compiling():
                 return torch.compiler.disable(UMNNMAF._invert_newton)(self, z, context, tol, max_iter)
@@ -323,6 +334,64 @@ class UMNNMAF(nn.Module):
                 x_j, _, _ = _I.newton_solve(eval_fn, z[:, [j]], torch.exp(self.scaling[j]).to(z.dtype), h_j[:, [0]], -50., 50., tol, max_iter)
                 x_inv[:, j] = x_j[:, 0]
         return x_inv
+
+    def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False):
+        """``invert(method="jacobi")``: x <- 0; repeat { h <- conditioner(x); x_i <- solve_i(z_i; h) for EVERY i }.  The conditioner is
+        autoregressive, so dimension i is final once x_<i are: after sweep t the first t dimensions hold the sequential answer, d sweeps
+        reproduce ``method="newton"``, and a fixed point is the inverse.  HIP path: per sweep one conditioner pass and ONE launch over the
+        B d rows (``umnn_cc_solve_block``), every sweep after the first warm-started from the previous x; host tensors, other dtypes
+        and nets the solve kernels do not cover run the same sweeps through ``integral.newton_solve`` over [B, d].
+        Stops when max |x_new - x| / max(1, |x_new|) <= ``sweep_tol`` (one scalar device-to-host read per sweep; ``sweep_tol`` = 0: no
+        test and no read), in any case after ``max_sweeps`` sweeps (default d).  -> (x, info); info (``want_info``) = {"sweeps",
+        "converged": the test was met or d sweeps ran, "status": the last sweep's status words [B,d], "max_evals": per sweep}."""
+        B, d = z.shape
+        dev = z.device
+        integrand = self.net.parallel_nets
+        spec = mlp_spec(integrand)
+        use_hip = _I._use_hip(spec, z) and self.nb_steps >= 1 and self.solver in _SOLVERS
+        in_kernel = use_hip and z.dtype == torch.float32 and B > 0
+        max_sweeps = d if max_sweeps is None else int(max_sweeps)
+        if max_sweeps < 1:
+            raise ValueError("umnn_amd: invert(method='jacobi') needs max_sweeps >= 1")
+        with torch.no_grad():
+            z = z.contiguous()
+            x = torch.zeros(B, d, device=dev, dtype=z.dtype)
+            scaling = self.scaling.detach().float().contiguous()
+            sweeps, met, status, evals = 0, False, None, []
+            for sweep in range(max_sweeps):
+                h = self.net.make_embeding(x, context)
+                x_init = x if sweep > 0 else None
+                out = None
+                if in_kernel:
+                    # (umnn_cc_solve_block reads an fp32 embedding; widening bf16 is exact)
+                    out = _I.hip_solve_block(spec, h.float().contiguous(), z, self.nb_steps, scaling=scaling, off_h0=True, x_init=x_init,
+                                             lo=-50., hi=50., tol=tol, max_iter=max_iter, want_info=want_info)
+                    in_kernel = out is not None
+                if out is None:
+                    def eval_fn(xc, h=h):
+                        if use_hip and xc.dtype == torch.float32:
+                            F, fx, _ = _I.hip_forward(spec, None, xc, h, self.nb_steps)
+                            return F, fx
+                        hh = h.to(xc.dtype)
+                        return _I.aten_forward(integrand, torch.zeros_like(xc), xc, hh, self.nb_steps), integrand(xc, hh)
+                    off = h.view(B, -1, d)[:, 0, :].to(z.dtype)
+                    out = _I.newton_solve(eval_fn, z, torch.exp(self.scaling).to(z.dtype).unsqueeze(0), off, -50., 50., tol, max_iter,
+                                          x_init=x_init)
+                x_new, status = out[0], out[2]
+                sweeps += 1
+                if want_info:
+                    evals.append((status & _I._lib.SOLVE_EVALS_MASK).max() if B > 0 else torch.zeros((), dtype=torch.int32, device=dev))
+                if sweep_tol > 0:
+                    moved = (x_new - x).abs() > sweep_tol * x_new.abs().clamp(min=1.)      # (a NaN row never counts as moving)
+                    met = not bool(moved.any())
+                x = x_new
+                if met:
+                    break
+        info = None
+        if want_info:
+            info = {"sweeps": sweeps, "converged": bool(met or sweeps >= d), "status": status,
+                    "max_evals": [int(e) for e in torch.stack(evals).tolist()]}
+        return x, info
 
     def _invert(self, z, iter=10, context=None):
         K = 10
@@ -448,14 +517,23 @@ class UMNNMAFFlow(nn.Module):
     def forward(self, x, context=None):
         return self._stack(x, context, False)[0]
 
-    def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64):
+    def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None,
+               return_info=False):
         """Sampling direction, block by block.  ``method="bracket"`` (default): the reference's search, ``iter`` rounds.
-        ``method="newton"``: the in-kernel Newton solve (``UMNNMAF.invert``), exactly nb_flow x d solve launches; ``iter`` is ignored."""
-        if method not in ("bracket", "newton"):
-            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket' or 'newton'")
+        ``method="newton"``: the in-kernel Newton solve (``UMNNMAF.invert``), exactly nb_flow x d solve launches; ``iter`` is ignored.
+        ``method="jacobi"``: the Jacobi iteration of ``UMNNMAF.invert`` in every block, one solve launch per sweep;
+        ``return_info=True`` -> (x, info) with info's entries as lists over the blocks in flow order."""
+        if method not in ("bracket", "newton", "jacobi"):
+            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
         if torch.jit.is_tracing():
             raise RuntimeError("umnn_amd: UMNNMAFFlow.invert cannot be traced by torch.jit.trace (data-dependent bracket "
                                "search); call it eagerly")
+        if method == "jacobi":
+            fn = torch.compiler.disable(UMNNMAFFlow._invert_jacobi) if torch.compiler.is_compiling() else UMNNMAFFlow._invert_jacobi
+            x, info = fn(self, z, context, tol, max_iter, sweep_tol, max_sweeps, return_info)
+            return (x, info) if return_info else x
+        if return_info:
+            raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
         if method == "newton":
             if torch.compiler.is_compiling():
                 return torch.compiler.disable(UMNNMAFFlow._invert_newton)(self, z, context, tol, max_iter)
@@ -469,6 +547,15 @@ class UMNNMAFFlow(nn.Module):
         for i in range(len(self.nets) - 1, -1, -1):
             z = self.nets[i].invert(torch.flip(z, [1]), context=context, method="newton", tol=tol, max_iter=max_iter)
         return z
+
+    def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False):
+        nb = len(self.nets)
+        infos = [None] * nb
+        z = torch.flip(z, [1])
+        for i in range(nb - 1, -1, -1):
+            z, infos[i] = self.nets[i]._invert_jacobi(torch.flip(z, [1]), context, tol, max_iter, sweep_tol, max_sweeps, want_info)
+        info = {k: [inf[k] for inf in infos] for k in ("sweeps", "converged", "status", "max_evals")} if want_info else None
+        return z, info
 
     def _invert(self, z, iter=10, context=None):
         z = torch.flip(z, [1])

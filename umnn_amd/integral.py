@@ -396,12 +396,49 @@ def hip_solve(spec, h, target, nb_steps, j=0, scale_row=None, scaling=None, off_
     return x_out, fx, status
 
 
-def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter):
+def hip_solve_block(spec, h, target, nb_steps, scaling=None, off_h0=False, x_init=None, lo=-50., hi=50., tol=1e-6, max_iter=64,
+                    want_info=True, x_out=None):
+    """Newton solve of EVERY (row, dimension) of a block under the given embedding in ONE launch (umnn_cc_solve_block):
+    exp(scaling[i]) (off + int_0^x f(t; h[b, :, i]) dt) = target[b, i], off = h[b, 0*d + i] when ``off_h0``.  ``target`` [B,d] and ``h``
+    [B,E*d] fp32 contiguous; ``x_init`` [B,d] fp32 contiguous or None: the first iterate of every row (clamped into [lo, hi]; a
+    non-finite entry starts that row at 0; may be ``x_out`` itself).  -> (x [B,d], f_x [B,d], status [B,d] int32), the last two None
+    unless ``want_info``.  Returns None when the library has no kernel for this net: the caller runs ``host_solve``."""
+    lib = _lib.lib()
+    B, d = target.shape
+    E = h.shape[1] // d
+    if E * d != h.shape[1] or spec.linears[0].in_features != 1 + E:
+        raise RuntimeError("umnn_amd: embedding width does not match the integrand")
+    w, s = device_tables(nb_steps, target.device)
+    if x_out is None:
+        x_out = torch.empty(B, d, device=target.device, dtype=torch.float32)
+    fx = torch.empty(B, d, device=target.device, dtype=torch.float32) if want_info else None
+    status = torch.empty(B, d, device=target.device, dtype=torch.int32) if want_info else None
+    desc, keep = _desc(spec)
+    with torch.cuda.device(target.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(target.device).cuda_stream)
+        rc = lib.umnn_cc_solve_block(ctypes.byref(desc), _ptr(h), _ptr(target), _ptr(scaling), 1 if off_h0 else 0, _ptr(x_init),
+                                     _ptr(w), _ptr(s), int(nb_steps), B, d, E, float(lo), float(hi), float(tol), int(max_iter),
+                                     _ptr(x_out), _ptr(fx), _ptr(status), stream)
+    if rc == _lib.EUNSUPPORTED:
+        _warn_once(("solve-host", tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
+                   "umnn_amd: no in-kernel Newton solve for this integrand / arithmetic mode "
+                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): the inverse runs the host-driven Newton loop "
+                   "(one forward launch per iteration).")
+        return None
+    _lib.check(rc, "umnn_cc_solve_block")
+    _state.path = "hip"
+    return x_out, fx, status
+
+
+def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=None):
     """The safeguarded Newton iteration of umnn_cc_solve (include/umnn_cc.h) in torch ops, elementwise on tensors of any shape:
     solves scale (off + F(x)) = target on [lo, hi], where ``eval_fn(x) -> (F(x), f(x))`` with f = dF/dx > 0.  The host-driven
-    loop over ``hip_forward`` and the generic ATen path are this function.  -> (x, f(x), status int32)."""
+    loop over ``hip_forward`` and the generic ATen path are this function.  ``x_init`` (shaped like ``target``, optional): the first
+    iterate, clamped into [lo, hi]; non-finite entries start at 0 like every row without it.  -> (x, f(x), status int32)."""
     lo, hi = float(lo), float(hi)
     x = torch.full_like(target, min(max(0., lo), hi))
+    if x_init is not None:
+        x = torch.where(torch.isfinite(x_init), x_init.to(target.dtype), torch.zeros_like(target)).clamp(lo, hi)
     a, b = torch.full_like(target, lo), torch.full_like(target, hi)
     a_open = torch.ones_like(target, dtype=torch.bool)
     b_open, done, bad = a_open.clone(), ~a_open, ~a_open
@@ -450,23 +487,23 @@ def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter):
     return x, fx, evals | flags
 
 
-def host_solve(spec, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0.):
+def host_solve(spec, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0., x_init=None):
     """Host-driven Newton loop over ``hip_forward`` (F and f_x in one launch per iteration): what runs when the library
     answers UMNN_EUNSUPPORTED for the in-kernel solve.  ``target`` [B,d], ``h`` [B,E*d] -> (x, f_x, status), each [B,d]."""
     def eval_fn(x):
         F, fx, _ = hip_forward(spec, None, x, h, nb_steps)
         return F, fx
     with torch.no_grad():
-        return newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter)
+        return newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=x_init)
 
 
-def aten_solve(integrand, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0.):
+def aten_solve(integrand, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0., x_init=None):
     """Generic ATen path of the inverse (CPU tensors, float64, integrands ``mlp_spec`` does not recognise): the same
     algorithm on ``aten_forward``."""
     def eval_fn(x):
         return aten_forward(integrand, torch.zeros_like(x), x, h, nb_steps), integrand(x, h)
     with torch.no_grad():
-        out = newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter)
+        out = newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=x_init)
     _state.path = "aten"
     return out
 
