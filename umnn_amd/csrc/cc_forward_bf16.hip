@@ -1,9 +1,9 @@
 // Forward quadrature on the bf16 matrix cores: variant table and launcher (the kernel template, with its layout notes,
-// lives in cc_fwd_bf16_kernel.h and is shared with the inversion variants of cc_invert.hip).
+// lives in cc_fwd_bf16_kernel.h and is shared with the inverse variants of cc_inv_launch.h; the image layout is cc_fwd_plan.h's).
 #ifndef UMNN_ASM_TIED
 #define UMNN_ASM_TIED 1      // cc_common.h: inline-assembly outputs tied to inputs in the forward translation units
 #endif
-#include "cc_fwd_bf16_kernel.h"
+#include "cc_fwd_plan.h"
 using namespace UMNN_FWD_NS;
 // (this file is compiled twice: as is -- bf16 pieces, umnn_launch_forward_bf16 -- and through cc_forward_f16.hip with
 // -DUMNN_FWD_PIECE_F16 -- fp16 pieces, umnn_launch_forward_f16, kernel names cc_fwd_f16<...>)
@@ -115,18 +115,9 @@ int FWD_LAUNCH(FwdArgs& a, const umnn_mlp* net, int nparts, int P, int ns, int n
     const bool p_forced = opt.fwd_p > 0 || fb, ns_forced = opt.fwd_ns > 0 || fb;
     int tmax = 0;
     for (int l = 1; l <= L; ++l) tmax = a.m.t_out[l] > tmax ? a.m.t_out[l] : tmax;
-    int T = tmax <= 2 ? 2 : tmax <= 4 ? 4 : 8;
-    // every hidden layer the same tile count above four: exact single-tile variants, odd counts with a half K-step
-    int wide = (nparts == 2 && tmax >= 5) ? tmax : 0;
-    for (int l = 1; l <= L && wide; ++l) if (a.m.t_out[l] != wide) wide = 0;
-    if (wide && (P == 1 || !p_forced)) { T = wide; P = 1; } else wide = 0;    // (no two-tile variant at these widths)
-    // uniform wide nets: how many workgroups of images fit a CU?  One -> eight waves per workgroup (both waves of every SIMD share the
-    // images); two -> four waves each.  Either way a CU runs eight waves.
-    int wpb = UMNN_WAVES_PER_BLOCK;
-    if (wide) {
-        const size_t img = (size_t)(L - 1) * wide * ((wide / 2) * nparts * 512 + (wide & 1) * nparts * 256) * sizeof(unsigned short);
-        if (2 * (img + 1024) > 160 * 1024) wpb = 8;
-    }
+    // uniform wide nets: two-piece single-tile variants only (no two-tile variant at these widths)
+    int wide = nparts == 2 ? fwd_uniform_wide(a.m, tmax) : 0;
+    if (wide && (P == 1 || !p_forced)) P = 1; else wide = 0;
     if (wide && !ns_forced) {
         // split the node range only as far as that fills the SIMDs (two waves each)
         const long long tiles16 = (a.NI + 15) / 16, slots = (long long)umnn_num_cus() * 8;
@@ -135,74 +126,31 @@ int FWD_LAUNCH(FwdArgs& a, const umnn_mlp* net, int nparts, int P, int ns, int n
     }
     FwdBf16Args args;
     args.f = a;
-    // ---- wide first hidden layer over a narrow rest: its own shape-exact family
-    {
-        bool wf = nparts == 2 && L >= 2 && a.m.t_out[1] >= 5 && a.m.t_out[1] <= 8 && (P == 1 || !p_forced);
-        for (int l = 2; l <= L && wf; ++l) if (a.m.t_out[l] > 4) wf = false;
-        if (wf) {
-            const int T1 = a.m.t_out[1];
-            int o16 = 0;
-            for (int l = 1; l <= L; ++l) {
-                args.pl.ks32[l] = l == 1 ? T1 / 2 : 2;
-                args.pl.half_in[l] = l == 1 ? (T1 & 1) : 0;
-                if (l >= 2) args.f.m.t_out[l] = 4;
-            }
-            for (int l = 1; l < L; ++l) {
-                args.pl.off16[l] = o16;
-                o16 += 4 * (args.pl.ks32[l] * 2 * 512 + args.pl.half_in[l] * 2 * 256);
-            }
-            args.f.m.lds_off[L] = (((o16 + 1) / 2) + 3) & ~3;
-            if (!ns_forced) {
-                const long long tiles16 = (a.NI + 15) / 16, slots = (long long)umnn_num_cus() * 4 * 2;
-                ns = tiles16 * 4 <= slots ? 4 : tiles16 * 2 <= slots ? 2 : 1;
-                if (ns > nb_steps + 1) ns = 1;
-            }
-            const int PW = 1;
-            const size_t lds_bytes = ((size_t)args.f.m.lds_off[L] + (ns > 1 ? UMNN_WAVES_PER_BLOCK * 3 * PW * 16 : 0)) * sizeof(float);
-            int nrest = a.m.ks_in[2];           // live registers of the later layers when they all agree (13 = widths 48..51)
-            for (int l = 2; l <= L; ++l) if (a.m.ks_in[l] != nrest) nrest = 0;
-            if (nrest != 13) nrest = 0;
-            const Bf16WideFirst* pick = nullptr;
-            for (const Bf16WideFirst& v : kBf16WideFirst) if (v.t1 == T1 && v.nrl == nrest && v.p == PW) pick = &v;
-            if (!pick) for (const Bf16WideFirst& v : kBf16WideFirst) if (v.t1 == T1 && v.nrl == nrest && v.p == 1) pick = &v;
-            if (pick && lds_bytes <= 160 * 1024) {
-                if (int rc = umnn_allow_lds((const void*)pick->fn, lds_bytes)) return rc;
-                args.f.ns = ns;
-                args.f.ngroups = (unsigned)((a.NI + 16 * pick->p - 1) / (16 * pick->p));
-                const unsigned gpb = UMNN_WAVES_PER_BLOCK / ns;
-                const unsigned nblk = (args.f.ngroups + gpb - 1) / gpb;
-                return launch_planned(pick->fn, pick->name, nblk, lds_bytes, args, a, net, pick->p, ns, nb_steps, stream, ovf, UMNN_BLOCK);
-            }
-            args.f = a;         // (not launched: fall through to the generic plan)
+    // ---- wide first hidden layer over a narrow rest: its own shape-exact family (cc_fwd_plan.h)
+    FwdLayout lay;
+    if (nparts == 2 && (P == 1 || !p_forced) && fwd_plan_wide_first(args, nparts, &lay)) {
+        if (!ns_forced) {
+            const long long tiles16 = (a.NI + 15) / 16, slots = (long long)umnn_num_cus() * 4 * 2;
+            ns = tiles16 * 4 <= slots ? 4 : tiles16 * 2 <= slots ? 2 : 1;
+            if (ns > nb_steps + 1) ns = 1;
         }
+        const size_t lds_bytes = ((size_t)args.f.m.lds_off[L] + (ns > 1 ? UMNN_WAVES_PER_BLOCK * 3 * 16 : 0)) * sizeof(float);
+        const Bf16WideFirst* pick = nullptr;
+        for (const Bf16WideFirst& v : kBf16WideFirst) if (v.t1 == lay.T && v.nrl == lay.nrl && v.p == 1) pick = &v;
+        if (pick && lds_bytes <= 160 * 1024) {
+            if (int rc = umnn_allow_lds((const void*)pick->fn, lds_bytes)) return rc;
+            args.f.ns = ns;
+            args.f.ngroups = (unsigned)((a.NI + 16 * pick->p - 1) / (16 * pick->p));
+            const unsigned gpb = UMNN_WAVES_PER_BLOCK / ns;
+            const unsigned nblk = (args.f.ngroups + gpb - 1) / gpb;
+            return launch_planned(pick->fn, pick->name, nblk, lds_bytes, args, a, net, pick->p, ns, nb_steps, stream, ovf, UMNN_BLOCK);
+        }
+        args.f = a;         // (not launched: fall through to the generic plan)
     }
     if (a.z2_save) return UMNN_EUNSUPPORTED;      // (only the wide-first kernels above know how to leave z_2 behind)
-    int off16 = 0;
-    for (int l = 1; l <= L; ++l) {
-        args.pl.half_in[l] = wide ? (wide & 1) : 0;
-        args.pl.ks32[l] = wide ? wide / 2 : (a.m.t_out[l] + 1) / 2;
-    }
-    for (int l = 1; l < L; ++l) {
-        args.pl.off16[l] = off16;
-        off16 += a.m.t_out[l + 1] * (args.pl.ks32[l] * nparts * 512 + args.pl.half_in[l] * nparts * 256);
-    }
-    const int img_floats = (off16 + 1) / 2;
-    args.f.m.lds_off[L] = (img_floats + 3) & ~3;          // NS-reduction scratch starts after the images
-    int exact = 1, nrl = a.m.ks_in[1];        // live registers per lane when every hidden layer has the same K-step count
-    for (int l = 1; l <= L; ++l) {
-        exact = exact && a.m.t_out[l] == T;
-        if (a.m.ks_in[l] != nrl) nrl = 0;
-    }
-    // Mixed or narrow widths up to 63: zero-pad every layer to four tiles (the staged images carry the zeros) and run
-    // the shape-exact kernels -- the padded MFMAs cost less than the runtime guards of the generic variants
-    // (UMNN_FWD_PAD=0 keeps the generic ones).
-    if (!exact && !wide && nparts == 2 && tmax <= 4 && tmax >= opt.fwd_pad_min && opt.fwd_pad) {
-        T = 4; exact = 1; nrl = 0;
-        for (int l = 1; l <= L; ++l) { args.f.m.t_out[l] = 4; args.pl.ks32[l] = 2; }
-        off16 = 0;
-        for (int l = 1; l < L; ++l) { args.pl.off16[l] = off16; off16 += 4 * 2 * nparts * 512; }
-        args.f.m.lds_off[L] = (((off16 + 1) / 2) + 3) & ~3;
-    }
+    // mixed or narrow widths up to 63 run zero-padded on the shape-exact kernels (UMNN_FWD_PAD=0 keeps the generic ones)
+    lay = fwd_plan_images(args, nparts, tmax, wide, nparts == 2 && opt.fwd_pad, opt.fwd_pad_min);
+    const int T = lay.T, exact = lay.exact, nrl = lay.nrl;
     const bool want_pipe = opt.fwd_pipe != 0 && L >= 2;
     // the 32x32x16 formulation of the flagship shape: opt-in (UMNN_FWD_PIPE=2 / option fwd_pipe = 2).  Same wall time as the
     // default at C3 with 10 % fewer cycles -- the chip clocks it lower (the kernel is power-bound)
@@ -216,7 +164,9 @@ int FWD_LAUNCH(FwdArgs& a, const umnn_mlp* net, int nparts, int P, int ns, int n
     // (measured at the POWER and VAE shapes: P=2, NS=1 beats every P=1 split by 6-7 %)
     if (want_pipe && exact && T == 4 && nparts == 2 && !p_forced && !ns_forced &&
         (a.NI + 15) / 16 >= 2LL * umnn_num_cus() * 4) { P = 2; ns = 1; }
-    if (!(wide && exact)) wpb = UMNN_WAVES_PER_BLOCK;
+    // uniform wide nets: how many workgroups of images fit a CU?  One -> eight waves per workgroup (both waves of every SIMD share the
+    // images); two -> four waves each.  Either way a CU runs eight waves.
+    int wpb = wide && exact && 2 * ((size_t)args.f.m.lds_off[L] * sizeof(float) + 1024) > 160 * 1024 ? 8 : UMNN_WAVES_PER_BLOCK;
     size_t lds_bytes = ((size_t)args.f.m.lds_off[L] + (ns > 1 ? wpb * 3 * P * 16 : 0)) * sizeof(float);
     if (lds_bytes > 160 * 1024 && wpb == 8) { wpb = UMNN_WAVES_PER_BLOCK; lds_bytes = ((size_t)args.f.m.lds_off[L] + (ns > 1 ? wpb * 3 * P * 16 : 0)) * sizeof(float); }
     if (lds_bytes > 160 * 1024) return UMNN_EUNSUPPORTED;

@@ -337,29 +337,53 @@ def hip_flow_block(spec, x, h, scaling, nb_steps, reverse_z=False, log_jac_in=No
     return z, lj, fx, fx0
 
 
-def hip_invert_dim(spec, h, z, scaling, nb_steps, j, iters, x_inv):
-    """Bracket search of flow dimension j for every sample in ONE launch (umnn_flow_invert_dim): writes x_inv[:, j].
-    Returns False when the library has no kernel for this net (single hidden layer / LDS): the caller keeps its own loop."""
+def _inverse_call(fn_name, spec, h, rows, nb_steps, call, warn_key, warn_text):
+    """What the in-kernel inverse entry points share: ``rows`` [B,d] gives B, d and the device; checks the embedding, makes the
+    quadrature tables and runs ``call(lib, desc, w, s, B, d, E, stream)`` -> rc on the current stream.  False (after a one-time
+    warning) when the library has no kernel for this net, else True; any other error raises."""
     lib = _lib.lib()
-    B, d = z.shape
+    B, d = rows.shape
     E = h.shape[1] // d
     if E * d != h.shape[1] or spec.linears[0].in_features != 1 + E:
         raise RuntimeError("umnn_amd: embedding width does not match the integrand")
-    w, s = device_tables(nb_steps, z.device)
+    w, s = device_tables(nb_steps, rows.device)
     desc, keep = _desc(spec)
-    with torch.cuda.device(z.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(z.device).cuda_stream)
-        rc = lib.umnn_flow_invert_dim(ctypes.byref(desc), _ptr(h), _ptr(z), _ptr(scaling), _ptr(w), _ptr(s), int(nb_steps),
-                                      B, d, E, int(j), int(iters), _ptr(x_inv), stream)
+    with torch.cuda.device(rows.device):
+        stream = ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
+        rc = call(lib, ctypes.byref(desc), _ptr(w), _ptr(s), B, d, E, stream)
     if rc == _lib.EUNSUPPORTED:
-        _warn_once(("invert-host", tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
-                   "umnn_amd: no in-kernel inversion for this integrand / arithmetic mode "
-                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): UMNNMAF.invert runs the host-driven bracket "
-                   "search (d x iter forward launches per block).")
+        _warn_once((warn_key, tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
+                   warn_text.format(_lib.lib().umnn_last_error().decode('utf-8', 'replace')))
         return False
-    _lib.check(rc, "umnn_flow_invert_dim")
+    _lib.check(rc, fn_name)
     _state.path = "hip"
     return True
+
+
+def hip_invert_dim(spec, h, z, scaling, nb_steps, j, iters, x_inv):
+    """Bracket search of flow dimension j for every sample in ONE launch (umnn_flow_invert_dim): writes x_inv[:, j].
+    Returns False when the library has no kernel for this net (single hidden layer / LDS): the caller keeps its own loop."""
+    return _inverse_call(
+        "umnn_flow_invert_dim", spec, h, z, nb_steps,
+        lambda lib, desc, w, s, B, d, E, stream: lib.umnn_flow_invert_dim(
+            desc, _ptr(h), _ptr(z), _ptr(scaling), w, s, int(nb_steps), B, d, E, int(j), int(iters), _ptr(x_inv), stream),
+        "invert-host", "umnn_amd: no in-kernel inversion for this integrand / arithmetic mode ({}): UMNNMAF.invert runs the "
+        "host-driven bracket search (d x iter forward launches per block).")
+
+
+def _solve_call(fn_name, spec, h, target, nb_steps, x_out, want_info, info_shape, call):
+    """hip_solve / hip_solve_block: allocates x_out (when None) and the ``info_shape`` f_x / status (when ``want_info``), runs
+    ``call(lib, desc, w, s, B, d, E, stream, x_out, fx, status)`` -> rc.  -> (x_out, f_x, status), or None without a kernel."""
+    dev = target.device
+    if x_out is None:
+        x_out = torch.empty(target.shape, device=dev, dtype=torch.float32)
+    fx = torch.empty(info_shape, device=dev, dtype=torch.float32) if want_info else None
+    status = torch.empty(info_shape, device=dev, dtype=torch.int32) if want_info else None
+    ok = _inverse_call(
+        fn_name, spec, h, target, nb_steps, lambda *a: call(*a, _ptr(x_out), _ptr(fx), _ptr(status)),
+        "solve-host", "umnn_amd: no in-kernel Newton solve for this integrand / arithmetic mode ({}): the inverse runs the "
+        "host-driven Newton loop (one forward launch per iteration).")
+    return (x_out, fx, status) if ok else None
 
 
 def hip_solve(spec, h, target, nb_steps, j=0, scale_row=None, scaling=None, off_row=None, off_h0=False, lo=-50., hi=50., tol=1e-6,
@@ -369,31 +393,11 @@ def hip_solve(spec, h, target, nb_steps, j=0, scale_row=None, scaling=None, off_
     scale = ``scale_row`` [B], else exp(``scaling``[j]), else 1; off = ``off_row`` [B], else embedding row 0 (``off_h0``), else 0.
     Writes ``x_out``[:, j] ([B,d] fp32 contiguous; allocated when None) -> (x_out, f_x [B], status [B] int32), the last two None
     unless ``want_info``.  Returns None when the library has no kernel for this net: the caller runs ``host_solve``."""
-    lib = _lib.lib()
-    B, d = target.shape
-    E = h.shape[1] // d
-    if E * d != h.shape[1] or spec.linears[0].in_features != 1 + E:
-        raise RuntimeError("umnn_amd: embedding width does not match the integrand")
-    w, s = device_tables(nb_steps, target.device)
-    if x_out is None:
-        x_out = torch.empty(B, d, device=target.device, dtype=torch.float32)
-    fx = torch.empty(B, device=target.device, dtype=torch.float32) if want_info else None
-    status = torch.empty(B, device=target.device, dtype=torch.int32) if want_info else None
-    desc, keep = _desc(spec)
-    with torch.cuda.device(target.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(target.device).cuda_stream)
-        rc = lib.umnn_cc_solve(ctypes.byref(desc), _ptr(h), _ptr(target), d, _ptr(scale_row), _ptr(scaling), _ptr(off_row),
-                               1 if off_h0 else 0, _ptr(w), _ptr(s), int(nb_steps), B, d, E, int(j), float(lo), float(hi),
-                               float(tol), int(max_iter), _ptr(x_out), d, _ptr(fx), _ptr(status), stream)
-    if rc == _lib.EUNSUPPORTED:
-        _warn_once(("solve-host", tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
-                   "umnn_amd: no in-kernel Newton solve for this integrand / arithmetic mode "
-                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): the inverse runs the host-driven Newton loop "
-                   "(one forward launch per iteration).")
-        return None
-    _lib.check(rc, "umnn_cc_solve")
-    _state.path = "hip"
-    return x_out, fx, status
+    return _solve_call(
+        "umnn_cc_solve", spec, h, target, nb_steps, x_out, want_info, target.shape[:1],
+        lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve(
+            desc, _ptr(h), _ptr(target), d, _ptr(scale_row), _ptr(scaling), _ptr(off_row), 1 if off_h0 else 0, w, s, int(nb_steps),
+            B, d, E, int(j), float(lo), float(hi), float(tol), int(max_iter), x, d, fx, status, stream))
 
 
 def hip_solve_block(spec, h, target, nb_steps, scaling=None, off_h0=False, x_init=None, lo=-50., hi=50., tol=1e-6, max_iter=64,
@@ -403,31 +407,11 @@ def hip_solve_block(spec, h, target, nb_steps, scaling=None, off_h0=False, x_ini
     [B,E*d] fp32 contiguous; ``x_init`` [B,d] fp32 contiguous or None: the first iterate of every row (clamped into [lo, hi]; a
     non-finite entry starts that row at 0; may be ``x_out`` itself).  -> (x [B,d], f_x [B,d], status [B,d] int32), the last two None
     unless ``want_info``.  Returns None when the library has no kernel for this net: the caller runs ``host_solve``."""
-    lib = _lib.lib()
-    B, d = target.shape
-    E = h.shape[1] // d
-    if E * d != h.shape[1] or spec.linears[0].in_features != 1 + E:
-        raise RuntimeError("umnn_amd: embedding width does not match the integrand")
-    w, s = device_tables(nb_steps, target.device)
-    if x_out is None:
-        x_out = torch.empty(B, d, device=target.device, dtype=torch.float32)
-    fx = torch.empty(B, d, device=target.device, dtype=torch.float32) if want_info else None
-    status = torch.empty(B, d, device=target.device, dtype=torch.int32) if want_info else None
-    desc, keep = _desc(spec)
-    with torch.cuda.device(target.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(target.device).cuda_stream)
-        rc = lib.umnn_cc_solve_block(ctypes.byref(desc), _ptr(h), _ptr(target), _ptr(scaling), 1 if off_h0 else 0, _ptr(x_init),
-                                     _ptr(w), _ptr(s), int(nb_steps), B, d, E, float(lo), float(hi), float(tol), int(max_iter),
-                                     _ptr(x_out), _ptr(fx), _ptr(status), stream)
-    if rc == _lib.EUNSUPPORTED:
-        _warn_once(("solve-host", tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
-                   "umnn_amd: no in-kernel Newton solve for this integrand / arithmetic mode "
-                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): the inverse runs the host-driven Newton loop "
-                   "(one forward launch per iteration).")
-        return None
-    _lib.check(rc, "umnn_cc_solve_block")
-    _state.path = "hip"
-    return x_out, fx, status
+    return _solve_call(
+        "umnn_cc_solve_block", spec, h, target, nb_steps, x_out, want_info, target.shape,
+        lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve_block(
+            desc, _ptr(h), _ptr(target), _ptr(scaling), 1 if off_h0 else 0, _ptr(x_init), w, s, int(nb_steps), B, d, E,
+            float(lo), float(hi), float(tol), int(max_iter), x, fx, status, stream))
 
 
 def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=None):
