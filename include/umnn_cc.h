@@ -252,6 +252,13 @@ int umnn_flow_block_cotangents(const float* g_z, const float* g_log_jac, const f
                                long long B, int d, int reverse_z, float* gF, float* g_fx, void* stream);
 int umnn_flow_ll_forward(const float* z, const float* log_jac, long long B, int d, float* ll, void* stream);
 int umnn_flow_ll_backward(const float* z, const float* g_ll, long long B, int d, float* g_z, float* g_log_jac, void* stream);
+/* One adjoint Jacobi sweep's elementwise step (the gradient through a sample x = T^-1(z), umnn_amd/inverse.py): with J = dT/dx lower
+ * triangular and D = exp(log_jac) its diagonal, J^T lam = g is iterated as lam <- lam + (g - r) / D, r = J^T lam the block's VJP.
+ *     lam_out[q] = lam[q] + (g[q] - r[q]) exp(-log_jac[q])      over the B d entries, all [B,d] fp32; lam_out may be lam.
+ * flags[0] (zeroed by the caller) gets bit 0 ORed in when some entry has |g - r| > tol max(1, |g|) and bit 1 when some g - r is not
+ * finite; a non-finite entry never sets bit 0.  tol >= 0.  B = 0: no launch. */
+int umnn_flow_adjoint_update(const float* g, const float* r, const float* log_jac, const float* lam, long long B, int d, float tol,
+                             float* lam_out, unsigned* flags, void* stream);
 
 /* Replaces compute_cc_weights -- ParallelNeuralIntegral.py:14-34: writes nb_steps+1 fp32
  * weights and nodes into HOST buffers (float64 arithmetic, cast at the end). */

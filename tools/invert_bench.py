@@ -10,7 +10,13 @@ of the g5 fixtures.  The jacobi rows carry the sweep count and the largest evalu
 
 Device-synchronised wall time of whole calls (conditioner passes included), ``--warmup`` untimed calls of every method first, then
 ``--repeats`` rounds that alternate the methods, so drift hits both alike; every figure comes with its min / max / standard
-deviation.  ``--root`` imports the package from another checkout (a tree without the Newton method -- the parent of this change --
+deviation.  ``--grad`` times the gradient through a sample instead (the same block shapes): ``rsample`` and the backward of
+``x.square().sum()`` with the default stop rule (row ``rsample_backward``: the sweep counts of that backward), the same backward at
+two fixed sweep counts (``adj_tol=0``, ``max_adj_sweeps`` 2 and 6: their difference over 4 is the time of ONE sweep, printed as
+``ms_per_sweep``), and one training backward of the block (``-compute_ll(x).mean()``, parameters and x requiring grad) to hold a sweep
+against -- the one row a tree without ``inverse`` (``--root``) also gives; ``--methods`` selects rows by name there (a kernel trace
+of the sweeps alone: ``--grad --methods rsample_backward_6_sweeps --repeats 1 --warmup 0``: seven launches of the main backward
+kernel, one parameter reduction).  ``--root`` imports the package from another checkout (a tree without the Newton method -- the parent of this change --
 times the bracket search only), which is how the same-box comparison against an older build is taken.  Per-launch kernel time is
 a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/invert_bench.py --repeats 1 --only c3
 """
@@ -30,8 +36,10 @@ def main():
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--out", default=None)
     ap.add_argument("--only", default="c3,mnist,c3_made3,mnist_made3,monotonic")
-    ap.add_argument("--methods", default="bracket,newton,jacobi")
+    ap.add_argument("--methods", default=ap_default_methods)
     ap.add_argument("--label", default="")
+    ap.add_argument("--adj-tol", type=float, default=None, help="--grad: adj_tol of the rsample_backward row (default: the method's own)")
+    ap.add_argument("--grad", action="store_true", help="time rsample + backward and the adjoint sweeps instead of the solves")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
@@ -75,6 +83,9 @@ def main():
     results = []
     shapes = {"c3": dict(d=63, hd=[50] * 4, he=[512, 512], E=30, n=100, B=8192),
               "mnist": dict(d=784, hd=[100, 50, 50, 50, 50], he=[1024] * 3, E=30, n=100, B=100)}
+    if args.grad:
+        results += grad_mode(args, umnn_amd, torch, dev, shapes, only, measure)
+        only = set()
     with torch.no_grad():
         for case, c in [(name + tag, dict(c, made_gain=gain)) for name, c in shapes.items() for tag, gain in (("", 1.), ("_made3", 3.))]:
             if case not in only:
@@ -132,6 +143,92 @@ def main():
         with open(args.out, "w") as f:
             json.dump(dict(device=torch.cuda.get_device_name(0), precision=umnn_amd.get_forward_precision(), label=args.label,
                            has_newton=has_newton, results=results), f, indent=1)
+
+
+ap_default_methods = "bracket,newton,jacobi"
+
+
+def grad_mode(args, umnn_amd, torch, dev, shapes, only, measure):
+    """The ``--grad`` rows of every block shape in ``only``."""
+    results = []
+    has_inverse = hasattr(umnn_amd.UMNNMAFFlow, "rsample")
+    for case, c in [(name + tag, dict(c, made_gain=gain)) for name, c in shapes.items() for tag, gain in (("", 1.), ("_made3", 3.))]:
+        if case not in only:
+            continue
+        torch.manual_seed(0)
+        flow = umnn_amd.UMNNMAFFlow(nb_flow=1, nb_in=c["d"], hidden_derivative=c["hd"], hidden_embedding=c["he"],
+                                    embedding_s=c["E"], nb_steps=c["n"], solver="CCParallel").to(dev)
+        if c["made_gain"] != 1.:
+            with torch.no_grad():
+                for mod in flow.nets[0].net.made.net:
+                    if hasattr(mod, "weight"):
+                        mod.weight.mul_(c["made_gain"])
+            umnn_amd.invalidate_caches(flow)
+        params = [p for p in flow.parameters() if p.requires_grad]
+        state = {}
+
+        def timed_backward(make_loss):
+            """Forward untimed, then the backward alone between two device synchronisations (the row's ``backward_ms``)."""
+            loss = make_loss()
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            grads = torch.autograd.grad(loss, params, allow_unused=True)
+            torch.cuda.synchronize()
+            state.setdefault("bwd", []).append((time.perf_counter() - t0) * 1e3)
+            return grads
+
+        x_train = torch.randn(c["B"], c["d"], device=dev, requires_grad=True)
+
+        def train_backward():
+            return timed_backward(lambda: -flow.compute_ll(x_train)[0].mean())
+
+        def rsample_backward(**kw):
+            def make_loss():
+                x, state["info"] = flow.rsample(c["B"], generator=torch.Generator(device=dev).manual_seed(1), return_info=True, **kw)
+                return x.square().sum()
+            return timed_backward(make_loss)
+
+        fns = {"train_backward": train_backward}
+        if has_inverse:
+            fns["rsample_backward"] = (lambda: rsample_backward(adj_tol=args.adj_tol)) if args.adj_tol is not None else rsample_backward
+            fns["rsample_backward_2_sweeps"] = lambda: rsample_backward(adj_tol=0., max_adj_sweeps=2)
+            fns["rsample_backward_6_sweeps"] = lambda: rsample_backward(adj_tol=0., max_adj_sweeps=6)
+        if args.methods != ap_default_methods:        # (a kernel trace of one row: --methods rsample_backward_6_sweeps --repeats 1 --warmup 0)
+            fns = {k: fn for k, fn in fns.items() if k in args.methods.split(",")}
+        bwd = {}
+
+        def extra(k, outs):
+            # (measure() calls this once per method after the rounds, in order: hand every method its own backward timings)
+            if not bwd:
+                per, n = state["bwd"][args.warmup * len(fns):], len(fns)
+                for i, name in enumerate(fns):
+                    bwd[name] = per[i::n]
+            v = bwd[k]
+            out = dict(backward_ms=statistics.mean(v), backward_min_ms=min(v), backward_max_ms=max(v), backward_std_ms=statistics.pstdev(v))
+            if k == "rsample_backward":
+                out.update(adjoint=state_default.get("adjoint"), adj_tol=args.adj_tol)
+            return out
+
+        state_default = {}
+        if "rsample_backward" in fns:                 # the default stop rule's sweep counts (one untimed call)
+            x, info = flow.rsample(c["B"], generator=torch.Generator(device=dev).manual_seed(1), return_info=True,
+                                   **({} if args.adj_tol is None else {"adj_tol": args.adj_tol}))
+            torch.autograd.grad(x.square().sum(), params, allow_unused=True)
+            state_default["adjoint"] = info["adjoint"]
+        rows = measure(case, fns, extra)
+        if "rsample_backward_2_sweeps" in fns and "rsample_backward_6_sweeps" in fns and "train_backward" in fns:
+            per_sweep = (bwd["rsample_backward_6_sweeps"][i] - bwd["rsample_backward_2_sweeps"][i] for i in range(args.repeats))
+            per_sweep = [v / 4. for v in per_sweep]
+            row = dict(case=case, method="ms_per_sweep", label=args.label, mean_ms=statistics.mean(per_sweep), min_ms=min(per_sweep),
+                       max_ms=max(per_sweep), std_ms=statistics.pstdev(per_sweep), repeats=len(per_sweep),
+                       train_backward_ms=statistics.mean(bwd["train_backward"]),
+                       sweep_over_train_backward=statistics.mean(per_sweep) / statistics.mean(bwd["train_backward"]))
+            print(json.dumps(row), flush=True)
+            rows.append(row)
+        results += rows
+        del flow, params, x_train
+        torch.cuda.empty_cache()
+    return results
 
 
 if __name__ == "__main__":

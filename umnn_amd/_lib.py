@@ -106,6 +106,7 @@ SIGNATURES = {
     "umnn_flow_block_cotangents": (ctypes.c_int, [_fp, _fp, _fp, _fp, _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp]),
     "umnn_flow_ll_forward": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp]),
     "umnn_flow_ll_backward": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp, _fp]),
+    "umnn_flow_adjoint_update": (ctypes.c_int, [_fp, _fp, _fp, _fp, _ll, ctypes.c_int, ctypes.c_float, _fp, _fp, _fp]),
     "umnn_made_split3": (ctypes.c_int, [_fp, _ll, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, _fp]),
     "umnn_made_launch_count": (ctypes.c_longlong, []),
     "umnn_made_relu_bwd_bias_row_blocks": (ctypes.c_int, [_ll, ctypes.c_int]),

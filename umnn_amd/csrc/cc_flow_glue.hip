@@ -5,6 +5,8 @@
 //                                (UMNNMAF.py:80-83,134,138-139): cotangents of F and f_x from those of z and log_jac
 //   umnn_flow_ll_forward         ll = sum_i log_jac - 1/2 sum_i (log 2 pi + z_i^2)                  (UMNNMAFFlow.py:109-119)
 //   umnn_flow_ll_backward        its backward: g_log_jac = g_ll, g_z = -z g_ll
+// and of the adjoint Jacobi sweeps behind a differentiable sample (inverse.py FlowBlockInverse.backward):
+//   umnn_flow_adjoint_update     lam <- lam + (g - J^T lam) / D,  D = exp(log_jac), and the convergence / non-finite bits of g - J^T lam
 #include "cc_host.h"
 
 __global__ __launch_bounds__(256) void flow_block_cotangents_kernel(const float* __restrict__ g_z, const float* __restrict__ g_lj,
@@ -71,4 +73,38 @@ extern "C" int umnn_flow_ll_backward(const float* z, const float* g_ll, long lon
     hipLaunchKernelGGL(flow_ll_backward_kernel, dim3((unsigned)((NI + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z, g_ll, NI, d, g_z,
                        g_log_jac);
     return umnn_check(hipGetLastError(), "flow_ll_backward launch");
+}
+
+// lam and lam_out may be the same buffer (each thread reads its own entry before it writes it): no __restrict__ on them
+__global__ __launch_bounds__(256) void flow_adjoint_update_kernel(const float* __restrict__ g, const float* __restrict__ r,
+                                                                  const float* __restrict__ log_jac, const float* lam, long long NI,
+                                                                  float tol, float* lam_out, unsigned* __restrict__ flags) {
+    const long long q = (long long)blockIdx.x * 256 + threadIdx.x;
+    unsigned bits = 0;
+    if (q < NI) {
+        const float gq = g[q];
+        const float res = gq - r[q];
+        lam_out[q] = lam[q] + res * expf(-log_jac[q]);
+        // (a non-finite residual is reported, and never counts as "not converged yet": a NaN row cannot keep the sweeps going)
+        bits = !isfinite(res) ? 2u : (fabsf(res) > tol * fmaxf(1.f, fabsf(gq)) ? 1u : 0u);
+    }
+    const bool over = __ballot(bits & 1u) != 0, bad = __ballot(bits & 2u) != 0;       // every lane arrives here: no early return above
+    if ((threadIdx.x & 63) == 0 && (over || bad)) {
+        // one vector atomic per wave with something to report, and only while the word lacks its bits: in the early sweeps every wave
+        // is over tol, and 8000 atomics on one address cost 90 us where the pass itself takes 5 (a stale read only repeats an OR)
+        const unsigned w = (over ? 1u : 0u) | (bad ? 2u : 0u);
+        if ((__atomic_load_n(flags, __ATOMIC_RELAXED) & w) != w) atomicOr(flags, w);
+    }
+}
+
+extern "C" int umnn_flow_adjoint_update(const float* g, const float* r, const float* log_jac, const float* lam, long long B, int d,
+                                        float tol, float* lam_out, unsigned* flags, void* stream) {
+    if (B < 0 || d < 1 || !(tol >= 0.f)) return umnn_fail(UMNN_EINVAL, "flow adjoint update: B >= 0, d >= 1, tol >= 0");
+    if (B == 0) return 0;
+    if (!g || !r || !log_jac || !lam || !lam_out || !flags) return umnn_fail(UMNN_EINVAL, "flow adjoint update: null pointer");
+    const long long NI = B * (long long)d;
+    if ((NI + 255) / 256 > 0x7fffffffLL) return umnn_fail(UMNN_EINVAL, "flow adjoint update: B d too large for one launch");
+    hipLaunchKernelGGL(flow_adjoint_update_kernel, dim3((unsigned)((NI + 255) / 256)), dim3(256), 0, (hipStream_t)stream, g, r, log_jac,
+                       lam, NI, tol, lam_out, flags);
+    return umnn_check(hipGetLastError(), "flow_adjoint_update launch");
 }

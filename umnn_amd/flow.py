@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 
 from . import integral as _I
+from . import inverse as _inv
 from . import ops as _ops
 from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, IntegralWithJacobianParams, _flatten  # noqa: F401
 from .made import MADE, ConditionnalMADE
@@ -393,6 +394,27 @@ class UMNNMAF(nn.Module):
                     "max_evals": [int(e) for e in torch.stack(evals).tolist()]}
         return x, info
 
+    def inverse(self, z, context=None, method="newton", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, adj_tol=1e-6,
+                max_adj_sweeps=None, return_info=False):
+        """x with ``self(x) = z``, DIFFERENTIABLE in z, the block's parameters and the context (``invert`` runs under no_grad): the
+        solve of ``invert(method="newton" | "jacobi")`` -- ``tol``, ``max_iter``, ``sweep_tol``, ``max_sweeps`` are its arguments;
+        ``"bracket"`` is refused -- as one autograd node, ``inverse.FlowBlockInverse``, whose backward is the implicit gradient: J^T lam =
+        g_x by adjoint Jacobi sweeps (one block VJP without parameter gradients and one elementwise launch each), then g_z = lam and one
+        more VJP with -lam for the parameters and the context.  The sweeps stop when every |g_x - J^T lam| <= ``adj_tol`` max(1, |g_x|)
+        (one 4-byte device-to-host read per sweep; ``adj_tol`` = 0: no test, no read) and in any case after ``max_adj_sweeps`` (default d,
+        where lam is exact: J is triangular).  ``return_info=True`` -> (x, info): info["solve"] holds the Jacobi solve's info per block
+        (None for newton), info["adjoint"] is filled by the backward with {"sweeps", "vjps", "flags"} per block ("sweeps": the updates
+        lam needed -- the first k whose lam^k met the test, or the cap; "vjps": the block VJPs run, one more when the test ended the
+        loop; "flags": the last flag word read -- bit 0 not converged, bit 1 a non-finite residual -- or None with ``adj_tol`` = 0).
+        In float32 the VJP's own rounding (a few 1e-6 of max(1, |g_x|) once the dimensions are strongly coupled) can sit above the default
+        ``adj_tol``: the sweeps then run to the cap -- the exact answer, at d block backwards; ``adj_tol=1e-5`` stops such blocks after
+        the 5-7 sweeps the iteration needs (EXPERIMENTS.md).
+        The Jacobian is this package's own (dF/dx = f(x), the Leibniz term), so a finite difference of ``invert`` differs by the
+        quadrature error of f.  Entries whose solve ended SOLVE_CLAMPED or SOLVE_NONFINITE are not solutions of T(x) = z and have no
+        defined gradient; the rows of a batch are independent, so every other sample is unaffected.  Eager only, like ``invert``."""
+        return _inv.inverse([self], False, "UMNNMAF.inverse", z, context, method, tol, max_iter, sweep_tol, max_sweeps, adj_tol,
+                            max_adj_sweeps, return_info)
+
     def _invert(self, z, iter=10, context=None):
         K = 10
         B, d = z.shape
@@ -556,6 +578,35 @@ class UMNNMAFFlow(nn.Module):
             z, infos[i] = self.nets[i]._invert_jacobi(torch.flip(z, [1]), context, tol, max_iter, sweep_tol, max_sweeps, want_info)
         info = {k: [inf[k] for inf in infos] for k in ("sweeps", "converged", "status", "max_evals")} if want_info else None
         return z, info
+
+    def inverse(self, z, context=None, method="newton", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, adj_tol=1e-6,
+                max_adj_sweeps=None, return_info=False):
+        """The sampling direction with gradients to z, every parameter and the context: ``UMNNMAF.inverse`` block by block, walking
+        the blocks and flipping as ``invert(method="newton")`` does (the flips are ordinary differentiable ops).  ``return_info=True``
+        -> (x, info) with info["solve"] / info["adjoint"] as lists over the blocks in flow order; the backward fills info["adjoint"]."""
+        return _inv.inverse(self.nets, True, "UMNNMAFFlow.inverse", z, context, method, tol, max_iter, sweep_tol, max_sweeps, adj_tol,
+                            max_adj_sweeps, return_info)
+
+    def _base_noise(self, n, generator=None):
+        """z ~ N(0, I), [n, d] on the model's device (drawn on the generator's own device when one is given)."""
+        blk = self.nets[0]
+        dev = self.pi.device
+        z = torch.randn(int(n), blk.input_size, generator=generator, dtype=blk.scaling.dtype,
+                        device=dev if generator is None else generator.device)
+        return z.to(dev)
+
+    def sample(self, n, context=None, generator=None, **solve_opts):
+        """n samples x = T^-1(z), z ~ N(0, I), without a graph: ``invert`` (method "newton" unless ``solve_opts`` says otherwise)."""
+        solve_opts.setdefault("method", "newton")
+        with torch.no_grad():
+            return self.invert(self._base_noise(n, generator), context=context, **solve_opts)
+
+    def rsample(self, n, context=None, generator=None, **opts):
+        """n reparameterised samples: ``inverse`` of z ~ N(0, I), differentiable in the parameters and the context."""
+        return self.inverse(self._base_noise(n, generator), context=context, **opts)
+
+    def log_prob(self, x, context=None):
+        return self.compute_ll(x, context)[0]
 
     def _invert(self, z, iter=10, context=None):
         z = torch.flip(z, [1])

@@ -764,6 +764,29 @@ def hip_flow_block_cotangents(gz, glj, fx, scaling, reverse_z):
     return gF, gfx
 
 
+def flow_adjoint_update(g, r, log_jac, lam, tol, flags, out=None):
+    """One adjoint Jacobi step: out = lam + (g - r) exp(-log_jac), all [B,d]; ``out`` may be ``lam`` itself (allocated when None).
+    ``flags`` (int32 [1], zeroed by the caller) gets bit 0 when some |g - r| > tol max(1, |g|) and bit 1 when some g - r is not finite
+    (such an entry never sets bit 0).  One launch of umnn_flow_adjoint_update for contiguous fp32 GPU tensors; the same arithmetic in
+    torch ops for host tensors and other dtypes.  -> out"""
+    if out is None:
+        out = torch.empty_like(lam)
+    if lam.is_cuda and all(t.dtype == torch.float32 and t.is_contiguous() for t in (g, r, log_jac, lam, out)) \
+            and not getattr(_state, "force_generic", False):
+        B, d = lam.shape
+        with torch.cuda.device(lam.device):
+            rc = _lib.lib().umnn_flow_adjoint_update(_ptr(g), _ptr(r), _ptr(log_jac), _ptr(lam), B, d, float(tol), _ptr(out), _ptr(flags),
+                                                     _stream(lam.device))
+        _lib.check(rc, "umnn_flow_adjoint_update")
+        return out
+    res = g - r
+    bad = ~torch.isfinite(res)
+    over = (res.abs() > tol * g.abs().clamp(min=1.)) & ~bad
+    flags |= over.any().to(flags.dtype) + 2 * bad.any().to(flags.dtype)
+    torch.add(lam, res * torch.exp(-log_jac), out=out)
+    return out
+
+
 def hip_flow_ll(z, log_jac):
     """ll [B] fp32 of a flow from its z and summed log_jac (umnn_flow_ll_forward)."""
     z, log_jac = z.contiguous(), log_jac.contiguous()
