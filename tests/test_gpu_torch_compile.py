@@ -224,8 +224,8 @@ def test_training_step_compiles(shape, B):
 
 def test_training_step_compiles_with_the_aten_backward():
     """A deep wide integrand (five unequal hidden layers above 63 units, as in test_gpu_round3.py): the HIP backward has no
-    shape-exact kernel, so cc_backward runs the ATen backward of ops.py inside the compiled graph, against eager's
-    integral.aten_backward_jac."""
+    shape-exact kernel, so cc_backward runs the ATen backward (integral.aten_vjp on the ops' W[] / b[]) inside the compiled
+    graph, against eager's, on the module."""
     flow = _flow(d=3, nb_flow=2, hidden=[100, 72, 80, 96, 70], E=4, n=10)
     x = torch.randn(32, 3, device=DEV) * 0.5
     with warnings.catch_warnings():

@@ -11,6 +11,7 @@ from torch.fx.experimental.symbolic_shapes import DimDynamic, ShapeEnv, Stateles
 import umnn_amd
 from umnn_amd import integral, made, ops
 from umnn_amd.nets import IntegrandNetwork
+from umnn_amd.quadrature import device_tables
 
 SCHEMA_ARGS = {
     "cc_forward": ["x0", "x", "h", "W", "b", "hidden_act", "out_act", "nb_steps", "inv_f"],
@@ -173,22 +174,60 @@ def test_import_loads_no_library():
     assert out.returncode == 0 and out.stdout.strip().endswith("ok"), out.stderr
 
 
-@pytest.mark.parametrize("hidden,act", [([12, 12], "ELU"), ([10, 20, 10], "Sigmoid")])
-@pytest.mark.parametrize("with_gfx", [False, True])
-def test_op_aten_backward_matches_the_module_chain(hidden, act, with_gfx):
-    """The ATen backward cc_backward runs for nets the HIP backward turns away, against integral.py's own ATen chain."""
+def _dense_float64_truth(net, x0, x, h, g, gfx, n, inv_f):
+    """(dx0, dx, dh, dtheta) of the quadrature from a construction that shares nothing with the implementation: the un-chunked sum
+    over all n + 1 nodes of the package's own tables (``device_tables``, widened to float64) as one scalar, differentiated by plain
+    ``torch.autograd.grad``; the g_fx term by autograd through f(x; h); the Leibniz terms f(x) g and -f(x0) g."""
+    w, s = device_tables(n, x.device)
+    w, u = w.double().view(-1), s.double().view(-1) + 1
+    hr, xr = h.clone().requires_grad_(True), x.clone().requires_grad_(True)
+    params = list(net.parameters())
+    total = 0
+    for k in range(n + 1):
+        f = net(x0 + (x - x0) * u[k] / 2, hr)
+        total = total + w[k] * (1 / f if inv_f else f)
+    loss = (total * (x - x0) / 2 * g).sum()
+    fx = net(xr, hr)
+    if gfx is not None:
+        loss = loss + (fx * gfx).sum()
+    grads = torch.autograd.grad(loss, [hr, xr] + params, allow_unused=True)
+    dx = fx.detach() * g + (grads[1] if grads[1] is not None else 0)
+    return -net(x0, h).detach() * g, dx, grads[0], torch.cat([p.reshape(-1) for p in grads[2:]])
+
+
+def _check_aten_backward(hidden, act, with_gfx, inv_f):
     torch.manual_seed(0)
     B, d, E, n = 9, 3, 4, 12
     net = IntegrandNetwork(d, 1 + E, hidden, 1, act_func=act).double()
     x0, x = torch.randn(B, d, dtype=torch.float64), torch.randn(B, d, dtype=torch.float64)
     h, g = torch.randn(B, E * d, dtype=torch.float64), torch.randn(B, d, dtype=torch.float64)
     gfx = torch.randn(B, d, dtype=torch.float64) if with_gfx else None
-    want = integral.aten_backward_jac(net, x0, x, h, g, gfx, n)
+    want = _dense_float64_truth(net, x0, x, h, g, gfx, n, inv_f)
     lins = [m for m in net.net if isinstance(m, torch.nn.Linear)]
-    got = ops.aten_backward([l.weight for l in lins], [l.bias for l in lins], 0, 0 if act == "ELU" else 1, x0, x, h, g, gfx, n,
-                            False)
-    for a, w in zip(got, want):
-        torch.testing.assert_close(a, w.view(a.shape), rtol=1e-10, atol=1e-12)
+    tensors = ops.pure_mlp([l.weight for l in lins], [l.bias for l in lins], 0, 0 if act == "ELU" else 1)
+    for adapter, integrand in (("module", net), ("W[] / b[]", tensors)):
+        got = integral.aten_vjp(integrand, x0, x, h, g, gfx, n, inv_f)
+        for name, a, w in zip(("dx0", "dx", "dh", "dtheta"), got, want):
+            torch.testing.assert_close(a, w.view(a.shape), rtol=1e-10, atol=1e-12, msg=lambda m: f"{adapter} adapter, {name}: {m}")
+    if not with_gfx:        # (the reference-shaped return of integrate(compute_grad=True))
+        dtheta, dh = integral.aten_backward(net, x0, x, h, g, n, inv_f)
+        torch.testing.assert_close(dtheta, want[3], rtol=1e-10, atol=1e-12)
+        torch.testing.assert_close(dh, want[2], rtol=1e-10, atol=1e-12)
+
+
+@pytest.mark.parametrize("hidden,act", [([12, 12], "ELU"), ([10, 20, 10], "Sigmoid")])
+@pytest.mark.parametrize("with_gfx", [False, True])
+def test_op_aten_backward_matches_the_module_chain(hidden, act, with_gfx):
+    """The one ATen quadrature backward (``integral.aten_vjp``: what cc_backward runs for nets the HIP backward turns away, and
+    what the eager operators run off the GPU) through both of its adapters -- the module and the ops' W[] / b[] -- against the
+    dense float64 quadrature differentiated by plain autograd."""
+    _check_aten_backward(hidden, act, with_gfx, False)
+
+
+@pytest.mark.parametrize("hidden,act", [([12, 12], "ELU"), ([10, 20, 10], "Sigmoid")])
+def test_aten_backward_of_an_inverse_integrand_matches_dense_float64(hidden, act):
+    """The same for ``inv_f`` (the integral of 1/f; no operator with an f_x output has it, so no g_fx)."""
+    _check_aten_backward(hidden, act, False, True)
 
 
 def test_native_pointers_refuse_jit_trace():

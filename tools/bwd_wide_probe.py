@@ -21,7 +21,7 @@ for (B, d, E, hid, n) in ((256, 6, 10, [110] * 4, 50), (2048, 6, 10, [110] * 4, 
     print(hid, "B", B, "hip_backward_ok:", I._hip_backward_ok(spec, x, h), flush=True)
     res = {}
     for name, fn in (("hip (generic kernels)", lambda: I.hip_backward(spec, None, x, h, g, gf, n)),
-                     ("aten chain", lambda: I.aten_backward_jac(net, torch.zeros_like(x), x, h, g, gf, n))):
+                     ("aten chain", lambda: I.aten_vjp(net, torch.zeros_like(x), x, h, g, gf, n))):
         try:
             out = fn()
             torch.cuda.synchronize()

@@ -22,7 +22,6 @@ import torch.nn as nn
 
 from . import integral as _I
 from . import inverse as _inv
-from . import ops as _ops
 from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, IntegralWithJacobianParams, _flatten  # noqa: F401
 from .made import MADE, ConditionnalMADE
 from .nets import ELUPlus, IntegrandNetwork, compute_lipschitz_linear, mlp_spec  # noqa: F401  (re-exported)
@@ -68,6 +67,25 @@ class EmbeddingNetwork(nn.Module):
         return self.parallel_nets.forward(x_t, self.m_embeding)
 
 
+def _invert_dispatch(cls, flow, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info):
+    """``cls.invert`` of UMNNMAF and UMNNMAFFlow: checks the options and runs ``cls._invert`` / ``_invert_newton`` / ``_invert_jacobi``.
+    Eager only: compiled callers get an eager call, torch.jit.trace raises."""
+    if method not in ("bracket", "newton", "jacobi"):
+        raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
+    if torch.jit.is_tracing():
+        raise RuntimeError(f"umnn_amd: {cls.__name__}.invert cannot be traced by torch.jit.trace (data-dependent bracket search); "
+                           "call it eagerly")
+    if return_info and method != "jacobi":
+        raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
+    fn, args = {"bracket": (cls._invert, (z, iter, context)), "newton": (cls._invert_newton, (z, context, tol, max_iter)),
+                "jacobi": (cls._invert_jacobi, (z, context, tol, max_iter, sweep_tol, max_sweeps, return_info))}[method]
+    if torch.compiler.is_compiling():
+        # (applied here, not as a decorator: torch.compiler.disable imports torch._dynamo, ~1 s at every package import)
+        fn = torch.compiler.disable(fn)
+    out = fn(flow, *args)
+    return out[0] if method == "jacobi" and not return_info else out
+
+
 class UMNNMAF(nn.Module):
     def __init__(self, net, input_size, nb_steps=100, device="cpu", solver="CC"):
         super().__init__()
@@ -107,11 +125,7 @@ class UMNNMAF(nn.Module):
         h = self.net.make_embeding(x, context)
         d = x.shape[1]
         z0 = h.view(h.shape[0], -1, d)[:, 0, :]
-        if _I._graph_mode():
-            gspec = _I._graph_spec(integrand, x)
-            if gspec is not None:                   # (anything else: the generic path below)
-                return self._transform_graph(x, h, z0, gspec, x0, want_jac, reverse_z, log_jac_in)
-        spec = mlp_spec(integrand)
+        spec = _I._hip_spec(integrand, x)       # (eager and recorded alike; the calls below launch, or record the op of the launch)
         if self.nb_steps < 1:
             raise ValueError("UMNNMAF: nb_steps must be >= 1 when integrating (call set_steps_nb first)")
         # No-graph fast path only when nothing can ask for a gradient.  The reference's eval-mode direct integration
@@ -120,19 +134,14 @@ class UMNNMAF(nn.Module):
         no_graph = (not torch.is_grad_enabled()) or not (
             x.requires_grad or h.requires_grad or (x0 is not None and x0.requires_grad)
             or any(p.requires_grad for p in integrand.parameters()))
-        if _I._use_hip(spec, x):
-            if no_graph and x0 is None:
-                z, log_jac, _, _ = _I.hip_flow_block(spec, x, h, self.scaling, self.nb_steps, reverse_z, log_jac_in)
-                return z, log_jac
+        if spec is not None:
+            # training: the whole block -- quadrature + epilogue, and their backward -- as ONE autograd node
+            one_node = (not no_graph and _I.fused_block_ok(x, h, self.scaling, x0, want_jac)
+                        and (log_jac_in is None or log_jac_in.dtype == torch.float32))
+            if one_node or (no_graph and x0 is None):
+                return _I.flow_block(spec, integrand, x, h, self.scaling, self.nb_steps, reverse_z, log_jac_in, train=one_node)
             x0 = x0.to(x.device) if x0 is not None else None      # None = lower limit 0 inside the kernels
-            if no_graph:
-                F, fx, _ = _I.hip_forward(spec, x0, x, h, self.nb_steps)
-            elif _I.fused_block_ok(x, h, self.scaling, x0, want_jac) and (log_jac_in is None or log_jac_in.dtype == torch.float32):
-                # training: the whole block -- quadrature + epilogue, and their backward -- as ONE autograd node
-                return _I.FlowBlockTransform.apply(x.contiguous(), integrand, h.contiguous(), self.scaling, self.nb_steps,
-                                                   reverse_z, log_jac_in, *integrand.parameters())
-            else:
-                F, fx = IntegralWithJacobianParams.apply(x0, x, integrand, h, self.nb_steps, *integrand.parameters())
+            F, fx = _I.cc_forward_jac(spec, integrand, x0, x, h, self.nb_steps, no_graph)
         else:
             x0 = x0.to(x.device) if x0 is not None else torch.zeros_like(x)
             if no_graph:
@@ -149,35 +158,6 @@ class UMNNMAF(nn.Module):
             log_jac = log_jac_in + log_jac
         return z, log_jac
 
-    def _transform_graph(self, x, h, z0, spec, x0, want_jac, reverse_z, log_jac_in):
-        """``_transform`` under torch.compile / export / jit.trace: the same choice of one-node, fused or composed block, with the
-        HIP launches as torch.ops.umnn ops.  No z_2 hand-off (the backward recomputes it: never a different result)."""
-        integrand = self.net.parallel_nets
-        if self.nb_steps < 1:
-            raise ValueError("UMNNMAF: nb_steps must be >= 1 when integrating (call set_steps_nb first)")
-        W, b, ha, oa = _ops.spec_args(spec)
-        no_graph = (not torch.is_grad_enabled()) or not (
-            x.requires_grad or h.requires_grad or (x0 is not None and x0.requires_grad)
-            or any(p.requires_grad for p in integrand.parameters()))
-        if no_graph and x0 is None:                 # (like eager's hip_flow_block call: no gradient for scaling on this path)
-            z, log_jac, _ = torch.ops.umnn.flow_block(x, h, self.scaling.detach(), W, b, ha, oa, self.nb_steps, reverse_z,
-                                                      log_jac_in)
-            return z, log_jac
-        x0 = x0.to(x.device) if x0 is not None else None
-        if (not no_graph and _I.fused_block_ok(x, h, self.scaling, x0, want_jac)
-                and (log_jac_in is None or log_jac_in.dtype == torch.float32)):
-            z, log_jac, _ = torch.ops.umnn.flow_block(x.contiguous(), h.contiguous(), self.scaling, W, b, ha, oa, self.nb_steps,
-                                                      reverse_z, log_jac_in)
-            return z, log_jac
-        F, fx = torch.ops.umnn.cc_forward(x0, x, h, W, b, ha, oa, self.nb_steps, False)
-        z = torch.exp(self.scaling).unsqueeze(0) * (F + z0)
-        log_jac = torch.log(fx + 1e-10) + self.scaling.unsqueeze(0) if want_jac else None
-        if reverse_z:
-            z = torch.flip(z, [1])
-        if log_jac_in is not None and log_jac is not None:
-            log_jac = log_jac_in + log_jac
-        return z, log_jac
-
     # ------------------------------------------------------------------ reference API
     def forward(self, x, method=None, x0=None, context=None):
         return self._transform(x, context, x0, want_jac=False)[0]
@@ -185,21 +165,13 @@ class UMNNMAF(nn.Module):
     def compute_log_jac(self, x, context=None):
         h = self.net.make_embeding(x, context)
         integrand = self.net.parallel_nets
-        gspec = _I._graph_spec(integrand, x) if _I._graph_mode() else None
-        spec = gspec if gspec is not None else mlp_spec(integrand)
-        if gspec is not None:
-            # graph mode: f(x;h) from a one-step umnn::cc_forward, differentiable through the op in every output
-            W, b, ha, oa = _ops.spec_args(gspec)
-            jac = torch.ops.umnn.cc_forward(None, x, h, W, b, ha, oa, 1, False)[1]
-        elif _I._use_hip(spec, x):
+        spec = _I._hip_spec(integrand, x)
+        if spec is not None:
             # f(x;h) is quadrature node 0: a one-step launch of the forward kernel evaluates it (two nodes) without the
             # [B*d, 1+E] row matrix the reference materialises (UMNNMAF.py:136-139, 263-284)
-            wants_graph = torch.is_grad_enabled() and (x.requires_grad or h.requires_grad
-                                                       or any(p.requires_grad for p in integrand.parameters()))
-            if wants_graph:
-                jac = IntegralWithJacobianParams.apply(None, x, integrand, h, 1, *integrand.parameters())[1]
-            else:
-                jac = _I.hip_forward(spec, None, x, h, 1)[1]
+            no_graph = not (torch.is_grad_enabled() and (x.requires_grad or h.requires_grad
+                                                         or any(p.requires_grad for p in integrand.parameters())))
+            jac = _I.cc_forward_jac(spec, integrand, None, x, h, 1, no_graph)[1]
         else:
             jac = integrand(x, h)
         return torch.log(jac + 1e-10) + self.scaling.unsqueeze(0).expand(x.shape[0], -1)
@@ -267,25 +239,36 @@ class UMNNMAF(nn.Module):
         conditioner pass and ONE solve of all d dimensions under that embedding (``umnn_cc_solve_block``), warm-started from the previous
         sweep; stops when no entry moved by more than ``sweep_tol * max(1, |x|)`` or after ``max_sweeps`` sweeps (default d, where the
         result is the sequential one by construction).  ``return_info=True`` (jacobi only) -> (x, info)."""
-        if method not in ("bracket", "newton", "jacobi"):
-            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
-        if torch.jit.is_tracing():
-            raise RuntimeError("umnn_amd: UMNNMAF.invert cannot be traced by torch.jit.trace (data-dependent bracket search); "
-                               "call it eagerly")
-        if method == "jacobi":
-            fn = torch.compiler.disable(UMNNMAF._invert_jacobi) if torch.compiler.is_compiling() else UMNNMAF._invert_jacobi
-            x, info = fn(self, z, context, tol, max_iter, sweep_tol, max_sweeps, return_info)
-            return (x, info) if return_info else x
-        if return_info:
-            raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
-        if method == "newton":
-            if torch.compiler.is_compiling():
-                return torch.compiler.disable(UMNNMAF._invert_newton)(self, z, context, tol, max_iter)
-            return self._invert_newton(z, context, tol, max_iter)
-        if torch.compiler.is_compiling():
-            # (applied here, not as a decorator: torch.compiler.disable imports torch._dynamo, ~1 s at every package import)
-            return torch.compiler.disable(UMNNMAF._invert)(self, z, iter, context)
-        return self._invert(z, iter, context)
+        return _invert_dispatch(UMNNMAF, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info)
+
+    def _dim_embedding(self, x_inv, context, rows_ok):
+        """The conditioner pass of the dimension-by-dimension sampling loops -> ``embed(j, widen)``: the embedding h [B, E*d] that
+        dimension j is solved under, from ``x_inv``'s current contents.  Dimension j reads E of the E*d embedding entries.  Wide
+        unconditional conditioners compute only those columns of their last layer (MADE.raw_rows: for d = 784 that layer is 23 520 rows
+        of which 30 are read) into a standing buffer, where ``rows_ok`` (the in-kernel path) and the conditioner allow it; otherwise a
+        full pass, with ``widen`` as contiguous fp32 -- exact for a bf16 embedding (set_embedding_dtype, autocast), which the fp32-only
+        entry points would misread."""
+        made = self.net.made
+        B, d = x_inv.shape
+        dev = x_inv.device
+        E = made.nout // made.nin
+        restrict = (rows_ok and context is None and not isinstance(made, ConditionnalMADE)
+                    and self.net.embedding_dtype in (None, torch.float32) and os.environ.get("UMNN_INVERT_ROWS", "1") != "0")
+        rows_all = (torch.arange(E, device=dev) * d).view(1, E) + torch.arange(d, device=dev).view(d, 1) if restrict else None
+        h_buf = None
+
+        def embed(j, widen):
+            nonlocal restrict, h_buf
+            hj = made.raw_rows(x_inv, rows_all[j]) if restrict else None
+            if hj is not None:
+                if h_buf is None:
+                    h_buf = torch.zeros(B, E * d, device=dev)
+                h_buf.view(B, E, d)[:, :, j] = hj
+                return h_buf
+            restrict = False
+            h = self.net.make_embeding(x_inv, context)
+            return h.float().contiguous() if widen else h
+        return embed
 
     def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
         """``invert(method="newton")``.  HIP path: d x (conditioner + ONE launch), the whole solve of a dimension inside the kernel,
@@ -300,25 +283,9 @@ class UMNNMAF(nn.Module):
             z = z.contiguous()
             x_inv = torch.zeros(B, d, device=dev, dtype=z.dtype)
             scaling = self.scaling.detach().float().contiguous()
-            made = self.net.made
-            E = made.nout // made.nin
-            # (the conditioner pass of one dimension: as in _invert -- only the E columns dimension j reads, where MADE.raw_rows applies)
-            restrict = (in_kernel and context is None and not isinstance(made, ConditionnalMADE)
-                        and self.net.embedding_dtype in (None, torch.float32) and os.environ.get("UMNN_INVERT_ROWS", "1") != "0")
-            rows_all = (torch.arange(E, device=dev) * d).view(1, E) + torch.arange(d, device=dev).view(d, 1) if restrict else None
-            h_buf = None
+            embed = self._dim_embedding(x_inv, context, in_kernel)
             for j in range(self.input_size):
-                hj = made.raw_rows(x_inv, rows_all[j]) if restrict else None
-                if hj is not None:
-                    if h_buf is None:
-                        h_buf = torch.zeros(B, E * d, device=dev)
-                    h_buf.view(B, E, d)[:, :, j] = hj
-                    h = h_buf
-                else:
-                    restrict = False
-                    h = self.net.make_embeding(x_inv, context)
-                    if in_kernel:
-                        h = h.float().contiguous()      # (umnn_cc_solve reads an fp32 embedding; widening bf16 is exact)
+                h = embed(j, in_kernel)             # (umnn_cc_solve reads an fp32 embedding)
                 if in_kernel:
                     if _I.hip_solve(spec, h, z, self.nb_steps, j=j, scaling=scaling, off_h0=True, lo=-50., hi=50., tol=tol,
                                     max_iter=max_iter, x_out=x_inv, want_info=False) is not None:
@@ -428,26 +395,9 @@ class UMNNMAF(nn.Module):
                 x_inv = torch.zeros(B, d, device=dev)
                 scaling = self.scaling.detach().float().contiguous()
                 done = True
-                # Dimension j reads E of the E*d embedding entries.  Wide unconditional conditioners compute only those columns of
-                # their last layer (MADE.raw_rows: for d = 784 that layer is 23 520 rows of which 30 are read) into a standing buffer
-                made = self.net.made
-                E = made.nout // made.nin
-                restrict = (context is None and not isinstance(made, ConditionnalMADE) and self.net.embedding_dtype in (None, torch.float32)
-                            and os.environ.get("UMNN_INVERT_ROWS", "1") != "0")
-                rows_all = (torch.arange(E, device=dev) * d).view(1, E) + torch.arange(d, device=dev).view(d, 1) if restrict else None
-                h_buf = None
+                embed = self._dim_embedding(x_inv, context, True)
                 for j in range(self.input_size):
-                    hj = made.raw_rows(x_inv, rows_all[j]) if restrict else None
-                    if hj is not None:
-                        if h_buf is None:
-                            h_buf = torch.zeros(B, E * d, device=dev)
-                        h_buf.view(B, E, d)[:, :, j] = hj
-                        h = h_buf
-                    else:
-                        restrict = False
-                        # umnn_flow_invert_dim reads an fp32 embedding (it has no umnn_io descriptor): a bf16 embedding
-                        # (set_embedding_dtype, autocast) is widened here -- exact -- instead of being misread as fp32
-                        h = self.net.make_embeding(x_inv, context).float().contiguous()
+                    h = embed(j, True)              # (umnn_flow_invert_dim reads an fp32 embedding: it has no umnn_io descriptor)
                     if not _I.hip_invert_dim(spec, h, z, scaling, self.nb_steps, j, iter, x_inv):
                         done = False
                         break
@@ -545,24 +495,7 @@ class UMNNMAFFlow(nn.Module):
         ``method="newton"``: the in-kernel Newton solve (``UMNNMAF.invert``), exactly nb_flow x d solve launches; ``iter`` is ignored.
         ``method="jacobi"``: the Jacobi iteration of ``UMNNMAF.invert`` in every block, one solve launch per sweep;
         ``return_info=True`` -> (x, info) with info's entries as lists over the blocks in flow order."""
-        if method not in ("bracket", "newton", "jacobi"):
-            raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
-        if torch.jit.is_tracing():
-            raise RuntimeError("umnn_amd: UMNNMAFFlow.invert cannot be traced by torch.jit.trace (data-dependent bracket "
-                               "search); call it eagerly")
-        if method == "jacobi":
-            fn = torch.compiler.disable(UMNNMAFFlow._invert_jacobi) if torch.compiler.is_compiling() else UMNNMAFFlow._invert_jacobi
-            x, info = fn(self, z, context, tol, max_iter, sweep_tol, max_sweeps, return_info)
-            return (x, info) if return_info else x
-        if return_info:
-            raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
-        if method == "newton":
-            if torch.compiler.is_compiling():
-                return torch.compiler.disable(UMNNMAFFlow._invert_newton)(self, z, context, tol, max_iter)
-            return self._invert_newton(z, context, tol, max_iter)
-        if torch.compiler.is_compiling():           # (an eager call inside compiled code; see UMNNMAF.invert)
-            return torch.compiler.disable(UMNNMAFFlow._invert)(self, z, iter, context)
-        return self._invert(z, iter, context)
+        return _invert_dispatch(UMNNMAFFlow, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info)
 
     def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
         z = torch.flip(z, [1])
@@ -620,68 +553,40 @@ class UMNNMAFFlow(nn.Module):
     def compute_log_jac_bis(self, x, context=None):
         return self._stack(x, context, True)
 
-    def _one_pass_ok(self, x):
-        """The fused one-pass log-likelihood (umnn_flow_ll_block_forward) applies: HIP path, fp32, nothing can ask for
-        a gradient (same rule as UMNNMAF._transform)."""
-        if len(self.nets) == 0 or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2:
-            return False
+    def _one_pass_specs(self, x):
+        """The integrand specs of the blocks when the fused one-pass log-likelihood (umnn_flow_ll_block_forward) applies, else None:
+        HIP path, fp32, nothing can ask for a gradient (same rule as UMNNMAF._transform)."""
+        if len(self.nets) == 0 or not x.is_cuda or x.dtype != torch.float32 or x.dim() != 2 or torch.is_autocast_enabled():
+            return None
+        specs, graph = [], _I._graph_mode()
         for net in self.nets:
-            if net.solver not in _SOLVERS or net.nb_steps < 1 or not _I._use_hip(mlp_spec(net.net.parallel_nets), x):
-                return False
-            if net.net.embedding_dtype not in (None, torch.float32) or torch.is_autocast_enabled():
-                return False                        # (the one-pass entry point is fp32-only; bf16 storage takes the _io route)
-        if not torch.is_grad_enabled():
-            return True
-        return not (x.requires_grad or any(p.requires_grad for p in self.parameters()))
-
-    def _compute_ll_graph(self, x, context):
-        """``compute_ll`` under torch.compile / export / jit.trace: one-pass, fused or composed as in eager, through the ops."""
-        nb = len(self.nets)
-        specs = [_I._graph_spec(net.net.parallel_nets, x) for net in self.nets]
-        one_pass = (nb > 0 and x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and not torch.is_autocast_enabled()
-                    and all(net.solver in _SOLVERS and net.nb_steps >= 1 and spec is not None
-                            and net.net.embedding_dtype in (None, torch.float32) for net, spec in zip(self.nets, specs))
-                    and (not torch.is_grad_enabled() or not (x.requires_grad or any(p.requires_grad for p in self.parameters()))))
-        if one_pass:
-            with torch.no_grad():
-                x = x.contiguous()
-                ll = None
-                for i, (net, spec) in enumerate(zip(self.nets, specs)):
-                    h = net.net.make_embeding(x, context)
-                    W, b, ha, oa = _ops.spec_args(spec)
-                    x, ll = torch.ops.umnn.flow_ll_block(x, h.contiguous(), net.scaling, W, b, ha, oa, net.nb_steps, i + 1 < nb,
-                                                         i == 0, i + 1 == nb, ll)
-            return ll, x
-        z, log_jac = self._stack(x, context, True)
-        if (z.is_cuda and z.dtype == torch.float32 and log_jac.dtype == torch.float32 and z.dim() == 2 and torch.is_grad_enabled()
-                and (z.requires_grad or log_jac.requires_grad) and not torch.is_autocast_enabled()
-                and os.environ.get("UMNN_FUSED_TRAIN", "1") != "0"):
-            return torch.ops.umnn.flow_ll(z.contiguous(), log_jac.contiguous()), z
-        log_prob_gauss = -.5 * (torch.log(self.pi * 2) + z ** 2).sum(1)
-        return log_jac.sum(1) + log_prob_gauss, z
+            # (the one-pass entry point is fp32-only; bf16 storage takes the _io route)
+            if net.solver not in _SOLVERS or net.nb_steps < 1 or net.net.embedding_dtype not in (None, torch.float32):
+                return None
+            specs.append(_I._hip_spec(net.net.parallel_nets, x, graph))
+            if specs[-1] is None:
+                return None
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            return None
+        return specs
 
     def compute_ll(self, x, context=None):
-        if _I._graph_mode():
-            return self._compute_ll_graph(x, context)
-        if self._one_pass_ok(x):
+        specs = self._one_pass_specs(x)
+        if specs is not None:
             # nb_flow x (conditioner + ONE launch): z, the running per-sample log-likelihood and the Gaussian term all
             # leave the quadrature kernel; no [B,d] log_jac accumulation, no elementwise epilogue (UMNNMAFFlow.py:109-119)
             with torch.no_grad():
                 x = x.contiguous()
-                ll = torch.empty(x.shape[0], device=x.device, dtype=torch.float32)
-                scratch = torch.empty_like(x)
-                cnt = _I.ll_counters(x.shape[0], x.device)      # (under a hipGraph capture: this call's own zeroed buffer)
-                nb = len(self.nets)
-                for i, net in enumerate(self.nets):
+                work, ll, nb = _I.flow_ll_workspace(x), None, len(self.nets)
+                for i, (net, spec) in enumerate(zip(self.nets, specs)):
                     h = net.net.make_embeding(x, context)
-                    x = _I.hip_flow_ll_block(mlp_spec(net.net.parallel_nets), x, h.contiguous(), net.scaling, net.nb_steps,
-                                             reverse_z=i + 1 < nb, first=i == 0, last=i + 1 == nb, ll=ll, scratch=scratch, cnt=cnt)
+                    x, ll = _I.flow_ll_link(spec, x, h.contiguous(), net.scaling, net.nb_steps, i + 1 < nb, i == 0, i + 1 == nb, ll, work)
             return ll, x
         z, log_jac = self._stack(x, context, True)
         if (z.is_cuda and z.dtype == torch.float32 and log_jac.dtype == torch.float32 and z.dim() == 2 and torch.is_grad_enabled()
                 and (z.requires_grad or log_jac.requires_grad) and not torch.is_autocast_enabled()
                 and os.environ.get("UMNN_FUSED_TRAIN", "1") != "0"):
-            return _I.FlowLogLikelihood.apply(z, log_jac), z        # (training: the reduction and its backward as one launch each)
+            return _I.flow_ll(z, log_jac), z        # (training: the reduction and its backward as one launch each)
         log_prob_gauss = -.5 * (torch.log(self.pi * 2) + z ** 2).sum(1)
         return log_jac.sum(1) + log_prob_gauss, z
 

@@ -30,6 +30,7 @@ import torch
 from torch.autograd.function import once_differentiable
 
 from . import _lib
+from ._common import _graph_mode, _ptr, _stream, traced_native_call  # noqa: F401  (the names are part of this module)
 from .nets import graph_spec, mlp_spec
 from .quadrature import compute_cc_weights, device_tables
 
@@ -78,30 +79,6 @@ def _flatten(sequence):
 # ----------------------------------------------------------------------------------------------
 # HIP path
 # ----------------------------------------------------------------------------------------------
-def _graph_mode():
-    """True while torch.compile / torch.export trace a call (Dynamo) or torch.jit.trace records one: the HIP launches then
-    go through the ``torch.ops.umnn`` ops (ops.py), which the graph records, instead of ctypes calls it cannot see."""
-    return torch.compiler.is_compiling() or torch.jit.is_tracing()
-
-
-def traced_native_call():
-    """The error for a native pointer taken while torch.jit.trace records: the tracer would keep the output allocation and
-    drop the launch, so the traced graph would return uninitialised memory.  Names the function that took the pointer."""
-    import sys
-    fn = sys._getframe(2).f_code.co_name
-    return RuntimeError(f"umnn_amd: {fn}() passed a tensor to a native call while torch.jit.trace was recording; the trace "
-                        "would not contain that launch.  Traced code has to reach the HIP kernels through torch.ops.umnn "
-                        "(umnn_amd.ops).")
-
-
-def _ptr(t):
-    if t is None:
-        return None
-    if torch._C._is_tracing():
-        raise traced_native_call()
-    return ctypes.c_void_p(t.data_ptr())
-
-
 _desc_cache = {}      # id(spec.linears[0]) -> (key, MlpDesc, keep-alive tensors)
 
 
@@ -136,18 +113,29 @@ def _desc(spec):
     return d, keep
 
 
-def _use_hip(spec, x):
-    if spec is None or getattr(_state, "force_generic", False):
+def _use_hip(spec, x, graph=False):
+    """The HIP kernels take this call.  ``graph`` (a call torch.compile / export / jit.trace records): the same rule without the
+    thread-local ``force_generic`` switch and the one-time host warning, which traced code can neither read nor raise."""
+    if spec is None or (not graph and getattr(_state, "force_generic", False)):
         return False
     if not x.is_cuda:
-        _warn_once("host", "umnn_amd: MLP integrand on host tensors -> generic ATen quadrature "
-                           "(the HIP kernels need GPU tensors; move the model and data to 'cuda').")
+        if not graph:
+            _warn_once("host", "umnn_amd: MLP integrand on host tensors -> generic ATen quadrature "
+                               "(the HIP kernels need GPU tensors; move the model and data to 'cuda').")
         return False
     if x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
         return False
     if spec.linears[0].weight.device != x.device:
         raise RuntimeError("umnn_amd: integrand weights and inputs are on different devices")
     return True
+
+
+def _hip_spec(integrand, x, graph=None):
+    """The MlpSpec of ``integrand`` when the HIP kernels take this call, else None: THE path decision, eager and recorded (there
+    from ``nets.graph_spec``, which writes no cache onto the module).  ``graph``: ``_graph_mode()``, for callers that ask per block."""
+    graph = _graph_mode() if graph is None else graph
+    spec = graph_spec(integrand) if graph else mlp_spec(integrand)
+    return spec if _use_hip(spec, x, graph) else None
 
 
 _bwd_kind = {}
@@ -185,26 +173,6 @@ def _hip_backward_ok(spec, x, h):
     return kind >= 0
 
 
-def aten_backward_jac(integrand, x0, x, h, gF, gfx, nb_steps):
-    """ATen counterpart of hip_backward for IntegralWithJacobian: the reference's quadrature VJP for the cotangent of F
-    plus ordinary autograd through f(x;h) for the cotangent of f_x -> (dx0, dx, dh, dtheta_flat)."""
-    dtheta, dh = aten_backward(integrand, x0, x, h, gF, nb_steps)
-    dh = dh.view(h.shape)
-    params = list(integrand.parameters())
-    xr, hr = x.detach().requires_grad_(True), h.detach().requires_grad_(True)
-    with torch.enable_grad():
-        fx = integrand(xr, hr)
-    dx = fx.detach() * gF
-    if gfx is not None:
-        grads = torch.autograd.grad(fx, [xr, hr] + params, gfx, allow_unused=True)
-        dx = dx + grads[0]
-        dh = dh + grads[1]
-        dtheta = dtheta + _flatten([g if g is not None else torch.zeros_like(p) for g, p in zip(grads[2:], params)])
-    with torch.no_grad():
-        dx0 = -integrand(x0, h) * gF
-    return dx0, dx, dh, dtheta
-
-
 def _shape(spec, x, h):
     if x.dim() != 2 or h.dim() != 2 or h.shape[0] != x.shape[0]:
         raise RuntimeError("umnn_amd: expected x [B,d] and h [B,E*d]")
@@ -223,14 +191,15 @@ def _f32c(t):
 def _io_prep(x_like, h):
     """Storage plan of one call (configuration C4: bf16 activations): tensors are handed to the kernels in the dtype the
     caller stores them in when that is fp32 or bf16 (no conversion pass, bf16 loads/stores inside the kernels); fp16 and
-    anything else is converted to fp32 at the boundary.  -> (x dtype, h dtype, umnn_io or None)."""
+    anything else is converted to fp32 at the boundary.  -> (x dtype, h dtype, umnn_io pointer; None = all fp32: every ``_io``
+    entry point takes a null descriptor for that)."""
     xd = x_like.dtype if x_like.dtype in (torch.float32, torch.bfloat16) else torch.float32
     hd = h.dtype if h.dtype in (torch.float32, torch.bfloat16) else torch.float32
     if xd == torch.float32 and hd == torch.float32:
         return xd, hd, None
     io = _lib.IoDesc(_lib.DTYPE_BF16 if xd == torch.bfloat16 else _lib.DTYPE_F32,
                      _lib.DTYPE_BF16 if hd == torch.bfloat16 else _lib.DTYPE_F32)
-    return xd, hd, io
+    return xd, hd, ctypes.byref(io)
 
 
 def _as(t, dtype):
@@ -248,13 +217,8 @@ def hip_forward(spec, x0, x, h, nb_steps, inv_f=False):
     F, fx, fx0 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
     desc, keep = _desc(spec)
     with torch.cuda.device(x.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        if io is None:
-            rc = lib.umnn_cc_forward(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps),
-                                     B, d, E, int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0), stream)
-        else:
-            rc = lib.umnn_cc_forward_io(ctypes.byref(desc), ctypes.byref(io), _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s),
-                                        int(nb_steps), B, d, E, int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0), stream)
+        rc = lib.umnn_cc_forward_io(ctypes.byref(desc), io, _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps), B, d, E,
+                                    int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0), _stream(x.device))
     _lib.check(rc, "umnn_cc_forward")
     _state.path = "hip"
     if out_dtype != xd:                   # fp16 callers: fp32 inside, their dtype outside
@@ -275,6 +239,21 @@ def _z2_release(nbytes):
     _z2_live[0] -= nbytes
 
 
+def _z2_buffer(desc, x, h, B, d, E, nb_steps):
+    """-> (z2, floats): the fp32 buffer umnn_cc_backward_saved wants, or (None, 0) when the pair does not apply to this net / storage /
+    arithmetic mode or the buffer would exceed either cap."""
+    # (fp32 x-class tensors; the embedding h in fp32 or -- configuration C4 -- bf16, loaded as such by the kernels)
+    if x.dtype != torch.float32 or h.dtype not in (torch.float32, torch.bfloat16):
+        return None, 0
+    nfl = int(_lib.lib().umnn_cc_forward_z2_floats(ctypes.byref(desc), B, d, E, int(nb_steps)))
+    if not (0 < 4 * nfl <= _Z2_MAX_BYTES and _z2_live[0] + 4 * nfl <= _Z2_TOTAL_BYTES):
+        return None, 0
+    z2 = torch.empty(nfl, device=x.device, dtype=torch.float32)
+    _z2_live[0] += 4 * nfl
+    weakref.finalize(z2, _z2_release, 4 * nfl)
+    return z2, nfl
+
+
 def hip_flow_block(spec, x, h, scaling, nb_steps, reverse_z=False, log_jac_in=None, save_z2=False):
     """Fused block epilogue -> (z, log_jac, f_x, f_x0).  ``reverse_z``: z comes back with its dimensions reversed (the
     flip between the blocks of a flow); ``log_jac_in``: running log_jac of the previous blocks, added in the kernel.
@@ -282,59 +261,25 @@ def hip_flow_block(spec, x, h, scaling, nb_steps, reverse_z=False, log_jac_in=No
     the pair does not apply to this net / arithmetic mode or the buffer would exceed UMNN_SAVE_Z2_MAX_GB (default 2) per block."""
     lib = _lib.lib()
     B, d, E = _shape(spec, x, h)
-    if save_z2:
-        z2 = None
-        # (fp32 x-class tensors; the embedding h in fp32 or -- configuration C4 -- bf16, loaded as such by the kernels)
-        if x.dtype == torch.float32 and h.dtype in (torch.float32, torch.bfloat16):
-            desc, keep = _desc(spec)
-            nfl = int(lib.umnn_cc_forward_z2_floats(ctypes.byref(desc), B, d, E, int(nb_steps)))
-            if 0 < 4 * nfl <= _Z2_MAX_BYTES and _z2_live[0] + 4 * nfl <= _Z2_TOTAL_BYTES:
-                _, _, io = _io_prep(x, h)
-                x, h, scaling = _f32c(x), h.detach().contiguous(), _f32c(scaling)
-                w, s = device_tables(nb_steps, x.device)
-                z2 = torch.empty(nfl, device=x.device, dtype=torch.float32)
-                _z2_live[0] += 4 * nfl
-                weakref.finalize(z2, _z2_release, 4 * nfl)
-                z, lj, fx, fx0 = (torch.empty_like(x) for _ in range(4))
-                lj_in = _as(log_jac_in, torch.float32)
-                with torch.cuda.device(x.device):
-                    stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-                    if io is None:
-                        rc = lib.umnn_flow_stack_block_forward_save(ctypes.byref(desc), _ptr(x), _ptr(h), _ptr(scaling), _ptr(w), _ptr(s),
-                                                                    int(nb_steps), B, d, E, 1 if reverse_z else 0, _ptr(lj_in), _ptr(z), _ptr(lj),
-                                                                    _ptr(fx), _ptr(fx0), _ptr(z2), nfl, stream)
-                    else:
-                        rc = lib.umnn_flow_stack_block_forward_save_io(ctypes.byref(desc), ctypes.byref(io), _ptr(x), _ptr(h), _ptr(scaling),
-                                                                       _ptr(w), _ptr(s), int(nb_steps), B, d, E, 1 if reverse_z else 0,
-                                                                       _ptr(lj_in), _ptr(z), _ptr(lj), _ptr(fx), _ptr(fx0), _ptr(z2), nfl, stream)
-                if rc == 0:
-                    _state.path = "hip"
-                    return z, lj, fx, fx0, z2
-                if rc != _lib.EUNSUPPORTED:
-                    _lib.check(rc, "umnn_flow_stack_block_forward_save")
-        return (*hip_flow_block(spec, x, h, scaling, nb_steps, reverse_z, log_jac_in), None)
+    desc, keep = _desc(spec)
+    z2, nfl = _z2_buffer(desc, x, h, B, d, E, nb_steps) if save_z2 else (None, 0)
     out_dtype = x.dtype
     xd, hd, io = _io_prep(x, h)
-    x, h, scaling = _as(x, xd), _as(h, hd), _f32c(scaling)
+    x, h, scaling, lj_in = _as(x, xd), _as(h, hd), _f32c(scaling), _as(log_jac_in, xd)
     w, s = device_tables(nb_steps, x.device)
     z, lj, fx, fx0 = (torch.empty_like(x) for _ in range(4))
-    desc, keep = _desc(spec)
+    args = (ctypes.byref(desc), io, _ptr(x), _ptr(h), _ptr(scaling), _ptr(w), _ptr(s), int(nb_steps), B, d, E, 1 if reverse_z else 0,
+            _ptr(lj_in), _ptr(z), _ptr(lj), _ptr(fx), _ptr(fx0))
     with torch.cuda.device(x.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        lj_in = _as(log_jac_in, xd)
-        if io is None:
-            rc = lib.umnn_flow_stack_block_forward(ctypes.byref(desc), _ptr(x), _ptr(h), _ptr(scaling), _ptr(w), _ptr(s),
-                                                   int(nb_steps), B, d, E, 1 if reverse_z else 0, _ptr(lj_in),
-                                                   _ptr(z), _ptr(lj), _ptr(fx), _ptr(fx0), stream)
-        else:
-            rc = lib.umnn_flow_stack_block_forward_io(ctypes.byref(desc), ctypes.byref(io), _ptr(x), _ptr(h), _ptr(scaling),
-                                                      _ptr(w), _ptr(s), int(nb_steps), B, d, E, 1 if reverse_z else 0,
-                                                      _ptr(lj_in), _ptr(z), _ptr(lj), _ptr(fx), _ptr(fx0), stream)
+        rc = lib.umnn_flow_stack_block_forward_save_io(*args, _ptr(z2), nfl, _stream(x.device)) if z2 is not None else _lib.EUNSUPPORTED
+        if rc == _lib.EUNSUPPORTED:         # no z_2 hand-off (not asked for, capped, or the library says it does not apply)
+            z2 = None
+            rc = lib.umnn_flow_stack_block_forward_io(*args, _stream(x.device))
     _lib.check(rc, "umnn_flow_stack_block_forward")
     _state.path = "hip"
     if out_dtype != xd:
         z, lj, fx, fx0 = z.to(out_dtype), lj.to(out_dtype), fx.to(out_dtype), fx0.to(out_dtype)
-    return z, lj, fx, fx0
+    return (z, lj, fx, fx0, z2) if save_z2 else (z, lj, fx, fx0)
 
 
 def _inverse_call(fn_name, spec, h, rows, nb_steps, call, warn_key, warn_text):
@@ -349,8 +294,7 @@ def _inverse_call(fn_name, spec, h, rows, nb_steps, call, warn_key, warn_text):
     w, s = device_tables(nb_steps, rows.device)
     desc, keep = _desc(spec)
     with torch.cuda.device(rows.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream)
-        rc = call(lib, ctypes.byref(desc), _ptr(w), _ptr(s), B, d, E, stream)
+        rc = call(lib, ctypes.byref(desc), _ptr(w), _ptr(s), B, d, E, _stream(rows.device))
     if rc == _lib.EUNSUPPORTED:
         _warn_once((warn_key, tuple(l.out_features for l in spec.linears), _lib.get_forward_precision()),
                    warn_text.format(_lib.lib().umnn_last_error().decode('utf-8', 'replace')))
@@ -545,13 +489,12 @@ def hip_flow_ll_block(spec, x, h, scaling, nb_steps, reverse_z, first, last, ll,
     w, s = device_tables(nb_steps, x.device)
     desc, keep = _desc(spec)
     with torch.cuda.device(x.device):
-        handle = torch.cuda.current_stream(x.device).cuda_stream
         if cnt is None:
             cnt = ll_counters(B, x.device)
         rc = lib.umnn_flow_ll_block_forward(ctypes.byref(desc), _ptr(x), _ptr(h), _ptr(scaling), _ptr(w), _ptr(s),
                                             int(nb_steps), B, d, E, 1 if reverse_z else 0, 1 if first else 0,
                                             1 if last else 0, _ptr(z), _ptr(scratch), _ptr(ll), _ptr(cnt),
-                                            ctypes.c_void_p(handle))
+                                            _stream(x.device))
     _lib.check(rc, "umnn_flow_ll_block_forward")
     _state.path = "hip"
     return z
@@ -575,24 +518,14 @@ def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True
     with torch.cuda.device(x.device):
         nbytes = lib.umnn_cc_backward_workspace_bytes(ctypes.byref(desc), B, d, E)
         ws = torch.empty(max(int(nbytes), 4), device=x.device, dtype=torch.uint8)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
-        if z2_saved is not None and io is not None and not inv_f and x0 is None and not need[0]:
-            rc = lib.umnn_cc_backward_saved_io(ctypes.byref(desc), ctypes.byref(io), _ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s),
-                                               int(nb_steps), B, d, E, _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved), int(z2_saved.numel()),
-                                               _ptr(ws), int(nbytes), stream)
-        elif z2_saved is not None and io is None and not inv_f and x0 is None and not need[0]:      # (that entry point has no d_x0 output)
-            rc = lib.umnn_cc_backward_saved(ctypes.byref(desc), _ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s), int(nb_steps),
-                                            B, d, E, _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved), int(z2_saved.numel()),
-                                            _ptr(ws), int(nbytes), stream)
-        elif io is None and not inv_f:
-            rc = lib.umnn_cc_backward(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(g), _ptr(g_fx),
-                                      _ptr(w), _ptr(s), int(nb_steps), B, d, E,
-                                      _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(ws), int(nbytes), stream)
+        head = (ctypes.byref(desc), io)
+        mid = (_ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s), int(nb_steps), B, d, E)
+        if z2_saved is not None and not inv_f and x0 is None and not need[0]:      # (that entry point has no x0 and no d_x0 output)
+            rc = lib.umnn_cc_backward_saved_io(*head, *mid, _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved), int(z2_saved.numel()),
+                                               _ptr(ws), int(nbytes), _stream(x.device))
         else:
-            rc = lib.umnn_cc_backward_io(ctypes.byref(desc), ctypes.byref(io) if io is not None else None,
-                                         _ptr(x0), _ptr(x), _ptr(h), _ptr(g), _ptr(g_fx),
-                                         _ptr(w), _ptr(s), int(nb_steps), B, d, E, int(bool(inv_f)),
-                                         _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(ws), int(nbytes), stream)
+            rc = lib.umnn_cc_backward_io(*head, _ptr(x0), *mid, int(bool(inv_f)), _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta),
+                                         _ptr(ws), int(nbytes), _stream(x.device))
     _lib.check(rc, "umnn_cc_backward")
     _state.path = _last_backward["path"] = "hip"
     if x_dtype != xd:
@@ -638,119 +571,146 @@ def aten_forward(integrand, x0, x, h, nb_steps, inv_f=False):
     return total * span / 2
 
 
-def aten_backward(integrand, x0, x, h, g, nb_steps, inv_f=False):
-    """d_theta (flat, parameters() order) and d_h: VJP of f over all nodes with cotangent g*(x-x0)/2*w_k."""
+def _pure(integrand):
+    """``integrand`` as a pure function of its parameters -> (f(params, t, h), params): a module through ``functional_call`` on its
+    detached ``parameters()``; any other callable with an empty parameter list; a pair that already is one (the ops' W[] / b[]
+    adapter, ``ops.pure_mlp``) as it is."""
+    if isinstance(integrand, tuple):
+        return integrand
+    if isinstance(integrand, torch.nn.Module):
+        names = [n for n, _ in integrand.named_parameters()]
+        return (lambda ps, t, h: torch.func.functional_call(integrand, dict(zip(names, ps)), (t, h)),
+                [p.detach() for p in integrand.parameters()])
+    return (lambda ps, t, h: integrand(t, h)), []
+
+
+def aten_vjp(integrand, x0, x, h, g, g_fx, nb_steps, inv_f=False, limits=True):
+    """THE ATen quadrature backward -> (dx0, dx, dh, dtheta): the VJP of f over all nodes with cotangent g (x - x0)/2 w_k for the
+    parameters and h, in node chunks; with ``g_fx`` the VJP of f(x; h) for the cotangent of the f_x output on top; the Leibniz terms
+    dx = f(x) g and dx0 = -f(x0) g (None unless ``limits``).  dtheta is flat, in parameters() order, None for an integrand without
+    parameters.  ``torch.func.vjp`` over the pure form of the integrand (``_pure``), so the same code runs inside a
+    ``once_differentiable`` backward and inside an op kernel below autograd, where ``torch.autograd.grad`` records nothing."""
+    f, params = _pure(integrand)
     w, s = device_tables(nb_steps, x.device)
     w, u = w.to(x.dtype), s.to(x.dtype) + 1
-    span = x - x0
-    cot = g * span / 2
-    params = [p for p in integrand.parameters()] if isinstance(integrand, torch.nn.Module) else []
-    g_params = [torch.zeros_like(p) for p in params]
-    g_h = torch.zeros_like(h)
-    B = x.shape[0]
-    for a, b in _node_chunks(nb_steps, B, h.shape[1] + x.shape[1]):
-        t, h_rep = _eval_chunk(integrand, x0, span, h, u[a:b])
-        h_rep = h_rep.detach().requires_grad_(True)
-        with torch.enable_grad():
-            f = integrand(t.detach(), h_rep)
-            if inv_f:
-                f = 1 / f
-            cot_c = (cot.unsqueeze(0) * w[a:b].view(-1, 1, 1)).reshape(f.shape)
-            grads = torch.autograd.grad(f, params + [h_rep], cot_c, allow_unused=True)
-        for acc, gr in zip(g_params, grads[:-1]):
-            if gr is not None:
+    with torch.no_grad():
+        span = x - x0
+        cot = g * span / 2
+        B = x.shape[0]
+        d_params = [torch.zeros_like(p) for p in params]
+        dh = torch.zeros_like(h)
+        for a, e in _node_chunks(nb_steps, B, h.shape[1] + x.shape[1]):
+            t, h_rep = _eval_chunk(None, x0, span, h, u[a:e])
+
+            def f_nodes(ps, hr, t=t):
+                v = f(ps, t, hr)
+                return 1 / v if inv_f else v
+
+            val, vjp = torch.func.vjp(f_nodes, params, h_rep)
+            gp, gh = vjp((cot.unsqueeze(0) * w[a:e].view(-1, 1, 1)).reshape(val.shape))
+            for acc, gr in zip(d_params, gp):
                 acc += gr
-        if grads[-1] is not None:
-            g_h += grads[-1].view(b - a, B, -1).sum(0)
+            dh += gh.view(e - a, B, -1).sum(0)
+        dx0 = dx = None
+        if g_fx is not None:
+            fx, vjp = torch.func.vjp(f, params, x, h)
+            gp, gx, gh = vjp(g_fx)
+            dx, dh = fx * g + gx, dh + gh
+            d_params = [acc + gr for acc, gr in zip(d_params, gp)]
+        elif limits:
+            dx = f(params, x, h) * g
+        if limits:
+            dx0 = -f(params, x0, h) * g
     _state.path = _last_backward["path"] = "aten"
-    return (_flatten(g_params) if params else None), g_h
+    return dx0, dx, dh, (_flatten(d_params) if d_params else None)
 
 
-def _graph_spec(integrand, x):
-    """Graph mode: the MlpSpec when the HIP kernels apply (same rule as ``_use_hip``, without its thread-local switches), else None."""
-    spec = graph_spec(integrand)
-    if spec is None or not x.is_cuda or x.dtype not in (torch.float32, torch.bfloat16, torch.float16):
-        return None
-    if spec.linears[0].weight.device != x.device:
-        raise RuntimeError("umnn_amd: integrand weights and inputs are on different devices")
-    return spec
+def aten_backward(integrand, x0, x, h, g, nb_steps, inv_f=False):
+    """(d_theta, d_h) of ``aten_vjp``: what ``integrate(compute_grad=True)`` returns."""
+    _, _, dh, dtheta = aten_vjp(integrand, x0, x, h, g, None, nb_steps, inv_f, limits=False)
+    return dtheta, dh
 
 
-def _graph_forward(ctx, spec, x0, x, h, nb_steps, inv_f, jac):
-    """Forward of the autograd Functions below in graph mode: ``umnn::cc_forward``, and for the backward only tensors and
-    plain values on ``ctx`` (Dynamo traces both methods; they may call nothing but torch.ops.umnn and ATen).  -> (F, f_x)"""
-    W, b = [l.weight for l in spec.linears], [l.bias for l in spec.linears]
-    ctx.graph = (spec.hidden_act, spec.out_act, int(nb_steps), bool(inv_f), bool(jac), len(W), x0 is None)
-    ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
-    return torch.ops.umnn.cc_forward(x0, x, h, W, b, spec.hidden_act, spec.out_act, int(nb_steps), bool(inv_f))
-
-
-def _graph_backward(ctx, gF, gfx, need):
-    """-> (dx0, dx, dh, dtheta_flat) through ``umnn::cc_backward`` (which picks the HIP or the ATen backward when it runs);
-    None where need[...] is False.  ``gfx`` is dropped for operators whose f_x output is not theirs (jac False)."""
-    ha, oa, nb_steps, inv_f, jac, L, x0_none = ctx.graph
-    saved = ctx.saved_tensors
-    x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
-    x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
-    need = [bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3])]
-    out = torch.ops.umnn.cc_backward(x0, x, h, gF, gfx if jac else None, W, b, ha, oa, nb_steps, need, inv_f)
+def quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None):
+    """The quadrature backward of every operator -> (dx0, dx, dh, dtheta_flat), None where ``need`` says so: the HIP kernels when
+    ``spec`` (None: the forward ran on ATen) has a backward kernel, else ``aten_vjp`` on ``integrand``.  x0 None: lower limit 0."""
+    need = (bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3]))
+    if spec is not None and _hip_backward_ok(spec, x, h):
+        return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f=inv_f, z2_saved=z2_saved)
+    out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
     return tuple(t if n else None for t, n in zip(out, need))
 
 
-class IntegralWithJacobianParams(torch.autograd.Function):
-    """IntegralWithJacobian with the integrand's parameters passed one by one instead of as one flat tensor: no
-    ``torch.cat`` in the forward and no cat-backward (a narrow + copy per parameter) in the backward -- the gradients are
-    views into the kernel's flat d_theta.  Internal to the flow blocks; the public operators keep the reference's
-    ``flat_params`` signature."""
+def split_flat(flat, shapes, needed):
+    """Flat d_theta -> views of ``shapes`` in parameters() order (W_0, b_0, W_1, ...), None where not ``needed``: no narrow + copy
+    per parameter."""
+    grads, o = [], 0
+    for shp, n in zip(shapes, needed):
+        k = int(torch.Size(shp).numel())
+        grads.append(flat[o:o + k].view(shp) if (n and flat is not None) else None)
+        o += k
+    return grads
 
-    @staticmethod
-    def forward(ctx, x0, x, integrand, h, nb_steps, *params):
-        if _graph_mode():
-            spec = _graph_spec(integrand, x)
-            if spec is None:
-                raise RuntimeError("IntegralWithJacobianParams needs an MLP integrand on a GPU")
-            return _graph_forward(ctx, spec, x0, x, h, nb_steps, False, True)
-        spec = mlp_spec(integrand)
-        if not _use_hip(spec, x):
-            raise RuntimeError("IntegralWithJacobianParams needs an MLP integrand on a GPU")
-        ctx.spec, ctx.nb_steps, ctx.integrand = spec, nb_steps, integrand
-        ctx.shapes = [p.shape for p in params]
-        ctx.x0_none = x0 is None                    # lower limit 0: no tensor to save, clone or differentiate
-        if ctx.x0_none:
-            ctx.save_for_backward(x.clone(), h)
+
+# ----------------------------------------------------------------------------------------------
+# the seam: a ctypes launch, or -- while a graph is recorded -- the torch.ops.umnn op of the same launch
+# ----------------------------------------------------------------------------------------------
+def spec_args(spec):
+    """MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it."""
+    return [l.weight for l in spec.linears], [l.bias for l in spec.linears], spec.hidden_act, spec.out_act
+
+
+def cc_forward(spec, x0, x, h, nb_steps, inv_f=False):
+    """-> (F, f_x).  Recorded: ``umnn::cc_forward``, differentiable through the op."""
+    if _graph_mode():
+        return torch.ops.umnn.cc_forward(x0, x, h, *spec_args(spec), int(nb_steps), bool(inv_f))
+    return hip_forward(spec, x0, x, h, nb_steps, inv_f)[:2]
+
+
+def cc_forward_jac(spec, integrand, x0, x, h, nb_steps, no_graph):
+    """(F, f_x) of a flow block whose epilogue is composed from torch ops: ``IntegralWithJacobianParams`` when a gradient can be
+    asked for, the bare launch otherwise (``no_graph``)."""
+    if no_graph or _graph_mode():
+        return cc_forward(spec, x0, x, h, nb_steps)
+    return IntegralWithJacobianParams.apply(x0, x, integrand, h, nb_steps, *integrand.parameters())
+
+
+def flow_block(spec, integrand, x, h, scaling, nb_steps, reverse_z, log_jac_in, train):
+    """(z, log_jac) of a block with the epilogue inside the launch.  ``train``: as ONE autograd node -- eager ``FlowBlockTransform``
+    with its z_2 hand-off, recorded ``umnn::flow_block`` (whose backward recomputes z_2: never a different result)."""
+    if _graph_mode():
+        if train:
+            x, h = x.contiguous(), h.contiguous()
         else:
-            ctx.save_for_backward(x0.clone(), x.clone(), h)
-        F, fx, _ = hip_forward(spec, x0, x, h, nb_steps, False)
-        return F, fx
-
-    @staticmethod
-    @once_differentiable        # double backward (create_graph=True through the quadrature) raises instead of silently detaching
-    def backward(ctx, gF, gfx):
-        if getattr(ctx, "graph", None) is not None:
-            nig = ctx.needs_input_grad
-            dx0, dx, dh, dtheta = _graph_backward(ctx, gF, gfx, (nig[0], nig[1], nig[3], any(nig[5:])))
-            return (dx0, dx, None, dh, None, *_split(dtheta, ctx.graph[5], ctx.saved_tensors[-2 * ctx.graph[5]:], nig[5:]))
-        if ctx.x0_none:
-            (x, h), x0 = ctx.saved_tensors, None
-        else:
-            x0, x, h = ctx.saved_tensors
-        if not _hip_backward_ok(ctx.spec, x, h):
-            dx0, dx, dh, dtheta = aten_backward_jac(ctx.integrand, torch.zeros_like(x) if x0 is None else x0, x, h, gF, gfx,
-                                                    ctx.nb_steps)
-        else:
-            need = (ctx.needs_input_grad[0] and x0 is not None, ctx.needs_input_grad[1], ctx.needs_input_grad[3],
-                    any(ctx.needs_input_grad[5:]))
-            dx0, dx, dh, dtheta = hip_backward(ctx.spec, x0, x, h, gF, gfx, ctx.nb_steps, need)
-        grads, o = [], 0
-        for shp, needed in zip(ctx.shapes, ctx.needs_input_grad[5:]):
-            n = int(torch.Size(shp).numel())
-            grads.append(dtheta[o:o + n].view(shp) if (needed and dtheta is not None) else None)
-            o += n
-        return (None if ctx.x0_none else dx0, dx, None, dh, None, *grads)
+            scaling = scaling.detach()          # (like the eager launch: no gradient for scaling on this path)
+        return torch.ops.umnn.flow_block(x, h, scaling, *spec_args(spec), nb_steps, reverse_z, log_jac_in)[:2]
+    if train:
+        return FlowBlockTransform.apply(x.contiguous(), integrand, h.contiguous(), scaling, nb_steps, reverse_z, log_jac_in,
+                                        *integrand.parameters())
+    return hip_flow_block(spec, x, h, scaling, nb_steps, reverse_z, log_jac_in)[:2]
 
 
-def _stream(device):
-    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+def flow_ll(z, log_jac):
+    """Differentiable ll [B] from z and the summed log_jac: one launch per direction."""
+    if _graph_mode():
+        return torch.ops.umnn.flow_ll(z.contiguous(), log_jac.contiguous())
+    return FlowLogLikelihood.apply(z, log_jac)
+
+
+def flow_ll_workspace(x):
+    """What the links of one one-pass log-likelihood share in eager mode -> (ll [B], scratch [B,d], row counters: under a hipGraph
+    capture this call's own zeroed buffer); None while a graph is recorded, where every ``umnn::flow_ll_block`` owns its own."""
+    if _graph_mode():
+        return None
+    return (torch.empty(x.shape[0], device=x.device, dtype=torch.float32), torch.empty_like(x), ll_counters(x.shape[0], x.device))
+
+
+def flow_ll_link(spec, x, h, scaling, nb_steps, reverse_z, first, last, ll, work):
+    """One link of the one-pass log-likelihood -> (z, running ll); ``ll`` None for the first link, ``work`` from ``flow_ll_workspace``."""
+    if work is None:
+        return torch.ops.umnn.flow_ll_block(x, h, scaling, *spec_args(spec), nb_steps, reverse_z, first, last, ll)
+    ll, scratch, cnt = work
+    return hip_flow_ll_block(spec, x, h, scaling, nb_steps, reverse_z, first, last, ll, scratch, cnt), ll
 
 
 def hip_flow_block_cotangents(gz, glj, fx, scaling, reverse_z):
@@ -810,14 +770,24 @@ def hip_flow_ll_backward(z, g_ll, need_z, need_lj):
     return gz, glj
 
 
+def flow_block_vjp(spec, integrand, x, h, fx, scaling, gz, glj, nb_steps, reverse_z, need, z2_saved=None):
+    """Backward of a fused block -> (dx, dh, dtheta_flat) for ``need``: one elementwise launch (cotangents of F and f_x from those of z
+    and log_jac), the quadrature backward, and the h_0 term added into d_h."""
+    B, d = x.shape
+    gF, gfx = hip_flow_block_cotangents(gz, glj, fx, scaling, reverse_z)
+    _, dx, dh, dtheta = quadrature_backward(spec, integrand, None, x, h, gF, gfx, nb_steps, (False, *need), z2_saved=z2_saved)
+    if dh is not None:
+        dh.view(B, -1, d)[:, 0, :].add_(gF)            # z carries h_0 = embedding row 0 (UMNNMAF.py:80)
+    return dx, dh, dtheta
+
+
 class FlowBlockTransform(torch.autograd.Function):
     """(z, log_jac) of one UMNN-MAF block on the TRAINING path as ONE autograd node (UMNNMAF.py:76-139):
 
         z[b, rev(i)] = exp(s_i) (int_0^{x_bi} f(t; h_b) dt + h_0[b,i]),     log_jac = [log_jac_in +] log(f(x; h) + 1e-10) + s
 
-    forward = the fused-epilogue launch of the inference path (umnn_flow_stack_block_forward); backward = one elementwise launch
-    (umnn_flow_block_cotangents: cotangents of F and f_x from those of z and log_jac), the quadrature backward, and the h_0 term
-    added into d_h.  Composed from torch ops (exp, mul, add, log, add, flip, select and their backward nodes) the same
+    forward = the fused-epilogue launch of the inference path (umnn_flow_stack_block_forward); backward = ``flow_block_vjp``.
+    Composed from torch ops (exp, mul, add, log, add, flip, select and their backward nodes) the same
     arithmetic is ~15 launches and 8 autograd nodes per block.  Internal to the flow blocks: fp32 storage, lower limit 0, frozen
     ``scaling`` (UMNNMAF.py:53) -- anything else keeps the composed path."""
 
@@ -838,24 +808,13 @@ class FlowBlockTransform(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, gz, glj):
         x, h, fx, scaling = ctx.saved_tensors
-        B, d = x.shape
+        nig = ctx.needs_input_grad
         gz = None if gz is None else gz.contiguous()
         glj = None if glj is None else glj.contiguous()
-        gF, gfx = hip_flow_block_cotangents(gz, glj, fx, scaling, ctx.reverse_z)
-        if not _hip_backward_ok(ctx.spec, x, h):
-            _, dx, dh, dtheta = aten_backward_jac(ctx.integrand, torch.zeros_like(x), x, h, gF, gfx, ctx.nb_steps)
-        else:
-            need = (False, ctx.needs_input_grad[0], ctx.needs_input_grad[2], any(ctx.needs_input_grad[7:]))
-            _, dx, dh, dtheta = hip_backward(ctx.spec, None, x, h, gF, gfx, ctx.nb_steps, need, z2_saved=ctx.z2)
-            ctx.z2 = None
-        if dh is not None:
-            dh.view(B, -1, d)[:, 0, :].add_(gF)            # z carries h_0 = embedding row 0 (UMNNMAF.py:80)
-        grads, o = [], 0
-        for shp, needed in zip(ctx.shapes, ctx.needs_input_grad[7:]):
-            n = int(torch.Size(shp).numel())
-            grads.append(dtheta[o:o + n].view(shp) if (needed and dtheta is not None) else None)
-            o += n
-        return (dx, None, dh, None, None, None, glj if ctx.needs_input_grad[6] else None, *grads)
+        dx, dh, dtheta = flow_block_vjp(ctx.spec, ctx.integrand, x, h, fx, scaling, gz, glj, ctx.nb_steps, ctx.reverse_z,
+                                        (nig[0], nig[2], any(nig[7:])), z2_saved=ctx.z2)
+        ctx.z2 = None
+        return (dx, None, dh, None, None, None, glj if nig[6] else None, *split_flat(dtheta, ctx.shapes, nig[7:]))
 
 
 class FlowLogLikelihood(torch.autograd.Function):
@@ -892,105 +851,108 @@ def integrate(x0, nb_steps, step_sizes, integrand, h, compute_grad=False, x_tot=
     (what the reference's backward consumes).  ``cc_weights``/``steps`` are accepted for signature parity; the
     tables are a pure function of nb_steps and come from the per-device cache."""
     x = x0 + nb_steps * step_sizes
-    gspec = _graph_spec(integrand, x) if _graph_mode() else None
-    if gspec is not None:
-        # graph mode: the same choices as below, with the launches as torch.ops.umnn ops (ParallelNeuralIntegral routes itself)
-        W, b = [l.weight for l in gspec.linears], [l.bias for l in gspec.linears]
-        if not compute_grad:
-            if torch.is_grad_enabled() and (x.requires_grad or (h is not None and h.requires_grad)
-                                            or any(p.requires_grad for p in integrand.parameters())):
-                return ParallelNeuralIntegral.apply(x0, x, integrand, _flatten(integrand.parameters()), h, nb_steps, inv_f)
-            return torch.ops.umnn.cc_forward(x0, x, h, W, b, gspec.hidden_act, gspec.out_act, int(nb_steps), bool(inv_f))[0]
-        with torch.no_grad():                       # (like the eager call: the gradients themselves are not differentiated)
-            _, _, dh, dtheta = torch.ops.umnn.cc_backward(x0, x, h, x_tot, None, W, b, gspec.hidden_act, gspec.out_act,
-                                                          int(nb_steps), [False, False, True, True], bool(inv_f))
+    spec = _hip_spec(integrand, x)
+    if compute_grad:
+        if spec is None:
+            return aten_backward(integrand, x0, x, h, x_tot, nb_steps, inv_f)
+        with torch.no_grad():                       # (the gradients themselves are not differentiated)
+            _, _, dh, dtheta = _launch_backward(_graph_mode() and spec_args(spec), spec, integrand, x0, x, h, x_tot, None, nb_steps,
+                                                (False, False, True, True), inv_f)
         return dtheta, dh
-    spec = mlp_spec(integrand)
-    if not compute_grad:
-        # The reference's direct integration is plain ATen, hence differentiable by ordinary autograd
-        # (ParallelNeuralIntegral.py:49-65).  Keep that: only when nothing can ask for a gradient is the graph skipped.
-        wants_graph = torch.is_grad_enabled() and (
-            x.requires_grad or (h is not None and h.requires_grad)
-            or (isinstance(integrand, torch.nn.Module) and any(p.requires_grad for p in integrand.parameters())))
-        if _use_hip(spec, x):
-            if wants_graph:
-                return ParallelNeuralIntegral.apply(x0, x, integrand, _flatten(integrand.parameters()), h, nb_steps, inv_f)
-            return hip_forward(spec, x0, x, h, nb_steps, inv_f)[0]
-        if wants_graph:
+    # The reference's direct integration is plain ATen, hence differentiable by ordinary autograd
+    # (ParallelNeuralIntegral.py:49-65).  Keep that: only when nothing can ask for a gradient is the graph skipped.
+    wants_graph = torch.is_grad_enabled() and (
+        x.requires_grad or (h is not None and h.requires_grad)
+        or (isinstance(integrand, torch.nn.Module) and any(p.requires_grad for p in integrand.parameters())))
+    if spec is None:
+        with torch.set_grad_enabled(wants_graph):
             return aten_forward(integrand, x0, x, h, nb_steps, inv_f)
-        with torch.no_grad():
-            return aten_forward(integrand, x0, x, h, nb_steps, inv_f)
-    if _use_hip(spec, x) and _hip_backward_ok(spec, x, h):
-        _, _, dh, dtheta = hip_backward(spec, x0, x, h, x_tot, None, nb_steps, need=(False, False, True, True), inv_f=inv_f)
-        return dtheta, dh
-    return aten_backward(integrand, x0, x, h, x_tot, nb_steps, inv_f)
+    if wants_graph:
+        return ParallelNeuralIntegral.apply(x0, x, integrand, _flatten(integrand.parameters()), h, nb_steps, inv_f)
+    return cc_forward(spec, x0, x, h, nb_steps, inv_f)[0]
 
 
-def _split(dtheta, L, Wb, needed):
-    """Graph mode: flat d_theta -> per-parameter views, in parameters() order (W_0, b_0, W_1, ...); ``Wb`` the saved W[] + b[]."""
-    params = [p for pair in zip(Wb[:L], Wb[L:]) for p in pair]
-    grads, o = [], 0
-    for p, n in zip(params, needed):
-        grads.append(dtheta[o:o + p.numel()].view(p.shape) if (n and dtheta is not None) else None)
-        o += p.numel()
-    return grads
+def _launch_backward(net, spec, integrand, x0, x, h, g, g_fx, nb_steps, need, inv_f=False):
+    """``quadrature_backward`` -> (dx0, dx, dh, dtheta_flat), None where not needed.  ``net`` = (W[], b[], hidden_act, out_act): as the recorded
+    ``umnn::cc_backward`` (which makes the same HIP / ATen choice when it runs); falsy: the eager call."""
+    if not net:
+        return quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need, inv_f)
+    need = [bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3])]
+    out = torch.ops.umnn.cc_backward(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
+    return tuple(t if n else None for t, n in zip(out, need))
 
 
-def _op_forward(ctx, x0, x, integrand, h, nb_steps, inv_f):
-    if _graph_mode():
-        spec = _graph_spec(integrand, x)
-        if spec is not None:
-            return _graph_forward(ctx, spec, x0, x, h, nb_steps, inv_f, False)[0]
-    ctx.integrand, ctx.nb_steps, ctx.inv_f = integrand, nb_steps, inv_f
-    spec = mlp_spec(integrand)
-    ctx.spec = spec
-    # clones: callers mutate their tensors in place after the call (UMNNMAF.compute_ll clamps z, :150)
-    ctx.save_for_backward(x0.clone(), x.clone(), h)
-    ctx.use_hip = _use_hip(spec, x)       # decided on the calling thread (force_generic is thread-local; backward runs elsewhere)
-    if ctx.use_hip:
-        return hip_forward(spec, x0, x, h, nb_steps, inv_f)[0]
-    return aten_forward(integrand, x0, x, h, nb_steps, inv_f)
+def _save(ctx, spec, integrand, *tensors):
+    """What a quadrature Function keeps for its backward.  Recorded (Dynamo traces both methods: they may hold nothing but tensors and
+    plain values, and call nothing but torch.ops.umnn and ATen): the integrand as W[] + b[] behind ``tensors`` and its codes in
+    ``ctx.net``.  Eager: the spec (None: the ATen path, decided on the calling thread -- force_generic is thread-local, backward
+    runs elsewhere) and the integrand themselves."""
+    if spec is not None and _graph_mode():
+        W, b, ha, oa = spec_args(spec)
+        ctx.net, ctx.spec, ctx.integrand = (ha, oa, len(W)), None, None
+        ctx.save_for_backward(*tensors, *W, *b)
+    else:
+        ctx.net, ctx.spec, ctx.integrand = None, spec, integrand
+        ctx.save_for_backward(*tensors)
 
 
-def _op_backward(ctx, grad_output):
-    if getattr(ctx, "graph", None) is not None:
-        nig = ctx.needs_input_grad
-        dx0, dx, dh, dtheta = _graph_backward(ctx, grad_output, None, (nig[0], nig[1], nig[4], nig[3]))
-        return dx0, dx, dtheta, dh
-    x0, x, h = ctx.saved_tensors
-    integrand, nb_steps, inv_f, spec = ctx.integrand, ctx.nb_steps, ctx.inv_f, ctx.spec
-    if ctx.use_hip and _hip_backward_ok(spec, x, h):
-        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4], ctx.needs_input_grad[3])
-        dx0, dx, dh, dtheta = hip_backward(spec, x0, x, h, grad_output, None, nb_steps, need, inv_f=inv_f)
-        return dx0, dx, dtheta, dh
-    dtheta, dh = aten_backward(integrand, x0, x, h, grad_output, nb_steps, inv_f)
-    with torch.no_grad():
-        dx = integrand(x, h) * grad_output
-        dx0 = -integrand(x0, h) * grad_output
-    return dx0, dx, dtheta, dh.view(h.shape)
+def _saved(ctx, n):
+    """-> (the n tensors of ``_save``, its ``net`` for ``_launch_backward``)."""
+    saved = ctx.saved_tensors
+    if ctx.net is None:
+        return saved, None
+    ha, oa, L = ctx.net
+    return saved[:n], (list(saved[n:n + L]), list(saved[n + L:]), ha, oa)
+
+
+def _quad_forward(ctx, who, x0, x, integrand, h, nb_steps, inv_f, jac):
+    """forward of the four quadrature operators -> (F, f_x or None).  ``jac``: the operator owns its f_x output (HIP path only)."""
+    spec = _hip_spec(integrand, x)
+    if jac and spec is None:
+        raise RuntimeError(f"{who} needs an MLP integrand on a GPU")
+    ctx.nb_steps, ctx.inv_f, ctx.jac, ctx.x0_none = nb_steps, bool(inv_f), jac, x0 is None      # (x0 None: lower limit 0, nothing to save)
+    lims = () if x0 is None else (x0,)
+    if spec is not None and _graph_mode():
+        _save(ctx, spec, integrand, *lims, x, h)
+    else:       # clones: callers mutate their tensors in place after the call (UMNNMAF.compute_ll clamps z, :150)
+        _save(ctx, spec, integrand, *(t.clone() for t in lims), x.clone(), h)
+    if spec is None:
+        return aten_forward(integrand, x0, x, h, nb_steps, inv_f), None
+    return cc_forward(spec, x0, x, h, nb_steps, inv_f)
+
+
+def _quad_backward(ctx, gF, gfx, need):
+    """backward of the four -> (dx0, dx, dh, dtheta_flat) for ``need``, given in that order (each class maps its own argument
+    positions).  ``gfx`` is dropped for operators whose f_x output is not theirs."""
+    n = 2 if ctx.x0_none else 3
+    tensors, net = _saved(ctx, n)
+    x0, x, h = (None if ctx.x0_none else tensors[0]), tensors[n - 2], tensors[n - 1]
+    return _launch_backward(net, ctx.spec, ctx.integrand, x0, x, h, gF, gfx if ctx.jac else None, ctx.nb_steps, need, ctx.inv_f)
 
 
 class ParallelNeuralIntegral(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, x, integrand, flat_params, h, nb_steps=20, inv_f=False):
-        return _op_forward(ctx, x0, x, integrand, h, nb_steps, inv_f)
+        return _quad_forward(ctx, "ParallelNeuralIntegral", x0, x, integrand, h, nb_steps, inv_f, False)[0]
 
     @staticmethod
     @once_differentiable        # double backward (create_graph=True through the quadrature) raises instead of silently detaching
     def backward(ctx, grad_output):
-        dx0, dx, dtheta, dh = _op_backward(ctx, grad_output)
+        nig = ctx.needs_input_grad
+        dx0, dx, dh, dtheta = _quad_backward(ctx, grad_output, None, (nig[0], nig[1], nig[4], nig[3]))
         return dx0, dx, None, dtheta, dh, None, None
 
 
 class NeuralIntegral(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, x, integrand, flat_params, h, nb_steps=20):
-        return _op_forward(ctx, x0, x, integrand, h, nb_steps, False)
+        return _quad_forward(ctx, "NeuralIntegral", x0, x, integrand, h, nb_steps, False, False)[0]
 
     @staticmethod
-    @once_differentiable        # double backward (create_graph=True through the quadrature) raises instead of silently detaching
+    @once_differentiable
     def backward(ctx, grad_output):
-        dx0, dx, dtheta, dh = _op_backward(ctx, grad_output)
+        nig = ctx.needs_input_grad
+        dx0, dx, dh, dtheta = _quad_backward(ctx, grad_output, None, (nig[0], nig[1], nig[4], nig[3]))
         return dx0, dx, None, dtheta, dh, None
 
 
@@ -1002,33 +964,33 @@ class IntegralWithJacobian(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x0, x, integrand, flat_params, h, nb_steps):
-        if _graph_mode():
-            spec = _graph_spec(integrand, x)
-            if spec is None:
-                raise RuntimeError("IntegralWithJacobian needs an MLP integrand on a GPU")
-            return _graph_forward(ctx, spec, x0, x, h, nb_steps, False, True)
-        spec = mlp_spec(integrand)
-        if not _use_hip(spec, x):
-            raise RuntimeError("IntegralWithJacobian needs an MLP integrand on a GPU")
-        ctx.spec, ctx.nb_steps, ctx.integrand = spec, nb_steps, integrand
-        ctx.save_for_backward(x0.clone(), x.clone(), h)
-        F, fx, _ = hip_forward(spec, x0, x, h, nb_steps, False)
-        return F, fx
+        return _quad_forward(ctx, "IntegralWithJacobian", x0, x, integrand, h, nb_steps, False, True)
 
     @staticmethod
-    @once_differentiable        # double backward (create_graph=True through the quadrature) raises instead of silently detaching
+    @once_differentiable
     def backward(ctx, gF, gfx):
-        if getattr(ctx, "graph", None) is not None:
-            nig = ctx.needs_input_grad
-            dx0, dx, dh, dtheta = _graph_backward(ctx, gF, gfx, (nig[0], nig[1], nig[4], nig[3]))
-            return dx0, dx, None, dtheta, dh, None
-        x0, x, h = ctx.saved_tensors
-        if not _hip_backward_ok(ctx.spec, x, h):
-            dx0, dx, dh, dtheta = aten_backward_jac(ctx.integrand, x0, x, h, gF, gfx, ctx.nb_steps)
-            return dx0, dx, None, dtheta, dh, None
-        need = (ctx.needs_input_grad[0], ctx.needs_input_grad[1], ctx.needs_input_grad[4], ctx.needs_input_grad[3])
-        dx0, dx, dh, dtheta = hip_backward(ctx.spec, x0, x, h, gF, gfx, ctx.nb_steps, need)
+        nig = ctx.needs_input_grad
+        dx0, dx, dh, dtheta = _quad_backward(ctx, gF, gfx, (nig[0], nig[1], nig[4], nig[3]))
         return dx0, dx, None, dtheta, dh, None
+
+
+class IntegralWithJacobianParams(torch.autograd.Function):
+    """IntegralWithJacobian with the integrand's parameters passed one by one instead of as one flat tensor: no
+    ``torch.cat`` in the forward and no cat-backward (a narrow + copy per parameter) in the backward -- the gradients are
+    views into the kernel's flat d_theta.  Internal to the flow blocks; the public operators keep the reference's
+    ``flat_params`` signature."""
+
+    @staticmethod
+    def forward(ctx, x0, x, integrand, h, nb_steps, *params):
+        ctx.shapes = [p.shape for p in params]
+        return _quad_forward(ctx, "IntegralWithJacobianParams", x0, x, integrand, h, nb_steps, False, True)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gF, gfx):
+        nig = ctx.needs_input_grad
+        dx0, dx, dh, dtheta = _quad_backward(ctx, gF, gfx, (nig[0], nig[1], nig[3], any(nig[5:])))
+        return (dx0, dx, None, dh, None, *split_flat(dtheta, ctx.shapes, nig[5:]))
 
 
 class InverseNeuralIntegral(torch.autograd.Function):
@@ -1044,26 +1006,15 @@ class InverseNeuralIntegral(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, integrand, flat_params, h, nb_steps=20, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False):
         lo, hi = float(x_range[0]), float(x_range[1])
-        if _graph_mode():
-            spec = _graph_spec(integrand, t)
-            if spec is not None:
-                W, b = [l.weight for l in spec.linears], [l.bias for l in spec.linears]
-                x, fx, status = torch.ops.umnn.cc_solve(t, h, W, b, spec.hidden_act, spec.out_act, int(nb_steps), lo, hi,
-                                                        float(tol), int(max_iter))
-                ctx.graph = (spec.hidden_act, spec.out_act, int(nb_steps), len(W))
-                ctx.save_for_backward(x, h, fx, *W, *b)
-                if not return_info:
-                    return x
-                ctx.mark_non_differentiable(fx, status)
-                return x, fx, status
-        spec = mlp_spec(integrand)
-        ctx.integrand, ctx.nb_steps, ctx.spec = integrand, nb_steps, spec
-        ctx.use_hip = _use_hip(spec, t)
-        if ctx.use_hip:
-            x, fx, status = solve_integral(spec, t, h, nb_steps, lo, hi, tol, max_iter)
-        else:
+        spec = _hip_spec(integrand, t)
+        if spec is None:
             x, fx, status = aten_solve(integrand, h.detach(), t.detach(), nb_steps, lo, hi, tol, max_iter)
-        ctx.save_for_backward(x, h, fx)
+        elif _graph_mode():
+            x, fx, status = torch.ops.umnn.cc_solve(t, h, *spec_args(spec), int(nb_steps), lo, hi, float(tol), int(max_iter))
+        else:
+            x, fx, status = solve_integral(spec, t, h, nb_steps, lo, hi, tol, max_iter)
+        ctx.nb_steps = nb_steps
+        _save(ctx, spec, integrand, x, h, fx)
         if not return_info:
             return x
         ctx.mark_non_differentiable(fx, status)
@@ -1073,24 +1024,10 @@ class InverseNeuralIntegral(torch.autograd.Function):
     @once_differentiable
     def backward(ctx, g_x, *_unused):
         nig = ctx.needs_input_grad
-        if getattr(ctx, "graph", None) is not None:
-            ha, oa, nb_steps, L = ctx.graph
-            saved = ctx.saved_tensors
-            x, h, fx, W, b = saved[0], saved[1], saved[2], list(saved[3:3 + L]), list(saved[3 + L:])
-            g_t = g_x / fx
-            need = [False, False, bool(nig[3]), bool(nig[2])]
-            dh = dtheta = None
-            if need[2] or need[3]:
-                _, _, dh, dtheta = torch.ops.umnn.cc_backward(None, x, h, -g_t, None, W, b, ha, oa, nb_steps, need, False)
-            return (g_t if nig[0] else None, None, dtheta if need[3] else None, dh if need[2] else None,
-                    None, None, None, None, None)
-        x, h, fx = ctx.saved_tensors
+        (x, h, fx), net = _saved(ctx, 3)
         g_t = g_x / fx
         dh = dtheta = None
         if nig[2] or nig[3]:
-            if ctx.use_hip and _hip_backward_ok(ctx.spec, x, h):
-                _, _, dh, dtheta = hip_backward(ctx.spec, None, x, h, -g_t, None, ctx.nb_steps, (False, False, nig[3], nig[2]))
-            else:
-                dtheta, dh = aten_backward(ctx.integrand, torch.zeros_like(x), x, h, -g_t, ctx.nb_steps)
-                dh = dh.view(h.shape)
-        return (g_t if nig[0] else None, None, dtheta if nig[2] else None, dh if nig[3] else None, None, None, None, None, None)
+            _, _, dh, dtheta = _launch_backward(net, ctx.spec, ctx.integrand, None, x, h, -g_t, None, ctx.nb_steps,
+                                                (False, False, nig[3], nig[2]))
+        return (g_t if nig[0] else None, None, dtheta, dh, None, None, None, None, None)

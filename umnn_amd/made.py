@@ -24,18 +24,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-
-def _graph_mode():
-    return torch.compiler.is_compiling() or torch.jit.is_tracing()
-
-
-def _ptr(t):
-    """data_ptr() for a native call; raises under torch.jit.trace, which would record the output allocation and drop the launch."""
-    if torch._C._is_tracing():
-        from .integral import traced_native_call
-        raise traced_native_call()
-    return t.data_ptr()
-
+from ._common import _graph_mode, _stream, _address as _ptr
 
 _capture_state = threading.local()      # .cache_ok: a capture on THIS thread that tracks weight versions itself (GraphedLL)
 
@@ -232,7 +221,7 @@ def _fast_chain(a, layers, last_rows=None, out_dtype=None):
     from . import _lib
     lib = _lib.lib()
     raw = a.contiguous()
-    stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+    stream = _stream(a.device)
     with torch.cuda.device(a.device):
         for i, layer in enumerate(layers):
             last = i == len(layers) - 1
@@ -309,7 +298,7 @@ def _fused_chain(a, layers, last_rows=None, out_dtype=None, mode=1):
         net.W[i], net.b[i] = _ptr(frags), _ptr(bias)
     bf16 = out_dtype == torch.bfloat16
     with torch.cuda.device(a.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+        stream = _stream(a.device)
         if mode == 1:
             out = torch.empty(a.shape[0], net.widths[len(inner)], device=a.device, dtype=torch.bfloat16 if bf16 else torch.float32)
             _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), _ptr(a), a.shape[0], _ptr(out), 1 if bf16 else 0, 0,
@@ -341,7 +330,7 @@ def _layered_chain(a, layers, last_rows=None, out_dtype=None, a2=None):
     B = cur.shape[0]
     rt, fg = int(os.environ.get("UMNN_MADE_LINEAR_RT", "0")), int(os.environ.get("UMNN_MADE_LINEAR_G", "0"))
     with torch.cuda.device(a.device):
-        stream = ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)
+        stream = _stream(a.device)
         for i, layer in enumerate(layers):
             last = i == len(layers) - 1
             bf16 = last and out_dtype == torch.bfloat16
@@ -417,7 +406,7 @@ class _MadeTrainChain(torch.autograd.Function):
         g = g.contiguous()
         B = g.shape[0]
         grads = [None] * (2 * L)
-        stream = ctypes.c_void_p(torch.cuda.current_stream(g.device).cuda_stream)
+        stream = _stream(g.device)
         with torch.cuda.device(g.device):
             for i in range(L - 1, -1, -1):
                 last = i == L - 1
@@ -544,7 +533,7 @@ class MADE(nn.Module):
         from . import _lib
         lib = _lib.lib()
         raw = x.contiguous()
-        stream = ctypes.c_void_p(torch.cuda.current_stream(x.device).cuda_stream)
+        stream = _stream(x.device)
         with torch.cuda.device(x.device):
             for i, layer in enumerate(layers):
                 last = i == len(layers) - 1

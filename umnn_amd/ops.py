@@ -33,7 +33,6 @@ from torch import Tensor
 from . import _lib
 from . import integral as _I
 from .nets import spec_from_tensors
-from .quadrature import device_tables
 
 _FLOATS = (torch.float32, torch.bfloat16, torch.float16)
 _F32 = (torch.float32,)
@@ -157,8 +156,8 @@ def _empty(like, dtype=None):
 
 
 def _param_grads(dtheta, W, b, need_W, need_b):
-    """Flat d_theta -> ([dW_l], [db_l]) views (integral._split), None where not needed."""
-    grads = _I._split(dtheta, len(W), list(W) + list(b), [n for pair in zip(need_W, need_b) for n in pair])
+    """Flat d_theta -> ([dW_l], [db_l]) views (``integral.split_flat``), None where not needed."""
+    grads = _I.split_flat(dtheta, [p.shape for pair in zip(W, b) for p in pair], [n for pair in zip(need_W, need_b) for n in pair])
     return grads[0::2], grads[1::2]
 
 
@@ -199,74 +198,33 @@ def _cc_forward_backward(ctx, gF, gfx):
 cc_forward.register_autograd(_cc_forward_backward, setup_context=_cc_forward_setup)
 
 
-def _mlp(params, hidden_act, out_act, rows):
-    a = rows
-    L = len(params) // 2
-    for l in range(L):
-        a = F.linear(a, params[2 * l], params[2 * l + 1])
-        if l + 1 < L:
-            a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
-    return F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)
+def pure_mlp(W, b, hidden_act, out_act):
+    """The integrand the ops get -- W[], b[] and the activation codes, never a module -- as ``integral.aten_vjp`` takes it:
+    (f(params, x, h) -> [B,d], params in parameters() order), f the MLP on the rows [x_i, h_{0,i}, ..., h_{E-1,i}]
+    (nets.IntegrandNetwork.rows)."""
+    L = len(W)
 
+    def f(params, x, h):
+        B, d = x.shape
+        a = torch.cat((x, h), 1).view(B, -1, d).transpose(1, 2).reshape(B * d, -1)
+        for l in range(L):
+            a = F.linear(a, params[2 * l], params[2 * l + 1])
+            if l + 1 < L:
+                a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
+        return (F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)).view(B, d)
 
-def _integrand(params, hidden_act, out_act, x, h):
-    """f(x; h) [B,d] of the integrand MLP on the rows [x_i, h_{0,i}, ..., h_{E-1,i}] (nets.IntegrandNetwork.rows)."""
-    B, d = x.shape
-    rows = torch.cat((x, h), 1).view(B, -1, d).transpose(1, 2).reshape(B * d, -1)
-    return _mlp(params, hidden_act, out_act, rows).view(B, d)
-
-
-def aten_backward(W, b, hidden_act, out_act, x0, x, h, g, g_fx, nb_steps, inv_f):
-    """The ATen backward for nets the HIP backward turns away, for an integrand given as tensors: the same quadrature VJP and
-    Leibniz terms as integral.py's ``aten_backward`` / ``_op_backward`` and, with ``g_fx``, the f(x;h) term of
-    ``aten_backward_jac``.  A second implementation of that arithmetic, because it runs inside an op kernel, below autograd,
-    where torch.autograd.grad records nothing: the VJPs are torch.func.vjp.  (tests/test_torch_ops.py holds the two to the
-    same values.)  -> (dx0, dx, dh, dtheta_flat)."""
-    params = [p.detach() for pair in zip(W, b) for p in pair]
-    x0 = torch.zeros_like(x) if x0 is None else x0
-    w, s = device_tables(nb_steps, x.device)
-    w, u = w.to(x.dtype), s.to(x.dtype) + 1
-    span = x - x0
-    cot = g * span / 2
-    B = x.shape[0]
-    g_params = [torch.zeros_like(p) for p in params]
-    dh = torch.zeros_like(h)
-    for a, e in _I._node_chunks(nb_steps, B, h.shape[1] + x.shape[1]):
-        t, h_rep = _I._eval_chunk(None, x0, span, h, u[a:e])
-
-        def f_nodes(ps, hr, t=t):
-            f = _integrand(ps, hidden_act, out_act, t, hr)
-            return 1 / f if inv_f else f
-
-        f, vjp = torch.func.vjp(f_nodes, params, h_rep)
-        gp, gh = vjp((cot.unsqueeze(0) * w[a:e].view(-1, 1, 1)).reshape(f.shape))
-        for acc, gr in zip(g_params, gp):
-            acc += gr
-        dh += gh.view(e - a, B, -1).sum(0)
-    fx, vjp = torch.func.vjp(lambda ps, xx, hh: _integrand(ps, hidden_act, out_act, xx, hh), params, x, h)
-    dx = fx * g
-    if g_fx is not None:
-        gp, gx, gh = vjp(g_fx)
-        dx, dh = dx + gx, dh + gh
-        g_params = [a + c for a, c in zip(g_params, gp)]
-    dx0 = -_integrand(params, hidden_act, out_act, x0, h) * g
-    _I._state.path = _I._last_backward["path"] = "aten"
-    return dx0, dx, dh, torch.cat([p.reshape(-1) for p in g_params])
-
-
-def _backward(spec, W, b, x0, x, h, g, g_fx, nb_steps, need, inv_f):
-    if _I._hip_backward_ok(spec, x, h):
-        return _I.hip_backward(spec, x0, x, h, g, g_fx, nb_steps, tuple(need), inv_f=inv_f)
-    return aten_backward(W, b, spec.hidden_act, spec.out_act, x0, x, h, g, g_fx, nb_steps, inv_f)
+    return f, [p.detach() for pair in zip(W, b) for p in pair]
 
 
 @torch.library.custom_op("umnn::cc_backward", mutates_args=(), device_types="cuda")
 def cc_backward(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, g_fx: Optional[Tensor], W: List[Tensor], b: List[Tensor],
                 hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """HIP backward, or -- for the nets ``integral._hip_backward_ok`` turns away, decided here at run time -- the ATen one."""
+    """``integral.quadrature_backward`` for an integrand given as tensors: the HIP kernels, or -- for the nets
+    ``integral._hip_backward_ok`` turns away, decided here at run time -- the one ATen backward, on ``pure_mlp``."""
     _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
     need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
-    out = _backward(spec_from_tensors(W, b, hidden_act, out_act), W, b, x0, x, h, g, g_fx, nb_steps, need, inv_f)
+    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp(W, b, hidden_act, out_act), x0, x, h, g, g_fx,
+                                 nb_steps, need, inv_f)
     like = (x, x, h, W[0])
     return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
                  for i, (t, n, l) in enumerate(zip(out, need, like)))
@@ -380,17 +338,13 @@ flow_block.register_autograd(_flow_block_backward, setup_context=_flow_block_set
 def flow_block_backward(x: Tensor, h: Tensor, scaling: Tensor, fx: Tensor, gz: Tensor, glj: Tensor, W: List[Tensor],
                         b: List[Tensor], hidden_act: int, out_act: int, nb_steps: int, reverse_z: bool,
                         need: List[bool]) -> tuple[Tensor, Tensor, Tensor]:
-    """``FlowBlockTransform.backward``: cotangents of F and f_x (one launch), the quadrature backward, the h_0 term in d_h."""
+    """``FlowBlockTransform.backward`` without the z_2 hand-off (``integral.flow_block_vjp``)."""
     _check_flow_block_backward(x, h, scaling, fx, gz, glj, W, b, hidden_act, out_act, nb_steps, reverse_z, need)
-    B, d = x.shape
-    gF, gfx = _I.hip_flow_block_cotangents(gz.contiguous(), glj.contiguous(), fx.contiguous(), scaling.contiguous(), reverse_z)
-    _, dx, dh, dtheta = _backward(spec_from_tensors(W, b, hidden_act, out_act), W, b, None, x, h, gF, gfx, nb_steps,
-                                  [False, bool(need[0]), bool(need[1]), bool(need[2])], False)
-    if need[1]:
-        dh.view(B, -1, d)[:, 0, :].add_(gF)            # z carries h_0 = embedding row 0 (UMNNMAF.py:80)
+    out = _I.flow_block_vjp(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp(W, b, hidden_act, out_act), x, h, fx.contiguous(),
+                            scaling.contiguous(), gz.contiguous(), glj.contiguous(), nb_steps, reverse_z, [bool(n) for n in need])
     like = (x, h, W[0])
     return tuple(t.contiguous() if n else _empty(l, torch.float32 if i == 2 else None)
-                 for i, (t, n, l) in enumerate(zip((dx, dh, dtheta), need, like)))
+                 for i, (t, n, l) in enumerate(zip(out, need, like)))
 
 
 @flow_block_backward.register_fake
@@ -462,6 +416,4 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
 OPS = ("cc_forward", "cc_backward", "cc_solve", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
-def spec_args(spec):
-    """MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it."""
-    return [l.weight for l in spec.linears], [l.bias for l in spec.linears], spec.hidden_act, spec.out_act
+spec_args = _I.spec_args       # MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it
