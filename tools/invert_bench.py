@@ -5,7 +5,7 @@ n = 100) -- each with default-initialised weights and again with the MADE weight
 stronger coupling between the dimensions, more Jacobi sweeps) --, and ``MonotonicNN.inverse`` at 65 536 x 1 with the 3-100^3-1 net
 of the g5 fixtures.  The jacobi rows carry the sweep count and the largest evaluation count of every sweep.
 
-    python tools/invert_bench.py [--repeats 5] [--warmup 1] [--root TREE] [--out FILE.json] [--only c3,mnist,c3_made3,mnist_made3,monotonic]
+    python tools/invert_bench.py [--repeats 5] [--warmup 1] [--root TREE] [--out FILE.json] [--only c3,mnist,c3_made3,mnist_made3,monotonic,toy]
                                  [--methods bracket,newton,jacobi]
 
 Device-synchronised wall time of whole calls (conditioner passes included), ``--warmup`` untimed calls of every method first, then
@@ -17,7 +17,12 @@ two fixed sweep counts (``adj_tol=0``, ``max_adj_sweeps`` 2 and 6: their differe
 against -- the one row a tree without ``inverse`` (``--root``) also gives; ``--methods`` selects rows by name there (a kernel trace
 of the sweeps alone: ``--grad --methods rsample_backward_6_sweeps --repeats 1 --warmup 0``: seven launches of the main backward
 kernel, one parameter reduction).  ``--root`` imports the package from another checkout (a tree without the Newton method -- the parent of this change --
-times the bracket search only), which is how the same-box comparison against an older build is taken.  Per-launch kernel time is
+times the bracket search only), which is how the same-box comparison against an older build is taken.  ``--graph`` times eager
+``invert`` against ``umnn_amd.GraphedSampler`` replays (rows ``newton`` / ``newton_graph`` and ``jacobi`` / ``jacobi_graph``, alternating
+in every round; given noise copied into the static buffer, so both sides solve the same z) at the C3 block, the MNIST-shaped block and
+the 2-D toy flow of bench.py (case ``toy``: 4096 x 2, one block); the jacobi pair runs ``sweep_tol=0`` with ``max_sweeps`` set to the
+sweep count eager jacobi needed with its default stop rule (row field ``sweeps``), ``capture_ms`` is the one-time cost of building the
+sampler (warm-up + capture).  Per-launch kernel time is
 a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/invert_bench.py --repeats 1 --only c3
 """
 import argparse
@@ -35,11 +40,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     ap.add_argument("--out", default=None)
-    ap.add_argument("--only", default="c3,mnist,c3_made3,mnist_made3,monotonic")
+    ap.add_argument("--only", default=ap_default_only)
     ap.add_argument("--methods", default=ap_default_methods)
     ap.add_argument("--label", default="")
     ap.add_argument("--adj-tol", type=float, default=None, help="--grad: adj_tol of the rsample_backward row (default: the method's own)")
     ap.add_argument("--grad", action="store_true", help="time rsample + backward and the adjoint sweeps instead of the solves")
+    ap.add_argument("--graph", action="store_true", help="time eager invert against GraphedSampler replays (newton and fixed-sweep jacobi)")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
@@ -85,6 +91,10 @@ def main():
               "mnist": dict(d=784, hd=[100, 50, 50, 50, 50], he=[1024] * 3, E=30, n=100, B=100)}
     if args.grad:
         results += grad_mode(args, umnn_amd, torch, dev, shapes, only, measure)
+        only = set()
+    if args.graph:
+        results += graph_mode(args, umnn_amd, torch, dev, shapes, only if args.only != ap_default_only else {"c3", "mnist", "toy"},
+                              methods, measure, sync_time)
         only = set()
     with torch.no_grad():
         for case, c in [(name + tag, dict(c, made_gain=gain)) for name, c in shapes.items() for tag, gain in (("", 1.), ("_made3", 3.))]:
@@ -146,6 +156,46 @@ def main():
 
 
 ap_default_methods = "bracket,newton,jacobi"
+ap_default_only = "c3,mnist,c3_made3,mnist_made3,monotonic"
+
+
+def graph_mode(args, umnn_amd, torch, dev, shapes, only, methods, measure, sync_time):
+    """The ``--graph`` rows: eager ``invert`` and the replay of a ``GraphedSampler`` on the same z, per method."""
+    results = []
+    shapes = dict(shapes, toy=dict(d=2, hd=[100] * 4, he=[100] * 4, E=10, n=50, B=4096))
+    with torch.no_grad():
+        for case, c in shapes.items():
+            if case not in only:
+                continue
+            torch.manual_seed(0)
+            flow = umnn_amd.UMNNMAFFlow(nb_flow=1, nb_in=c["d"], hidden_derivative=c["hd"], hidden_embedding=c["he"],
+                                        embedding_s=c["E"], nb_steps=c["n"], solver="CCParallel").to(dev).eval()
+            x = torch.randn(c["B"], c["d"], device=dev)
+            z = flow(x)
+            fns, meta = {}, {}
+            if "newton" in methods:
+                ms, sampler = sync_time(lambda: umnn_amd.GraphedSampler(flow, c["B"], method="newton"))
+                meta["newton_graph"] = dict(capture_ms=ms)
+                fns["newton"] = lambda: flow.invert(z, method="newton")
+                fns["newton_graph"] = lambda sampler=sampler: sampler(z=z)
+            if "jacobi" in methods:
+                _, info = flow.invert(z, method="jacobi", return_info=True)
+                K = max(info["sweeps"])
+                ms, jsampler = sync_time(lambda: umnn_amd.GraphedSampler(flow, c["B"], method="jacobi", sweep_tol=0, max_sweeps=K))
+                meta["jacobi"] = dict(sweeps=K)
+                meta["jacobi_graph"] = dict(sweeps=K, capture_ms=ms)
+                fns["jacobi"] = lambda K=K: flow.invert(z, method="jacobi", sweep_tol=0, max_sweeps=K)
+                fns["jacobi_graph"] = lambda jsampler=jsampler: jsampler(z=z)
+
+            def extra(k, outs, x=x, meta=meta):
+                out = dict(max_abs_err_x=float((outs[k] - x).abs().max()), **meta.get(k, {}))
+                if k == "jacobi_graph":
+                    out["last_move"] = float(jsampler.last_move)
+                return out
+            results += measure(case, fns, extra)
+            del flow, fns
+            torch.cuda.empty_cache()
+    return results
 
 
 def grad_mode(args, umnn_amd, torch, dev, shapes, only, measure):

@@ -27,7 +27,7 @@ from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobi
 from .inverse import FlowBlockInverse
 from .nets import compute_lipschitz_linear
 from .quadrature import compute_cc_weights
-from .graphs import GraphedLL, GraphedTrainStep
+from .graphs import GraphedLL, GraphedSampler, GraphedTrainStep
 from . import ops  # noqa: F401  (registers the torch.ops.umnn custom ops; loads no library)
 from ._lib import set_forward_precision, get_forward_precision, set_backward_precision, get_backward_precision
 from ._lib import SOLVE_EVALS_MASK, SOLVE_CLAMPED, SOLVE_CAPPED, SOLVE_NONFINITE
@@ -64,7 +64,7 @@ def set_precision(name):
 
 __all__ = ["UMNNMAFFlow", "UMNNMAF", "EmbeddingNetwork", "IntegrandNetwork", "ListModule", "MonotonicNN",
            "IntegrandNN", "MADE", "ConditionnalMADE", "MaskedLinear", "NeuralIntegral", "ParallelNeuralIntegral",
-           "IntegralWithJacobian", "integrate", "compute_cc_weights", "path_taken", "GraphedLL", "GraphedTrainStep",
+           "IntegralWithJacobian", "integrate", "compute_cc_weights", "path_taken", "GraphedLL", "GraphedSampler", "GraphedTrainStep",
            "set_precision", "invalidate_caches", "set_made_fast_path", "get_made_fast_path", "set_forward_precision", "get_forward_precision", "set_backward_precision", "get_backward_precision",
            "set_backward_wide", "compute_lipschitz_linear", "backward_path_taken", "set_made_fused",
            "InverseNeuralIntegral", "FlowBlockInverse", "SOLVE_EVALS_MASK", "SOLVE_CLAMPED", "SOLVE_CAPPED", "SOLVE_NONFINITE"]

@@ -63,13 +63,60 @@ class EmbeddingNetwork(nn.Module):
             self.m_embeding = self.made.raw(x_made, out_dtype=self.embedding_dtype)
         return self.m_embeding
 
+    def graph_embedding(self, x_made, context, weights):
+        """``make_embeding`` for the recorded sampling loops: the conditioner's graph-mode composition on masked weights the caller
+        formed once (``made.graph_weights()``); writes no attribute."""
+        if isinstance(self.made, ConditionnalMADE):
+            return self.made.raw_graph(x_made, context, weights, out_dtype=self.embedding_dtype)
+        return self.made.raw_graph(x_made, weights, out_dtype=self.embedding_dtype)
+
     def forward(self, x_t):
         return self.parallel_nets.forward(x_t, self.m_embeding)
 
 
+def _recorded_blocks(cls, flow, z, method, sweep_tol, max_sweeps):
+    """The blocks of ``flow`` when this ``invert`` call, met while torch.compile / torch.export trace, is one the graph can hold:
+    "newton", or "jacobi" with a fixed sweep count (``sweep_tol`` = 0 and ``max_sweeps`` given: no host read decides anything), fp32
+    z and every block on the HIP path (``integral._hip_spec``).  None otherwise: the caller then makes today's eager call."""
+    if method == "bracket" or (method == "jacobi" and (sweep_tol != 0 or max_sweeps is None)):
+        return None
+    blocks = [flow] if cls is UMNNMAF else [flow.nets[i] for i in range(len(flow.nets))]
+    if len(blocks) == 0 or z.dim() != 2 or z.dtype != torch.float32:
+        return None
+    for blk in blocks:
+        if blk.solver not in _SOLVERS or blk.nb_steps < 1 or _I._hip_spec(blk.net.parallel_nets, z, True) is None:
+            return None
+    return blocks
+
+
+def _invert_recorded(cls, blocks, z, context, method, tol, max_iter, max_sweeps, return_info):
+    """``invert`` as torch.compile / torch.export record it: the block walk of ``_invert_newton`` / ``_invert_jacobi`` on
+    ``UMNNMAF._invert_block_recorded``.  info (jacobi): "sweeps" = K, the last sweep's "status" and "last_move" = max |x_K - x_{K-1}| /
+    max(1, |x_K|), a 0-dim device tensor the caller may test afterwards (NaN when a row ended non-finite) -- per block, as lists
+    over the blocks in flow order for a UMNNMAFFlow."""
+    stack = cls is not UMNNMAF
+    K = None if method == "newton" else int(max_sweeps)
+    if K is not None and K < 1:
+        raise ValueError("umnn_amd: invert(method='jacobi') needs max_sweeps >= 1")
+    status, moves = [], []
+    with torch.no_grad():
+        if stack:
+            z = torch.flip(z, [1])
+        for blk in reversed(blocks):
+            z, st, mv = blk._invert_block_recorded(torch.flip(z, [1]) if stack else z, context, tol, max_iter, K)
+            status.insert(0, st)
+            moves.insert(0, mv)
+    if not return_info:
+        return z
+    if stack:
+        return z, {"sweeps": [K] * len(blocks), "status": status, "last_move": moves}
+    return z, {"sweeps": K, "status": status[0], "last_move": moves[0]}
+
+
 def _invert_dispatch(cls, flow, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info):
     """``cls.invert`` of UMNNMAF and UMNNMAFFlow: checks the options and runs ``cls._invert`` / ``_invert_newton`` / ``_invert_jacobi``.
-    Eager only: compiled callers get an eager call, torch.jit.trace raises."""
+    While torch.compile / torch.export trace, "newton" and fixed-sweep "jacobi" on the HIP path are recorded (``_invert_recorded``);
+    every other call there is an eager call the graph breaks at, and torch.jit.trace raises."""
     if method not in ("bracket", "newton", "jacobi"):
         raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
     if torch.jit.is_tracing():
@@ -77,6 +124,10 @@ def _invert_dispatch(cls, flow, z, iter, context, method, tol, max_iter, sweep_t
                            "call it eagerly")
     if return_info and method != "jacobi":
         raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
+    if torch.compiler.is_compiling():
+        blocks = _recorded_blocks(cls, flow, z, method, sweep_tol, max_sweeps)
+        if blocks is not None:
+            return _invert_recorded(cls, blocks, z, context, method, tol, max_iter, max_sweeps, return_info)
     fn, args = {"bracket": (cls._invert, (z, iter, context)), "newton": (cls._invert_newton, (z, context, tol, max_iter)),
                 "jacobi": (cls._invert_jacobi, (z, context, tol, max_iter, sweep_tol, max_sweeps, return_info))}[method]
     if torch.compiler.is_compiling():
@@ -230,8 +281,11 @@ class UMNNMAF(nn.Module):
     def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None,
                return_info=False):
         """Dimension-by-dimension bracket search: 10 candidates per round on [left,right] (starting at +-50), keep
-        the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232).  Eager only:
-        compiled callers get an eager call; under torch.jit.trace it raises.
+        the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232).  Under torch.compile /
+        torch.export the search is an eager call (a graph break); under torch.jit.trace ``invert`` raises.  On the HIP path
+        ``method="newton"`` and ``method="jacobi"`` with ``sweep_tol=0`` and an explicit ``max_sweeps`` ARE recorded
+        (``_invert_block_recorded``: newton unrolls d conditioner + solve steps at trace time -- for small d; wide blocks record jacobi,
+        whose ``return_info`` there is {"sweeps": K, "status", "last_move": a 0-dim device tensor}).
         ``method="newton"`` (an extension; ``iter`` is ignored): the same dimension-by-dimension structure with the safeguarded Newton
         solve of ``umnn_cc_solve`` on [-50, 50] in place of the search -- residual to ``tol * max(1, |z_j|)``, at most ``max_iter``
         quadratures per dimension, typically four.
@@ -303,7 +357,7 @@ class UMNNMAF(nn.Module):
                 x_inv[:, j] = x_j[:, 0]
         return x_inv
 
-    def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False):
+    def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False, moves=None):
         """``invert(method="jacobi")``: x <- 0; repeat { h <- conditioner(x); x_i <- solve_i(z_i; h) for EVERY i }.  The conditioner is
         autoregressive, so dimension i is final once x_<i are: after sweep t the first t dimensions hold the sequential answer, d sweeps
         reproduce ``method="newton"``, and a fixed point is the inverse.  HIP path: per sweep one conditioner pass and ONE launch over the
@@ -311,7 +365,9 @@ class UMNNMAF(nn.Module):
         and nets the solve kernels do not cover run the same sweeps through ``integral.newton_solve`` over [B, d].
         Stops when max |x_new - x| / max(1, |x_new|) <= ``sweep_tol`` (one scalar device-to-host read per sweep; ``sweep_tol`` = 0: no
         test and no read), in any case after ``max_sweeps`` sweeps (default d).  -> (x, info); info (``want_info``) = {"sweeps",
-        "converged": the test was met or d sweeps ran, "status": the last sweep's status words [B,d], "max_evals": per sweep}."""
+        "converged": the test was met or d sweeps ran, "status": the last sweep's status words [B,d], "max_evals": per sweep}.
+        ``moves`` (a list; graphs.GraphedSampler): gets this block's max |x_K - x_{K-1}| / max(1, |x_K|) of the last sweep appended,
+        as a 0-dim device tensor, without a host read."""
         B, d = z.shape
         dev = z.device
         integrand = self.net.parallel_nets
@@ -325,7 +381,7 @@ class UMNNMAF(nn.Module):
             z = z.contiguous()
             x = torch.zeros(B, d, device=dev, dtype=z.dtype)
             scaling = self.scaling.detach().float().contiguous()
-            sweeps, met, status, evals = 0, False, None, []
+            sweeps, met, status, evals, x_prev = 0, False, None, [], x
             for sweep in range(max_sweeps):
                 h = self.net.make_embeding(x, context)
                 x_init = x if sweep > 0 else None
@@ -352,14 +408,44 @@ class UMNNMAF(nn.Module):
                 if sweep_tol > 0:
                     moved = (x_new - x).abs() > sweep_tol * x_new.abs().clamp(min=1.)      # (a NaN row never counts as moving)
                     met = not bool(moved.any())
-                x = x_new
+                x_prev, x = x, x_new
                 if met:
                     break
+            if moves is not None:
+                moves.append(((x - x_prev).abs() / x.abs().clamp(min=1.)).max())
         info = None
         if want_info:
             info = {"sweeps": sweeps, "converged": bool(met or sweeps >= d), "status": status,
                     "max_evals": [int(e) for e in torch.stack(evals).tolist()]}
         return x, info
+
+    def _invert_block_recorded(self, z, context, tol, max_iter, sweeps):
+        """One block of ``invert`` as a graph records it (caller: ``_invert_recorded``, under no_grad) -> (x, status, last_move).
+        The conditioner runs in its graph-mode composition with every mask product formed ONCE for the whole block inversion; scale
+        and offset are folded into the target by torch ops, t = z exp(-s) - h[:, 0, :], as ``MonotonicNN.inverse`` does.
+        ``sweeps`` None ("newton"): input_size steps of conditioner + ``umnn::cc_solve`` on the [B, 1] column -- the loop unrolls at
+        trace time, so this is for small d; wide blocks record "jacobi".  ``sweeps`` = K ("jacobi"): K x (conditioner +
+        ``umnn::cc_solve_block`` warm-started from the previous sweep), no test between them."""
+        B = z.shape[0]
+        d = self.input_size
+        net_args = _I.spec_args(_I._hip_spec(self.net.parallel_nets, z, True))
+        weights = self.net.made.graph_weights()
+        n, tol, max_iter = int(self.nb_steps), float(tol), int(max_iter)
+        target = z * torch.exp(-self.scaling.detach().float()).unsqueeze(0)
+        x = torch.zeros_like(z)
+        if sweeps is None:
+            for j in range(d):
+                h_j = self.net.graph_embedding(x, context, weights).view(B, -1, d)[:, :, j]       # [B,E]; row 0 doubles as the offset
+                x_j = torch.ops.umnn.cc_solve(target[:, j:j + 1] - h_j[:, :1].float(), h_j, *net_args, n, -50., 50., tol, max_iter)[0]
+                x = torch.cat((x[:, :j], x_j, x[:, j + 1:]), 1)
+            return x, None, None
+        x_prev, status = x, None
+        for sweep in range(sweeps):
+            h = self.net.graph_embedding(x, context, weights)
+            t = target - h.view(B, -1, d)[:, 0, :].float()
+            x_new, _, status = torch.ops.umnn.cc_solve_block(t, h, x if sweep > 0 else None, *net_args, n, -50., 50., tol, max_iter)
+            x_prev, x = x, x_new
+        return x, status, ((x - x_prev).abs() / x.abs().clamp(min=1.)).max()
 
     def inverse(self, z, context=None, method="newton", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, adj_tol=1e-6,
                 max_adj_sweeps=None, return_info=False):
@@ -494,7 +580,9 @@ class UMNNMAFFlow(nn.Module):
         """Sampling direction, block by block.  ``method="bracket"`` (default): the reference's search, ``iter`` rounds.
         ``method="newton"``: the in-kernel Newton solve (``UMNNMAF.invert``), exactly nb_flow x d solve launches; ``iter`` is ignored.
         ``method="jacobi"``: the Jacobi iteration of ``UMNNMAF.invert`` in every block, one solve launch per sweep;
-        ``return_info=True`` -> (x, info) with info's entries as lists over the blocks in flow order."""
+        ``return_info=True`` -> (x, info) with info's entries as lists over the blocks in flow order.
+        torch.compile / torch.export record "newton" and fixed-sweep "jacobi" (``sweep_tol=0``, ``max_sweeps=K``) on the HIP path, see
+        ``UMNNMAF.invert``; everything else stays an eager call there."""
         return _invert_dispatch(UMNNMAFFlow, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info)
 
     def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
@@ -503,12 +591,12 @@ class UMNNMAFFlow(nn.Module):
             z = self.nets[i].invert(torch.flip(z, [1]), context=context, method="newton", tol=tol, max_iter=max_iter)
         return z
 
-    def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False):
+    def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False, moves=None):
         nb = len(self.nets)
         infos = [None] * nb
         z = torch.flip(z, [1])
         for i in range(nb - 1, -1, -1):
-            z, infos[i] = self.nets[i]._invert_jacobi(torch.flip(z, [1]), context, tol, max_iter, sweep_tol, max_sweeps, want_info)
+            z, infos[i] = self.nets[i]._invert_jacobi(torch.flip(z, [1]), context, tol, max_iter, sweep_tol, max_sweeps, want_info, moves)
         info = {k: [inf[k] for inf in infos] for k in ("sweeps", "converged", "status", "max_evals")} if want_info else None
         return z, info
 
@@ -529,7 +617,8 @@ class UMNNMAFFlow(nn.Module):
         return z.to(dev)
 
     def sample(self, n, context=None, generator=None, **solve_opts):
-        """n samples x = T^-1(z), z ~ N(0, I), without a graph: ``invert`` (method "newton" unless ``solve_opts`` says otherwise)."""
+        """n samples x = T^-1(z), z ~ N(0, I), without a graph: ``invert`` (method "newton" unless ``solve_opts`` says otherwise).
+        Recorded by torch.compile / torch.export where ``invert`` is, when no generator is given."""
         solve_opts.setdefault("method", "newton")
         with torch.no_grad():
             return self.invert(self._base_noise(n, generator), context=context, **solve_opts)

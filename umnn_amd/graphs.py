@@ -3,7 +3,7 @@
 ``GraphedLL(model, x_example)`` records ``model.compute_ll`` once on static buffers (``torch.cuda.CUDAGraph``; the
 quadrature launches of libumnn_cc go to torch's current stream, so they are captured like any ATen kernel) and replays
 it per call.  Inference only (autograd off); shapes are fixed at capture.  For the large configurations the step is one
-long kernel per block and a graph buys nothing."""
+long kernel per block and a graph buys nothing.  ``GraphedSampler`` does the same for the sampling direction (``invert``)."""
 import torch
 
 
@@ -87,6 +87,108 @@ class GraphedLL:
             self._capture()
         if x is not None:
             self.x.copy_(x)
+        if context is not None:
+            self.context.copy_(context)
+        self.graph.replay()
+        return self.out
+
+
+class GraphedSampler:
+    """The sampling direction as one hipGraph: ``GraphedSampler(flow, n, context=None, method="newton", warmup=1, **solve_opts)``
+    records ``flow.invert(z, method=...)`` -- a ``UMNNMAFFlow`` or a single ``UMNNMAF`` block -- on a static [n, d] noise buffer.
+
+        sampler = umnn_amd.GraphedSampler(flow, n)
+        x = sampler()                   # fresh N(0, I) noise drawn into the buffer outside the graph, then one replay
+        x = sampler(z=z, context=c)     # given noise / context copied in, then one replay
+
+    The returned tensor is the captured output, overwritten by the next call.  Sampling is the most launch-bound thing the package
+    does -- per dimension a conditioner-row GEMM chain, a strided copy and a solve launch, d times per block -- and the replay
+    removes the host's share of it (measured: profiles/graph_sampling/; where the solve launches themselves fill the time the
+    graph buys little).
+
+    ``method="newton"`` (``tol``, ``max_iter``) or ``method="jacobi"`` with ``sweep_tol=0`` and an explicit ``max_sweeps=K`` (else
+    ValueError: the stop test of the sweeps is a device-to-host read, which a graph cannot hold); ``sampler.last_move`` is then the
+    0-dim device tensor max |x_K - x_{K-1}| / max(1, |x_K|) over the blocks, for the caller to test afterwards.  ``"bracket"`` is
+    refused.  Nets the in-kernel solve does not cover are refused as well (their Newton loop is driven from the host).
+
+    Like ``GraphedLL``: at least one eager warm-up (it fills the conditioner's caches, the quadrature tables and the overflow flag
+    ring with kernels that really ran), the conditioner's cached weights are baked in, and a parameter or buffer whose version
+    moved re-captures; ``refresh()`` after writes that bypass versioning.  The graph is a linear chain on one stream.
+    The fp16-piece overflow protocol is captured as it stands: every solve launch is followed by its queued bf16 pass, which idles
+    unless rows overflowed.  The generation numbers of the flag words are constants of the graph, so a replay AFTER one in which
+    rows overflowed runs those queued passes without need -- slower, never wrong."""
+
+    def __init__(self, flow, n, context=None, method="newton", warmup=1, **solve_opts):
+        from . import flow as _flow
+        if method not in ("newton", "jacobi"):
+            raise ValueError(f"umnn_amd: GraphedSampler records method 'newton' or 'jacobi', not {method!r}")
+        opts = dict(tol=1e-6, max_iter=64)
+        if method == "jacobi":
+            opts.update(sweep_tol=1e-6, max_sweeps=None)
+        unknown = set(solve_opts) - set(opts)
+        if unknown:
+            raise ValueError(f"umnn_amd: GraphedSampler(method={method!r}) has no option {sorted(unknown)}")
+        opts.update(solve_opts)
+        if method == "jacobi" and (opts["sweep_tol"] != 0 or opts["max_sweeps"] is None or int(opts["max_sweeps"]) < 1):
+            raise ValueError("umnn_amd: GraphedSampler(method='jacobi') needs sweep_tol=0 and max_sweeps=K >= 1 (a fixed sweep count; "
+                             "check sampler.last_move afterwards)")
+        blk = flow if isinstance(flow, _flow.UMNNMAF) else flow.nets[0]
+        dev = blk.scaling.device
+        assert dev.type == "cuda", "hipGraph capture needs the model on the device"
+        self.model, self.method, self.opts = flow, method, opts
+        self.z = torch.randn(int(n), blk.input_size, device=dev, dtype=torch.float32)
+        self.context = context.to(dev).clone() if context is not None else None
+        self.warmup = warmup
+        self.captures = 0
+        self.last_move = None
+        self._capture()
+
+    def _versions(self):
+        return tuple(t._version for t in self.model.parameters()) + tuple(t._version for t in self.model.buffers())
+
+    def _run(self):
+        o = self.opts
+        if self.method == "newton":
+            return self.model.invert(self.z, context=self.context, method="newton", tol=o["tol"], max_iter=o["max_iter"]), None
+        moves = []
+        x, _ = self.model._invert_jacobi(self.z, self.context, o["tol"], o["max_iter"], 0., int(o["max_sweeps"]), False, moves)
+        return x, torch.stack(moves).max()
+
+    def _capture(self):
+        from . import integral, made
+        dev = self.z.device
+        with torch.no_grad():
+            integral._state.host_solve = False
+            side = torch.cuda.Stream(device=dev)
+            side.wait_stream(torch.cuda.current_stream(dev))
+            with torch.cuda.stream(side):
+                for _ in range(max(1, self.warmup)):        # (at least one: see GraphedLL._capture)
+                    self._run()
+            torch.cuda.current_stream(dev).wait_stream(side)
+            if integral._state.host_solve or integral.path_taken() != "hip":
+                raise ValueError("umnn_amd: GraphedSampler needs the in-kernel solve (HIP path, an integrand the solve kernels cover): "
+                                 "the host-driven Newton loop reads the device every iteration and cannot be captured")
+            _prime_for_capture(self.model, self.z)
+            self.graph = torch.cuda.CUDAGraph()
+            with made.capture_may_cache(), torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
+                self.out, self.last_move = self._run()
+        self._seen = self._versions()
+        self.captures += 1
+
+    def refresh(self):
+        """Re-capture unconditionally (after weight writes that do not bump tensor versions)."""
+        from .made import invalidate_caches
+        invalidate_caches(self.model)
+        self._capture()
+
+    def __call__(self, z=None, context=None):
+        """One replay -> the captured [n, d] samples (overwritten by the next call).  ``z`` None: fresh N(0, I) noise."""
+        if self._versions() != self._seen:
+            self._capture()
+        if z is None:
+            self.z.normal_()
+        else:
+            self.z.copy_(z)
         if context is not None:
             self.context.copy_(context)
         self.graph.replay()

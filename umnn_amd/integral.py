@@ -327,6 +327,8 @@ def _solve_call(fn_name, spec, h, target, nb_steps, x_out, want_info, info_shape
         fn_name, spec, h, target, nb_steps, lambda *a: call(*a, _ptr(x_out), _ptr(fx), _ptr(status)),
         "solve-host", "umnn_amd: no in-kernel Newton solve for this integrand / arithmetic mode ({}): the inverse runs the "
         "host-driven Newton loop (one forward launch per iteration).")
+    if not ok:
+        _state.host_solve = True        # (graphs.GraphedSampler: a host-driven Newton loop reads the device and cannot be captured)
     return (x_out, fx, status) if ok else None
 
 

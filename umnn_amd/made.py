@@ -519,6 +519,24 @@ class MADE(nn.Module):
         out = _train_chain(x, layers) if _train_chain_ok(x, layers) else self.net(x)
         return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
 
+    def graph_weights(self):
+        """[mask * weight] of every masked linear, formed by ordinary torch ops: what a recorded caller that runs the conditioner
+        many times on unchanged weights (the sampling loops of ``UMNNMAF.invert``) forms once and hands to ``raw_graph``."""
+        return [l.mask * l.weight for l in self.net if isinstance(l, MaskedLinear)]
+
+    def _graph_chain(self, a, weights):
+        layers = [l for l in self.net if isinstance(l, MaskedLinear)]
+        for i, (layer, w) in enumerate(zip(layers, weights)):
+            a = F.linear(a, w, layer.bias)
+            if i + 1 < len(layers):
+                a = torch.relu(a)
+        return a
+
+    def raw_graph(self, x, weights, out_dtype=None):
+        """``raw(x)`` in its graph-mode composition (fp32 F.linear + ReLU) on the masked weights of ``graph_weights()``."""
+        out = self._graph_chain(_to_weight_dtype(x, self.net[0]), weights)
+        return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
+
     def raw_rows(self, x, rows):
         """Output COLUMNS ``rows`` (an int64 device tensor) of ``raw(x)`` only -> [B, len(rows)] fp32, or None when this
         conditioner / call is not one the restriction pays for (the caller then takes ``raw(x)``).  Sampling needs, per flow dimension
@@ -622,6 +640,13 @@ class ConditionnalMADE(MADE):
             a = layer(a)
         last = layers[-1]
         out = F.linear(a, last.masked_weight().index_select(0, keep), last.bias.index_select(0, keep))
+        return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
+
+    def raw_graph(self, x, context, weights, out_dtype=None):
+        if context.dtype != x.dtype:
+            context = context.to(x.dtype)
+        out = self._graph_chain(_to_weight_dtype(torch.cat((context, x), 1), self.net[0]), weights)
+        out = out.view(x.shape[0], out.shape[1] // self.nin, self.nin)[:, :, self.cond_in:].reshape(x.shape[0], -1)
         return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
 
     def forward(self, x, context):

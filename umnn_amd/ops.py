@@ -4,6 +4,7 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
     umnn::cc_forward(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)
     umnn::cc_backward(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
+    umnn::cc_solve_block(t, h, x_init?, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::flow_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, log_jac_in?) -> (z, log_jac, f_x)
     umnn::flow_block_backward(x, h, scaling, f_x, gz, glj, W[], b[], hidden_act, out_act, nb_steps, reverse_z, need[3])
         -> (dx, dh, dtheta)
@@ -16,7 +17,9 @@ implementation calls the eager path's own ``integral.hip_*`` function (same arit
 ``path_taken()`` bookkeeping); every output is a fresh tensor and no op writes an input.  Outputs an op is told it need not
 compute (``need``) come back as empty tensors.  cc_forward, flow_block and flow_ll are differentiable (their backward is the
 matching op; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` -- is differentiable in its x output through cc_backward,
-by the implicit-function theorem; flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
+by the implicit-function theorem; cc_solve_block -- the same solve for every (row, dimension) in ONE launch, optionally warm-started,
+what the recorded ``invert(method="jacobi")`` sweeps call under no_grad -- has no autograd formula: a backward through it raises;
+flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
 flow_ll_block are not.  Registration loads no library and touches no GPU.
 
 The ops are public, so every real and fake implementation first checks what it was given (``_check_*``): one CUDA device for
@@ -289,6 +292,45 @@ def _cc_solve_backward(ctx, g_x, _gfx, _gstatus):
 
 cc_solve.register_autograd(_cc_solve_backward, setup_context=_cc_solve_setup)
 
+
+def _check_cc_solve_block(t, h, x_init, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
+    # (umnn_cc_solve_block is fp32-only in t, x_init and x; a bf16 embedding is widened, which is exact)
+    op = "cc_solve_block"
+    B, d = _check_net(op, t, h, W, b, hidden_act, out_act, _F32)
+    if x_init is not None:
+        _check_tensor(op, "x_init", x_init, t, (B, d), _F32)
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+    _req(op, lo < hi, f"empty bracket [{lo}, {hi}]")
+    _req(op, tol >= 0, f"tol is {tol}; expected >= 0")
+    _req(op, 1 <= max_iter <= _lib.SOLVE_EVALS_MASK, f"max_iter is {max_iter}; expected 1..{_lib.SOLVE_EVALS_MASK}")
+
+
+@torch.library.custom_op("umnn::cc_solve_block", mutates_args=(), device_types="cuda")
+def cc_solve_block(t: Tensor, h: Tensor, x_init: Optional[Tensor], W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
+                   nb_steps: int, lo: float, hi: float, tol: float, max_iter: int) -> tuple[Tensor, Tensor, Tensor]:
+    """x [B,d] in [lo, hi] with int_0^x f(s; h[:, :, i]) ds = t[:, i] for EVERY (row, dimension) in one launch
+    (``integral.hip_solve_block`` without scale and offset: the caller folds the flow's into t), started at ``x_init`` when given;
+    f(x; h) and the int32 status word per element.  Nets outside the solve tables run ``integral.newton_solve`` over [B, d] on the
+    forward kernel.  No autograd formula: the sweeps of ``invert`` run under no_grad."""
+    _check_cc_solve_block(t, h, x_init, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter)
+    spec = spec_from_tensors(W, b, hidden_act, out_act)
+    t32, h32 = t.detach().contiguous(), _I._f32c(h)
+    x0 = None if x_init is None else x_init.detach().contiguous()
+    with torch.no_grad():
+        if t32.shape[0] == 0:
+            return torch.empty_like(t32), torch.empty_like(t32), torch.empty(t32.shape, device=t32.device, dtype=torch.int32)
+        out = _I.hip_solve_block(spec, h32, t32, nb_steps, scaling=None, off_h0=False, x_init=x0, lo=lo, hi=hi, tol=tol, max_iter=max_iter)
+        if out is None:
+            out = _I.host_solve(spec, h32, t32, nb_steps, lo, hi, tol, max_iter, x_init=x0)
+    return out
+
+
+@cc_solve_block.register_fake
+def _(t, h, x_init, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
+    _check_cc_solve_block(t, h, x_init, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter)
+    return t.new_empty(t.shape), t.new_empty(t.shape), t.new_empty(t.shape, dtype=torch.int32)
+
+
 # ---------------------------------------------------------------------------------------------------------- flow block
 @torch.library.custom_op("umnn::flow_block", mutates_args=(), device_types="cuda")
 def flow_block(x: Tensor, h: Tensor, scaling: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
@@ -413,7 +455,7 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
     return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
 
 
-OPS = ("cc_forward", "cc_backward", "cc_solve", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+OPS = ("cc_forward", "cc_backward", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
 spec_args = _I.spec_args       # MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it
