@@ -583,6 +583,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                         znext[t][r] = 4 * t + r < NLIVE ? hidden_act_f(fmaf(w1x[t][r], t0, c[0][t][r]), slope) : 0.f;
             }
             float cs_cur = a.ccs[k_lo], cw_cur = a.ccw[k_lo];       // node abscissa / weight: fetched one node ahead
+            float Fpair = 0.f, fxpair = 0.f, fx0pair = 0.f;          // quadrature sum, f(x), f(x0) of BOTH tiles (cc_fwd_shared.h)
             for (int k = k_lo; k < k_hi; ++k) {
                 const int kn = k + 1 <= n ? k + 1 : n;
                 const float cs_next = a.ccs[kn], cw_next = a.ccw[kn];
@@ -642,15 +643,15 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (4 * t + r < NLIVE) sd1 = fmaf(wout[t][r], hidden_act_f(acc1[t][r], slope), sd1);
-#pragma unroll
-                for (int pt = 0; pt < 2; ++pt) {
-                    const float sr = group_allreduce(pt == 0 ? sd0 : sd1);
-                    const float f = pc_out_act(sr, m.out_act);
-                    Facc[pt] = fmaf(wk, maybe_inverse(f, a.inv_f), Facc[pt]);
-                    if (k == 0) fxv[pt] = f;
-                    if (k == n) fx0v[pt] = f;
-                }
+                // one output stage for both tiles (group_allreduce_pair: tile 0 in lane groups 0 and 2, tile 1 in groups 1 and 3)
+                const float f = pc_out_act(group_allreduce_pair(sd0, sd1), m.out_act);
+                Fpair = fmaf(wk, maybe_inverse(f, a.inv_f), Fpair);
+                if (k == 0) fxpair = f;
+                if (k == n) fx0pair = f;
             }
+            group_unpair(Fpair, Facc[0], Facc[1]);
+            group_unpair(fxpair, fxv[0], fxv[1]);
+            group_unpair(fx0pair, fx0v[0], fx0v[1]);
         } else {
         // ---- bracket search state (INV): one sample per tile, candidate p on lane p ----
         float br_left = -50.f, br_right = 50.f, br_best = 0.f, inv_target = 0.f, inv_off = 0.f, inv_scale = 1.f, frac = 1.f;
@@ -684,6 +685,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
         const int rounds = INV ? a.inv_iters : 1;
         bool inv_bad = false;            // (fp16 pieces: some candidate integral of some round was not finite -- an overflowed piece)
         bool inv_nan = false;            // (bracket search: some candidate's distance to the target was not a number in some round)
+        [[maybe_unused]] float Fpair = 0.f, fxpair = 0.f, fx0pair = 0.f;      // (P = 2) both tiles' sums in one register (cc_fwd_shared.h)
         for (int round = 0; round < rounds; ++round) {
         if constexpr (INV == 1) {
             xv[0] = __fadd_rn(__fmul_rn(frac, br_right - br_left), br_left);      // x_range * (right - left) + left
@@ -838,6 +840,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 for (int l = 1; l < L; ++l) layer(std::true_type{}, l);
             }
 
+            float sd[P];
 #pragma unroll
             for (int pt = 0; pt < P; ++pt) {
                 float s = 0.f;
@@ -846,11 +849,21 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
                         if (4 * t + r < (TREST > 0 ? NREST : NLIVE)) s = fmaf(wout[t][r], act[pt][t][r], s);
-                s = group_allreduce(s);
-                const float f = pc_out_act(s, m.out_act);
-                Facc[pt] = fmaf(wk, maybe_inverse(f, a.inv_f), Facc[pt]);
-                if (k == 0) fxv[pt] = f;
-                if (k == n) fx0v[pt] = f;
+                sd[pt] = s;
+            }
+            if constexpr (P == 2) {        // one output stage for both tiles, as in the pipelined loop
+                const float f = pc_out_act(group_allreduce_pair(sd[0], sd[1]), m.out_act);
+                Fpair = fmaf(wk, maybe_inverse(f, a.inv_f), Fpair);
+                if (k == 0) fxpair = f;
+                if (k == n) fx0pair = f;
+            } else {
+#pragma unroll
+                for (int pt = 0; pt < P; ++pt) {
+                    const float f = pc_out_act(group_allreduce(sd[pt]), m.out_act);
+                    Facc[pt] = fmaf(wk, maybe_inverse(f, a.inv_f), Facc[pt]);
+                    if (k == 0) fxv[pt] = f;
+                    if (k == n) fx0v[pt] = f;
+                }
             }
         }
         if constexpr (INV == 2) {
@@ -941,6 +954,11 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             br_right = below ? hi : br_best;
         }
         }   // rounds
+        if constexpr (P == 2) {
+            group_unpair(Fpair, Facc[0], Facc[1]);
+            group_unpair(fxpair, fxv[0], fxv[1]);
+            group_unpair(fx0pair, fx0v[0], fx0v[1]);
+        }
         if constexpr (INV == 2) {
             // overflow protocol (cc_solve.hip): a row whose iterate overflowed an fp16 piece is left to the queued bf16 build, its slot
             // marked with a NaN; in the other builds such a row (and a NaN target) returns NaN with UMNN_SOLVE_NONFINITE set

@@ -74,6 +74,27 @@ __device__ __forceinline__ bool fwd_group_marked(const FwdArgs& a, unsigned grp,
     return __any(m);
 }
 
+// The output stage of a wave with TWO point tiles, once per wave instead of once per tile: after the lane-group reduction a tile's
+// total is one value per point, replicated over the four lane groups, so both tiles' totals fit one register.  permlane16_swap(v0, v1)
+// returns {rows (v0.0, v1.0, v0.2, v1.2), rows (v0.1, v1.1, v0.3, v1.3)}: their sum holds g0 + g1 and g2 + g3 of v0 in rows 0 and 2,
+// of v1 in rows 1 and 3, and the half swap adds (g0 + g1) + (g2 + g3) -- group_allreduce's operands in group_allreduce's order, the same
+// bits.  Lane groups 0 and 2 end with the total of v0, groups 1 and 3 with the total of v1; everything computed from that register
+// (output activation, 1/f, the quadrature fma, f(x) and f(x0)) keeps the layout until group_unpair.
+__device__ __forceinline__ float group_allreduce_pair(float v0, float v1) {
+    auto a = __builtin_amdgcn_permlane16_swap(__float_as_uint(v0), __float_as_uint(v1), false, false);
+    const float s = __uint_as_float(a[0]) + __uint_as_float(a[1]);
+    const unsigned w = __float_as_uint(s);
+    auto b = __builtin_amdgcn_permlane32_swap(w, w, false, false);
+    return __uint_as_float(b[0]) + __uint_as_float(b[1]);
+}
+// paired register -> the two tiles' values, each in every lane group (what fwd_epilogue expects)
+__device__ __forceinline__ void group_unpair(float v, float& t0, float& t1) {
+    const unsigned u = __float_as_uint(v);
+    auto a = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+    t0 = __uint_as_float(a[0]);
+    t1 = __uint_as_float(a[1]);
+}
+
 // Combine the node-range partials of the NS waves sharing a tile group (through LDS), then write F, f(x), f(x0)
 // and, for the flow entry point, z and log_jac.  Called by every wave of the workgroup (it contains a barrier).
 template <int P>
