@@ -203,7 +203,8 @@ int umnn_cc_solve_block(const umnn_mlp* net, const float* h, const float* target
  *           is one more VJP at quadrature node 0, including d f/d x.
  *   dtheta  [n_params] in integrand.parameters() order (W0,b0,W1,b1,...); OVERWRITTEN
  *   dh      [B,E*d]; dx, dx0 [B,d]  (dx = f(x;h)*g [+ g_fx * df/dx], dx0 = -f(x0;h)*g); each nullable.
- *   workspace: device scratch of at least umnn_cc_backward_workspace_bytes() bytes. */
+ *   workspace: device scratch of at least umnn_cc_backward_workspace_bytes() bytes (which never shrinks as B grows: a workspace
+ *   sized for the largest batch serves every smaller one). */
 int umnn_cc_backward(const umnn_mlp* net, const float* x0, const float* x, const float* h,
                      const float* g, const float* g_fx,
                      const float* cc_w, const float* cc_s, int nb_steps,
@@ -312,9 +313,10 @@ int umnn_get_forward_precision(void);
  *   BF16X3  the matrix-core kernels.  The forward recompute inside them is always fp32-LEVEL (the sign of every hidden
  *           pre-activation decides a LeakyReLU slope): six cross terms on three bf16 pieces, or three cross terms on two fp16
  *           pieces; the delta chain and the dW products carry three cross terms.  Which kernel runs:
- *             - four hidden layers of 32..63 units, ELU+1 output, un-split node range, >= 4 tiles per workgroup:
+ *           (the exact rules -- sizes, thresholds, eligibility -- are csrc/cc_bwd_plan.h: bwd_route; umnn_cc_backward_plan_name asks it)
+ *             - four hidden layers of 32..63 units at batches that fill the workgroups:
  *               the eight-wave workgroup pipeline -- on fp16 pieces (cc_bwd_ws16_kernel.h, kernel names cc_bwd_f16<...,WS>) for
- *               launches of >= 2^21 node evaluations (option bwd_ws16 = 1; 2 = whenever eligible; 0 = never), on bf16 pieces
+ *               large launches (option bwd_ws16 = 1; 2 = whenever eligible; 0 = never), on bf16 pieces
  *               (cc_bwd_ws_kernel.h, cc_bwd_bf16<...,WS>) otherwise and for 1/f launches and sigmoid outputs.  The fp16 kernel
  *               carries cotangents scaled by a per-launch power of two (cc_bwd_cotmax_kernel), detects an overflowed piece in
  *               its output-layer and dc sums, raises a flag word in the workspace, and the bf16 pipeline queued behind it
@@ -324,7 +326,7 @@ int umnn_get_forward_precision(void);
  *             - two or three hidden layers of 32..63 units, or small batches: the software-pipelined one-pass loop
  *               (cc_bwd_swp_kernel.h; option bwd_swp = 0: the round-2 loop);
  *             - a first hidden layer of 5..8 tiles over 2..4 narrower ones (31-100-50-50-50-50-1): three stages through HBM
- *               (cc_backward_front.hip) -- stages A and B on fp16 pieces for single-chunk calls of >= 2^21 node evaluations with
+ *               (cc_backward_front.hip) -- stages A and B on fp16 pieces for single-chunk calls under the same rule, with
  *               their bf16 builds queued as the overflow fallback, on bf16 pieces otherwise;
  *             - every other shape: the fp32 kernels below.
  *   FP32    exact fp32 MFMA (cc_backward.hip) for every one-pass shape; the three-stage family runs its build with three bf16
@@ -340,6 +342,15 @@ int umnn_get_forward_precision(void);
  * GPU), < -1 error.  The staged family takes its HBM scratch from the
  * workspace (umnn_cc_backward_workspace_bytes includes up to 2 GiB for it). */
 int umnn_cc_backward_kind(const umnn_mlp* net, int E);
+/* The name umnn_last_kernel_name_of(UMNN_PROF_BACKWARD) would hold after umnn_cc_backward_io(net, ..., nb_steps, B, d, E, ...) under the
+ * current options, "" where that call would return an error.  flags: UMNN_PLAN_* bits for what the call brings.  Read-only: the launch
+ * plan (csrc/cc_bwd_plan.h) is evaluated and nothing is launched, so it also answers without a device (as for 256 CUs). */
+#define UMNN_PLAN_INV_F 1            /* inv_f != 0 */
+#define UMNN_PLAN_G_FX 2             /* g_fx != NULL */
+#define UMNN_PLAN_Z2_SAVED 4         /* umnn_cc_backward_saved(_io) with a z_2 buffer */
+#define UMNN_PLAN_X_BF16 8           /* umnn_io::x_dtype = UMNN_DTYPE_BF16 */
+#define UMNN_PLAN_H_BF16 16          /* umnn_io::h_dtype = UMNN_DTYPE_BF16 */
+const char* umnn_cc_backward_plan_name(const umnn_mlp* net, long long B, int d, int E, int nb_steps, int flags);
 int umnn_set_backward_precision(int mode);
 int umnn_get_backward_precision(void);
 
@@ -351,7 +362,8 @@ int umnn_get_backward_precision(void);
  * round-2 node loop), "bwd_ws" (1, default: four-hidden-layer nets at large batch take the weight-stationary workgroup
  * pipeline, cc_bwd_ws_kernel.h; 0: they stay on the one-pass loop), "bwd_ws16" (that pipeline on fp16 pieces,
  * cc_bwd_ws16_kernel.h -- three-term recompute, cotangents scaled by a per-launch power of two, overflow flag + queued bf16
- * fallback: 1, default: launches of >= 2^21 node evaluations; 2: whenever the pipeline is eligible; 0: never), "front_bwd2" (1,
+ * fallback: 1, default: large launches, the threshold being bwd_ws16_ok of csrc/cc_bwd_plan.h; 2: whenever the pipeline is eligible;
+ * 0: never), "front_bwd2" (1,
  * default: the last stage of the three-stage backward runs two waves per tile of integrals, each on half of the wide first hidden
  * layer's feature tiles -- on fp16 pieces behind the fp16 middle stage, its bf16 build queued as the overflow fallback; 2: two waves,
  * bf16 pieces always; 0: one wave per tile);

@@ -7,10 +7,11 @@
 ``run`` executes a fixed list of small cases with fixed seeds -- the smallest shapes that reach each arm of the path selection in
 flow.py / integral.py / ops.py -- eagerly and under the compile backends tests/test_gpu_torch_compile.py uses (aot_eager for every
 case; Inductor, where Triton is installed, for the two kinds of graph that file compiles with it), and records per case every
-output and gradient tensor, ``path_taken()``, ``backward_path_taken()``, ``umnn_last_kernel_name()`` and the
-``umnn_launch_count()`` delta.  A case that raises is recorded by its exception type.  ``compare`` wants ``torch.equal`` on every
+output and gradient tensor, ``path_taken()``, ``backward_path_taken()``, ``umnn_last_kernel_name()``, the last kernel of the
+backward's main pass (``umnn_last_kernel_name_of(PROF_BACKWARD)``) and the ``umnn_launch_count()`` delta.  The list ends with the
+GPU cases of tests/_bwd_plan_cases.py: one ``integral.hip_backward`` call per kernel family and option of the backward's launch plan.  A case that raises is recorded by its exception type.  ``compare`` wants ``torch.equal`` on every
 tensor and equality of every string and count; it prints (and writes to REPORT) the number of tensors, the number of mismatches and
-the kernel names seen, and exits non-zero on any mismatch.  Only the public API is used, so the file runs in older checkouts too."""
+the kernel names seen, and exits non-zero on any mismatch.  Only the public API is used, so the file runs in older checkouts too (with tests/_bwd_plan_cases.py copied along)."""
 import os
 import sys
 import warnings
@@ -180,6 +181,18 @@ def _invert(method, cond):
     return make
 
 
+def _backward_plan_case(c):
+    def make(dev):
+        from tests import _bwd_plan_cases
+        return None, (lambda: _bwd_plan_cases.run(c, dev)), (), None
+    return make
+
+
+def _backward_plan_cases():
+    from tests import _bwd_plan_cases
+    return [(f"backward plan: {c['id']}", EAGER, _backward_plan_case(c)) for c in _bwd_plan_cases.GPU_CASES]
+
+
 EAGER, COMPILED, INDUCTOR = ("eager",), ("eager", "aot_eager"), ("eager", "aot_eager", "inductor")
 WIDE_FIRST = dict(d=8, E=10, hidden=(100, 50, 50, 50, 50))           # the z_2 hand-off from the training forward to the backward
 DEEP_WIDE = dict(d=2, E=4, hidden=(100, 72, 80, 96, 70), n=10)       # no shape-exact HIP backward: the ATen backward
@@ -204,7 +217,7 @@ CASES = [
     ("MonotonicNN.inverse", COMPILED, _monotonic(True)),
     ("InverseNeuralIntegral, gradients to h and the parameters", COMPILED, _inverse_integral),
 ] + [(f"flow.invert {method}{', context' if cond else ' (raw_rows)'}", COMPILED, _invert(method, cond))
-     for method in ("bracket", "newton", "jacobi") for cond in (False, True)]
+     for method in ("bracket", "newton", "jacobi") for cond in (False, True)] + _backward_plan_cases()
 
 
 def _flat(out):
@@ -252,11 +265,12 @@ def run(out_path):
                 rec["launches"] = int(lib.umnn_launch_count() - n0)
                 rec["path"], rec["backward_path"] = umnn_amd.path_taken(), umnn_amd.backward_path_taken()
                 rec["kernel"] = lib.umnn_last_kernel_name().decode()
+                rec["bwd_kernel"] = lib.umnn_last_kernel_name_of(_lib.PROF_BACKWARD).decode()
             except Exception as e:      # noqa: BLE001  (recorded: both checkouts must fail alike)
                 rec["error"] = type(e).__name__
             records.append(rec)
             print(f"{name} [{backend}]: {len(rec['tensors'])} tensors, {rec.get('launches')} launches, {rec.get('path')} / "
-                  f"{rec.get('backward_path')}, {rec.get('kernel')}{', ' + rec['error'] if rec['error'] else ''}", flush=True)
+                  f"{rec.get('backward_path')}, {rec.get('kernel')}, {rec.get('bwd_kernel')}{', ' + rec['error'] if rec['error'] else ''}", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     torch.save(records, out_path)
 
@@ -269,7 +283,7 @@ def compare(a_path, b_path, report=None):
         bad += 1
     for ra, rb in zip(a, b):
         where = f"{ra['case']} [{ra['backend']}]"
-        for key in ("error", "launches", "path", "backward_path", "kernel"):
+        for key in ("error", "launches", "path", "backward_path", "kernel", "bwd_kernel"):
             if ra.get(key) != rb.get(key):
                 bad += 1
                 lines.append(f"MISMATCH {where}: {key} {ra.get(key)!r} != {rb.get(key)!r}")
@@ -284,8 +298,7 @@ def compare(a_path, b_path, report=None):
             if not same:
                 bad += 1
                 lines.append(f"MISMATCH {where}: tensor {i} {tuple(ta.shape)} {ta.dtype} vs {tuple(tb.shape)} {tb.dtype}")
-        if ra.get("kernel"):
-            kernels.add(ra["kernel"])
+        kernels.update(k for k in (ra.get("kernel"), ra.get("bwd_kernel")) if k)
         if ra["error"]:
             lines.append(f"note {where}: both raised {ra['error']}" if ra["error"] == rb["error"] else "")
     head = [f"cases x backends: {len(a)}", f"tensors compared: {tensors}", f"mismatches: {bad}", "kernel names seen:"]

@@ -37,6 +37,7 @@ class IoDesc(ctypes.Structure):
 
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
+PLAN_INV_F, PLAN_G_FX, PLAN_Z2_SAVED, PLAN_X_BF16, PLAN_H_BF16 = 1, 2, 4, 8, 16      # flags of umnn_cc_backward_plan_name
 
 # name -> (restype, argtypes); must list every symbol include/umnn_cc.h declares
 SIGNATURES = {
@@ -81,6 +82,7 @@ SIGNATURES = {
     "umnn_set_forward_precision": (ctypes.c_int, [ctypes.c_int]),
     "umnn_get_forward_precision": (ctypes.c_int, []),
     "umnn_cc_backward_kind": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int]),
+    "umnn_cc_backward_plan_name": (ctypes.c_char_p, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
     "umnn_set_backward_precision": (ctypes.c_int, [ctypes.c_int]),
     "umnn_get_backward_precision": (ctypes.c_int, []),
     "umnn_profile_enable": (ctypes.c_int, [ctypes.c_int]),

@@ -22,7 +22,7 @@
 //     (deterministic, no atomics).
 #include <cstring>
 
-#include "cc_bwd_shared.h"
+#include "cc_bwd_plan.h"
 
 __device__ __forceinline__ void stage_rowmajor_images(const BwdArgs& a, float* lds, int tid, int nthreads) {
     const MlpDev& m = a.m;
@@ -467,10 +467,7 @@ __global__ __launch_bounds__(256) void cc_bwd_dcsum_kernel(float* __restrict__ d
 // bank 4 * (k p mod 16) + g): both the staging writes and the fragment reads are conflict-free -- every wave owns output tiles
 // (16 features x 16 embedding columns) and walks the chunk four integrals per v_mfma_f32_16x16x4_f32.  (Round 1-2 had one thread per output and two LDS reads per FMA:
 // 0.40 ms per C3 call against 165 MB of traffic; this one is bound by the dc / h stream.)
-__host__ __device__ inline int dw0_stride(int cols) { return ((cols + 15) / 16 * 16 + 16 + 31) / 32 * 32 - 16; }   // >= cols, = 16 mod 32
-__host__ __device__ inline size_t dw0_lds_floats(int chunk, int H1, int E) {
-    return (size_t)chunk * dw0_stride(H1) + (size_t)((E + 1 + 15) / 16 * 16) * (chunk + 4);
-}
+// (dw0_stride / dw0_lds_floats: cc_bwd_plan.h, next to the plan that sizes the chunks)
 // DW0_MAXT = output tiles per wave (compile-time: the accumulators stay in registers): 2 covers the 48..64-wide, E <= 31 nets,
 // 4 the 100-wide ones, 10 = ceil(8 x 5 / 4) everything up to H1 = 127, E = 79 in one launch (wider embeddings: one launch per
 // 40 tiles, `tile_base`; every launch writes its own entries of the same partial slices).
@@ -599,193 +596,30 @@ __global__ __launch_bounds__(256) void cc_bwd_reduce_kernel(const float* __restr
 // host side
 // ------------------------------------------------------------------------------------------
 typedef void (*bwd_kernel_t)(const BwdArgs);
-struct BwdVariant { int tmax, nacc, edge, ksc; bwd_kernel_t fn; const char* name; };
-#define BWD_VARIANT(T, N, E, K) { T, N, E, K, cc_bwd_kernel<T, N, (E) != 0, K>, "cc_bwd<T=" #T ",NACC=" #N ",EDGE=" #E ",KS=" #K ">" }
-static const BwdVariant kBwdVariants[] = {
-    BWD_VARIANT(4, 3, 1, 13), BWD_VARIANT(4, 3, 0, 13),     // exact: every hidden layer 48..51 wide (UCI / VAE nets)
-    BWD_VARIANT(2, 3, 1, 0), BWD_VARIANT(2, 3, 0, 0),
-    BWD_VARIANT(4, 3, 1, 0), BWD_VARIANT(4, 3, 0, 0),
-    BWD_VARIANT(5, 2, 1, 17), BWD_VARIANT(5, 3, 0, 17),     // exact: every hidden layer 64 wide
-    BWD_VARIANT(7, 1, 1, 26), BWD_VARIANT(7, 0, 1, 26), BWD_VARIANT(7, 1, 0, 26),   // exact: every hidden layer 100 wide (toy flows, MonotonicNN): no spills
-    BWD_VARIANT(7, 0, 1, 0), BWD_VARIANT(7, 1, 0, 0),
-    BWD_VARIANT(8, 0, 1, 0), BWD_VARIANT(8, 1, 0, 0),
-    BWD_VARIANT(8, 0, 1, 32), BWD_VARIANT(8, 1, 0, 32),     // exact: every hidden layer 124..127 wide, or zero-padded to that (edge pass without dW: no spills; 51 in the others)
-};
+// the variants of cc_bwd_plan.h's list, in its order: kBwdFp32Kernels[i] is the kernel of kBwdFp32Variants[i]
+#define BWD_FP32_KERNEL(T, N, E, K) cc_bwd_kernel<T, N, (E) != 0, K>,
+static const bwd_kernel_t kBwdFp32Kernels[] = { UMNN_BWD_FP32_VARIANTS(BWD_FP32_KERNEL) };
+static_assert(sizeof(kBwdFp32Kernels) / sizeof(kBwdFp32Kernels[0]) == kBwdFp32Count, "one kernel per variant");
 
-static const BwdVariant* find_bwd(int tmax, int nacc, int edge, int ksu) {
-    for (int exact = 1; exact >= 0; --exact)
-        for (const BwdVariant& v : kBwdVariants)
-            if (v.tmax == tmax && v.nacc == nacc && v.edge == edge && (exact ? (v.ksc && v.ksc == ksu) : !v.ksc)) return &v;
-    return nullptr;
+static BwdOptions bwd_options() {
+    const UmnnOptions& o = umnn_options();
+    return BwdOptions{o.bwd_precision, o.bwd_ws, o.bwd_ws16, o.bwd_swp, o.bwd_ns, o.front_bwd2};
 }
-// template tile count: the net's own when a shape-exact family exists for it, else the next generic bucket
-static int pick_tmax_bwd(int tmax, int ksu) {
-    if (ksu)
-        for (const BwdVariant& v : kBwdVariants)
-            if (v.ksc == ksu && v.tmax == tmax) return tmax;
-    return tmax <= 2 ? 2 : tmax <= 4 ? 4 : tmax <= 7 ? 7 : 8;
-}
-// dW layers a pass can hold: the largest NACC instantiated for (T, edge), preferring the shape-exact family
-static int best_nacc(int T, int edge, int ksu) {
-    for (int exact = 1; exact >= 0; --exact)
-        for (int n = 3; n >= 0; --n)
-            for (const BwdVariant& v : kBwdVariants)
-                if (v.tmax == T && v.nacc == n && v.edge == edge && (exact ? (v.ksc && v.ksc == ksu) : !v.ksc)) return n;
-    return -1;
-}
-
-// Nets with UNEQUAL hidden widths above 63 units (5..7 tiles) have no shape-exact variant of their own, and the generic
-// variants with runtime tile counts spill hundreds of registers there (687 ms per call at 256 x 784 integrals).  Pad them --
-// virtually: only the per-layer tile and K-step counts change, the staged images carry the zeros and the constant-one feature
-// of every layer stays at its own index width[l] -- to the smallest shape-exact family that holds the widest layer: (5 tiles,
-// 17 K-steps: widths up to 67) or (7, 26: up to 103).  A padded unit has zero weights and bias, so z = 0, act(0) = 0, and it
-// contributes exact zeros to every sum; d_theta is written for the real entries only.  Returns 1 if the net was padded.
-static int pad_to_exact_family(MlpDev& m, int* tmax, int* ksu) {
-    if (*tmax <= 4) return 0;
-    if (*ksu)
-        for (const BwdVariant& v : kBwdVariants)
-            if (v.ksc == *ksu && v.tmax == *tmax) return 0;
-    const int L = m.n_linear - 1;
-    int ksmax = 0;
-    for (int l = 1; l <= L; ++l) ksmax = m.ks_in[l] > ksmax ? m.ks_in[l] : ksmax;
-    static const int kFamilies[][2] = {{5, 17}, {7, 26}, {8, 32}};
-    for (const auto& f : kFamilies) {
-        if (*tmax > f[0] || ksmax > f[1]) continue;
-        for (int l = 1; l <= L; ++l) { m.t_out[l] = m.t_mfma[l] = f[0]; m.ks_in[l] = f[1]; }
-        int off = 0;
-        for (int l = 1; l < L; ++l) { m.lds_off[l] = off; off += m.t_out[l + 1] * m.ks_in[l] * 64; }
-        m.lds_off[L] = off;
-        *tmax = f[0]; *ksu = f[1];
-        return 1;
-    }
-    return 0;
-}
-
-// row stride for the row-major image: >= cols, minimising bank conflicts of both fragment shapes
-// (forward: 16 rows x 2 adjacent cols per half-wave; backward: 2 adjacent rows x 16 cols)
-static int pick_ld(int cols) {
-    int best = cols, best_cost = 1 << 30;
-    for (int ld = cols; ld < cols + 33; ++ld) {
-        int cost = 0;
-        for (int pattern = 0; pattern < 2; ++pattern) {
-            int cnt[32] = {0};
-            for (int a16 = 0; a16 < 16; ++a16)
-                for (int b2 = 0; b2 < 2; ++b2) {
-                    const int addr = pattern == 0 ? a16 * ld + b2 : b2 * ld + a16;
-                    cnt[((addr % 32) + 32) % 32]++;
-                }
-            int worst = 0;
-            for (int b = 0; b < 32; ++b) worst = cnt[b] > worst ? cnt[b] : worst;
-            cost += worst;
-        }
-        if (cost < best_cost) { best_cost = cost; best = ld; }
-    }
-    return best;
-}
-
-struct BwdPlan {
-    BwdArgs a;
-    int tmax;          // template tile count
-    int ksu;           // common K-step count when every hidden layer fills exactly `tmax` tiles, else 0
-    int nwaves, nblocks, wpb;
-    int ns;            // node-range split of the fp32 kernels (small batches: fewer tiles than waves)
-    size_t lds_bytes_for(int nacc, int waves) const { return (size_t)(a.scratch_off + waves * (nacc + 1) * tmax * 256) * sizeof(float); }
-    long long ws_partials, ws_dc, ws_p0;   // byte offsets in the workspace
-    long long ws_scal;                     // 256 B of launch scalars (cc_bwd_ws16_kernel.h)
-    long long ws_front, ws_front_bytes;    // HBM scratch of the staged backward (wide first hidden layer), 0 if not that family
-    long long ws_total;
-    int nparts0, chunk0;
-};
-
-static int plan_backward_impl(const umnn_mlp* net, long long B, int d, int E, BwdPlan* pl, bool allow_pad, int* padded);
-static int plan_backward(const umnn_mlp* net, long long B, int d, int E, BwdPlan* pl, int* padded_out = nullptr) {
-    int padded = 0;
-    int rc = plan_backward_impl(net, B, d, E, pl, true, &padded);
-    if (rc == UMNN_EUNSUPPORTED && padded) {              // (the padded images of a deep net can exceed the LDS: the net's own counts then)
-        padded = 0;
-        rc = plan_backward_impl(net, B, d, E, pl, false, &padded);
-    }
-    if (padded_out) *padded_out = padded;
-    return rc;
-}
-
-static int plan_backward_impl(const umnn_mlp* net, long long B, int d, int E, BwdPlan* pl, bool allow_pad, int* padded) {
+// the shape plan of (net, B, d, E) under the current options, on the current device; B >= 1
+static int plan_backward(const umnn_mlp* net, long long B, int d, int E, BwdShapePlan* pl) {
+    MlpDev m;
     int tmax = 0, ksu = 0;
-    if (int rc = umnn_prepare_mlp(net, E, &pl->a.m, &tmax, &ksu)) return rc;
-    BwdArgs& a = pl->a;
-    const int L = a.m.n_linear - 1;
-    // (the three-stage kernels of cc_backward_front.hip take their shape first: they read the unpadded tile counts)
-    const bool front = umnn_backward_front_shape(a.m);
-    *padded = (!front && allow_pad) ? pad_to_exact_family(a.m, &tmax, &ksu) : 0;
-    pl->tmax = pick_tmax_bwd(tmax, ksu);
-    pl->ksu = (ksu && tmax == pl->tmax) ? ksu : 0;
-    int off = 0;
-    for (int l = 1; l < L; ++l) {
-        a.ld[l] = pick_ld(4 * a.m.ks_in[l]);
-        a.roff[l] = off;
-        off += 4 * a.m.ks_in[l + 1] * a.ld[l];
-        off = (off + 3) & ~3;
-    }
-    a.scratch_off = off;
-    int po = 0;
-    for (int l = 0; l <= L; ++l) {
-        a.poffW[l] = po; po += net->widths[l + 1] * net->widths[l];
-        a.poffb[l] = po; po += net->widths[l + 1];
-    }
-    a.n_params = po;
-    a.NI = B * (long long)d; a.d = d; a.E = E;
-    a.ngroups = (unsigned)((a.NI + 15) / 16);
-    // waves per workgroup: as many (4, 2, 1) as leave room for the wave-private transpose tiles
-    const int nm = best_nacc(pl->tmax, 1, pl->ksu), nr = best_nacc(pl->tmax, 0, pl->ksu);
-    const int nacc_max = nm > nr ? nm : nr;
-    pl->wpb = 4;
-    while (pl->wpb > 1 && pl->lds_bytes_for(nacc_max, pl->wpb) > 160 * 1024) pl->wpb >>= 1;
-    if (pl->lds_bytes_for(nacc_max, pl->wpb) > 160 * 1024)
-        return umnn_fail(UMNN_EUNSUPPORTED, "backward: weight images exceed 160 KiB of LDS");
-    // fewer tiles than waves (the reference's own training batches are 100 samples): share a tile's nodes among
-    // up to 32 waves; every work item keeps its own d_theta / dc partial, summed in a fixed order afterwards
-    pl->ns = 1;
-    {
-        const long long waves = (long long)umnn_num_cus() * pl->wpb;
-        if ((long long)a.ngroups * 2 <= waves) pl->ns = (int)(waves / a.ngroups > 32 ? 32 : waves / a.ngroups);
-        if (const int v = umnn_options().bwd_ns; v >= 1 && v <= 32) pl->ns = v;
-    }
-    const long long items = (long long)a.ngroups * pl->ns;
-    pl->nblocks = umnn_num_cus();
-    if ((long long)pl->nblocks * pl->wpb > items) pl->nblocks = (int)((items + pl->wpb - 1) / pl->wpb);
-    if (pl->nblocks < 1) pl->nblocks = 1;
-    pl->nwaves = pl->nblocks * pl->wpb;
-    a.ns = 1;
-    const int H1 = net->widths[1];
-    pl->chunk0 = 64;
-    while (pl->chunk0 > 16 && dw0_lds_floats(pl->chunk0, H1, E) * sizeof(float) > 32 * 1024) pl->chunk0 /= 2;
-    while (pl->chunk0 > 16 && a.NI / pl->chunk0 < 2LL * umnn_num_cus()) pl->chunk0 /= 2;     // small batches: more, smaller chunks
-    {   // persistent blocks (four per CU), each accumulating its chunks in registers: at most that many partial slices
-        const long long nchunks = (a.NI + pl->chunk0 - 1) / pl->chunk0, cap = 4LL * umnn_num_cus();
-        pl->nparts0 = (int)(nchunks < cap ? nchunks : cap);
-    }
-    long long o = 0;
-    pl->ws_partials = o; o += (long long)pl->nwaves * a.n_params * 4; o = (o + 255) & ~255LL;
-    pl->ws_dc = o; o += a.NI * H1 * 4 * pl->ns; o = (o + 255) & ~255LL;
-    pl->ws_p0 = o; o += (long long)pl->nparts0 * H1 * (E + 1) * 4; o = (o + 255) & ~255LL;
-    pl->ws_scal = o; o += 256;
-    pl->ws_front = o;
-    pl->ws_front_bytes = (umnn_backward_front_shape(a.m) && pl->wpb == 4)
-                             ? umnn_backward_front_scratch_bytes(a.m, a.NI) : 0;
-    o += pl->ws_front_bytes; o = (o + 255) & ~255LL;
-    pl->ws_total = o;
+    if (int rc = umnn_prepare_mlp(net, E, &m, &tmax, &ksu)) return rc;
+    if (const char* err = bwd_plan_shape(pl, m, tmax, ksu, B, d, E, umnn_num_cus(), umnn_options().bwd_ns)) return umnn_fail(UMNN_EUNSUPPORTED, err);
     return 0;
 }
 
 extern "C" long long umnn_cc_backward_workspace_bytes(const umnn_mlp* net, long long B, int d, int E) {
-    BwdPlan pl;
+    BwdShapePlan pl{};
     if (B <= 0) return 0;
     if (plan_backward(net, B, d, E, &pl)) return -1;
     return pl.ws_total;
 }
-
-
-int umnn_launch_backward_bf16(const BwdArgs& base, const umnn_mlp* net, int nblocks_max, int* nwaves_out, hipStream_t stream);
 
 // Which kernel family umnn_cc_backward would use for this net: 1 = shape-exact kernels (compile-time tile counts),
 // 0 = generic kernels with at most four tiles per layer (runtime guards, ~2.5x slower), -1 = generic kernels with more
@@ -797,19 +631,25 @@ extern "C" int umnn_cc_backward_kind(const umnn_mlp* net, int E) {
     MlpDev m;
     int tmax = 0, ksu = 0;
     if (int rc = umnn_prepare_mlp(net, E, &m, &tmax, &ksu)) return rc < -1 ? rc : -2;
+    BwdShapePlan pl{};
+    bwd_plan_net(&pl, m, tmax, ksu);       // (images above the LDS limit: the plan holds the net's own counts, which is what is reported)
     // wide first hidden layer + narrow rest (MNISTExperiment's 100-50-50-50-50): the three-stage kernels of
     // cc_backward_front.hip (bwd_precision = fp32: their six-term build, cc_backward_front_p3.hip)
-    if (umnn_backward_front_shape(m)) return 1;
-    {   // unequal widths of 5..8 tiles run zero-padded on a shape-exact family, if the padded weight images fit the LDS
-        BwdPlan pl;
-        int padded = 0;
-        if (plan_backward(net, 16, 1, E, &pl, &padded) == 0 && padded) pad_to_exact_family(m, &tmax, &ksu);
-    }
-    const int T = pick_tmax_bwd(tmax, ksu);
-    const int ks = (ksu && tmax == T) ? ksu : 0;
-    const int nm = best_nacc(T, 1, ks);
-    if (ks && nm >= 0 && find_bwd(T, nm, 1, ks)->ksc) return 1;
-    return T <= 4 ? 0 : -1;
+    if (pl.front_shape) return 1;
+    const int nm = best_nacc(pl.tmax, 1, pl.ksu);
+    if (pl.ksu && nm >= 0 && kBwdFp32Variants[find_bwd(pl.tmax, nm, 1, pl.ksu)].ksc) return 1;
+    return pl.tmax <= 4 ? 0 : -1;
+}
+
+// What umnn_last_kernel_name_of(UMNN_PROF_BACKWARD) would hold after umnn_cc_backward_io(net, ..., nb_steps, B, d, E, inv_f, ...)
+// under the current options: shape plan + route, nothing launched ("" where the call would return an error).
+extern "C" const char* umnn_cc_backward_plan_name(const umnn_mlp* net, long long B, int d, int E, int nb_steps, int flags) {
+    BwdShapePlan pl{};
+    if (B < 1 || d < 1 || nb_steps < 1 || plan_backward(net, B, d, E, &pl)) return "";
+    // (a saved z_2 counts where the _saved entry points would take it: umnn_cc_forward_z2_floats != 0 under the current options)
+    const bool has_z2 = (flags & UMNN_PLAN_Z2_SAVED) && umnn_cc_forward_z2_floats(net, B, d, E, nb_steps) != 0;
+    const BwdRoute rt = bwd_route(pl, nb_steps, (flags & UMNN_PLAN_INV_F) != 0, (flags & UMNN_PLAN_G_FX) != 0, has_z2, true, bwd_options());
+    return rt.error ? "" : rt.name;
 }
 
 extern "C" int umnn_cc_backward(const umnn_mlp* net, const float* x0, const float* x, const float* h,
@@ -834,18 +674,22 @@ extern "C" int umnn_cc_backward_io(const umnn_mlp* net, const umnn_io* io, const
     return backward_impl(net, io, x0_, x_, h_, g_, g_fx_, cc_w, cc_s, nb_steps, B, d, E, inv_f, dx0_, dx_, dh_, dtheta, workspace,
                          workspace_bytes, stream_, nullptr);
 }
+// The z_2 buffer of the _saved entry points.  `need` follows the CURRENT process-wide precision options: if they changed between the
+// training forward and this call (need == 0: the pair no longer applies), the buffer is simply ignored and the backward recomputes z_2
+static int check_z2_saved(const umnn_mlp* net, long long B, int d, int E, int nb_steps, const float** z2_saved, long long z2_floats) {
+    const long long need = umnn_cc_forward_z2_floats(net, B, d, E, nb_steps);
+    if (need == 0) *z2_saved = nullptr;
+    else if (!*z2_saved || z2_floats < need)
+        return umnn_fail(UMNN_EINVAL, "backward (z_2 saved): buffer missing or smaller than umnn_cc_forward_z2_floats()");
+    return 0;
+}
 // umnn_cc_backward (lower limit 0, fp32 storage) with the z_2 buffer umnn_flow_stack_block_forward_save left: the three-stage family
 // skips its stage A.  z2_floats must be what umnn_cc_forward_z2_floats returned for the same (net, B, d, E, nb_steps).
 extern "C" int umnn_cc_backward_saved(const umnn_mlp* net, const float* x, const float* h, const float* g, const float* g_fx,
                                       const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E,
                                       float* dx, float* dh, float* dtheta, const float* z2_saved, long long z2_floats,
                                       void* workspace, long long workspace_bytes, void* stream_) {
-    // `need` follows the CURRENT process-wide precision options: if they changed between the training forward and this call (need == 0:
-    // the pair no longer applies), the buffer is simply ignored and the backward recomputes z_2 -- as the comment in backward_impl says
-    const long long need = umnn_cc_forward_z2_floats(net, B, d, E, nb_steps);
-    if (need == 0) z2_saved = nullptr;
-    else if (!z2_saved || z2_floats < need)
-        return umnn_fail(UMNN_EINVAL, "backward (z_2 saved): buffer missing or smaller than umnn_cc_forward_z2_floats()");
+    if (int rc = check_z2_saved(net, B, d, E, nb_steps, &z2_saved, z2_floats)) return rc;
     return backward_impl(net, nullptr, nullptr, x, h, g, g_fx, cc_w, cc_s, nb_steps, B, d, E, 0, nullptr, dx, dh, dtheta, workspace,
                          workspace_bytes, stream_, z2_saved);
 }
@@ -853,10 +697,7 @@ extern "C" int umnn_cc_backward_saved_io(const umnn_mlp* net, const umnn_io* io,
                                          const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E,
                                          void* dx, void* dh, float* dtheta, const float* z2_saved, long long z2_floats,
                                          void* workspace, long long workspace_bytes, void* stream_) {
-    const long long need = umnn_cc_forward_z2_floats(net, B, d, E, nb_steps);
-    if (need == 0) z2_saved = nullptr;
-    else if (!z2_saved || z2_floats < need)
-        return umnn_fail(UMNN_EINVAL, "backward (z_2 saved): buffer missing or smaller than umnn_cc_forward_z2_floats()");
+    if (int rc = check_z2_saved(net, B, d, E, nb_steps, &z2_saved, z2_floats)) return rc;
     return backward_impl(net, io, nullptr, x, h, g, g_fx, cc_w, cc_s, nb_steps, B, d, E, 0, nullptr, dx, dh, dtheta, workspace,
                          workspace_bytes, stream_, z2_saved);
 }
@@ -871,18 +712,20 @@ static int backward_impl(const umnn_mlp* net, const umnn_io* io, const void* x0_
     hipStream_t stream = (hipStream_t)stream_;
     if (B < 0 || d < 1) return umnn_fail(UMNN_EINVAL, "backward: B must be >= 0 and d >= 1");
     if (nb_steps < 1) return umnn_fail(UMNN_EINVAL, "backward: nb_steps must be >= 1");
-    BwdPlan pl;
     if (B == 0) {
         if (!net) return umnn_fail(UMNN_EINVAL, "net is null");
         if (dtheta) return umnn_check(hipMemsetAsync(dtheta, 0, umnn_param_count(net) * sizeof(float), stream), "memset");
         return 0;
     }
+    BwdShapePlan pl{};
     if (int rc = plan_backward(net, B, d, E, &pl)) return rc;
     if (!x || !h || !g || !cc_w || !cc_s) return umnn_fail(UMNN_EINVAL, "backward: x, h, g, cc_w, cc_s must be non-null");
     if (!workspace || workspace_bytes < pl.ws_total)
         return umnn_fail(UMNN_EINVAL, "backward: workspace smaller than umnn_cc_backward_workspace_bytes()");
+    const BwdRoute rt = bwd_route(pl, nb_steps, inv_f != 0, g_fx != nullptr, z2_saved != nullptr, true, bwd_options());
+    if (rt.error) return umnn_fail(UMNN_EUNSUPPORTED, rt.error);
     BwdArgs& a = pl.a;
-    const int L = a.m.n_linear - 1, H1 = net->widths[1];
+    const int H1 = net->widths[1];
     char* ws = (char*)workspace;
     a.x0 = x0; a.x = x; a.h = h; a.g = g; a.gfx = g_fx; a.ccw = cc_w; a.ccs = cc_s;
     a.dx0 = dx0; a.dx = dx; a.n = nb_steps;
@@ -891,52 +734,33 @@ static int backward_impl(const umnn_mlp* net, const umnn_io* io, const void* x0_
     a.partials = (float*)(ws + pl.ws_partials);
     a.dc = (float*)(ws + pl.ws_dc);
     a.scal = (unsigned*)(ws + pl.ws_scal);
-    a.z2_saved = (pl.ws_front_bytes > 0 && umnn_options().bwd_precision == UMNN_PRECISION_BF16X3) ? z2_saved : nullptr;
-    // (a call the three-stage kernels do not serve -- tiny batches, bwd_precision fp32 -- simply recomputes z_2: the buffer is ignored)
+    a.z2_saved = rt.use_z2 ? z2_saved : nullptr;
+    a.ns = rt.ns;
     float* p0 = (float*)(ws + pl.ws_p0);
     if (int rc = umnn_check(hipMemsetAsync(a.partials, 0, (size_t)pl.nwaves * a.n_params * 4, stream), "memset partials")) return rc;
 
-    // ---- bf16-split kernels (default) where the shape allows; otherwise / on request the fp32-MFMA kernels below
-    bool done = false;
-    int ns_used = pl.ns > nb_steps + 1 ? nb_steps + 1 : pl.ns;
-    a.ns = ns_used;
-    if (pl.ws_front_bytes > 0) {
-        a.ns = 1;
-        const int rc = umnn_options().bwd_precision == UMNN_PRECISION_BF16X3
-                           ? umnn_launch_backward_front(a, net, pl.nblocks, ws + pl.ws_front, pl.ws_front_bytes, stream)
-                           : umnn_launch_backward_front_p3(a, net, pl.nblocks, ws + pl.ws_front, pl.ws_front_bytes, stream);
-        if (rc == 0) { done = true; ns_used = 1; }
-        else if (rc != UMNN_EUNSUPPORTED) return rc;
-        else a.ns = ns_used;
+    // ---- the main pass: the family cc_bwd_plan.h named
+    switch (rt.family) {
+    case BWD_FAMILY_FRONT:
+        if (int rc = rt.front.npb == 2 ? umnn_launch_backward_front(a, net, rt, ws + pl.ws_front, stream)
+                                       : umnn_launch_backward_front_p3(a, net, rt, ws + pl.ws_front, stream)) return rc;
+        break;
+    case BWD_FAMILY_FP32:
+        // the EDGE pass (with as many dW layers as its variant holds), then the remaining layers
+        for (int pass = 0; pass < rt.npasses; ++pass) {
+            const BwdFp32Pass& p = rt.pass[pass];
+            const bwd_kernel_t fn = kBwdFp32Kernels[p.variant];
+            a.l_lo = p.l_lo;
+            a.scratch_per_wave = (p.nacc + 1) * pl.tmax * 256;
+            if (int rc = umnn_allow_lds((const void*)fn, p.lds_bytes)) return rc;
+            if (int rc = umnn_bwd_launch(stream, pass == 0 ? umnn_bwd_flops(net, nb_steps, a.NI) : 0.0, kBwdFp32Variants[p.variant].name, "cc_bwd launch",
+                                         [&] { hipLaunchKernelGGL(fn, dim3(rt.nblocks), dim3(64 * rt.wpb), p.lds_bytes, stream, a); })) return rc;
+        }
+        break;
+    default:
+        if (int rc = umnn_launch_backward_bf16(a, net, rt, stream)) return rc;
     }
-    int nslices = pl.nwaves;              // d_theta slices the main pass wrote (the reduction reads no more than that)
-    if (!done && umnn_options().bwd_precision == UMNN_PRECISION_BF16X3) {
-        int nw = 0;
-        const int rc = umnn_launch_backward_bf16(a, net, pl.nblocks, &nw, stream);
-        if (rc == 0) { done = true; if (nw > 0 && nw < nslices) nslices = nw; }
-        else if (rc != UMNN_EUNSUPPORTED) return rc;
-    }
-    // ---- passes: the EDGE pass (with as many dW layers as its variant holds), then the remaining layers
-    const int T = pl.tmax;
-    const int nacc_main = best_nacc(T, 1, pl.ksu), nacc_rest = best_nacc(T, 0, pl.ksu);
-    if (nacc_main < 0 || nacc_rest < 1) return umnn_fail(UMNN_EUNSUPPORTED, "backward: no kernel variant for this width");
-    int l_next = 1;
-    for (int pass = 0; !done && (pass == 0 || l_next < L); ++pass) {
-        const int nacc = pass == 0 ? nacc_main : nacc_rest;
-        const BwdVariant* v = find_bwd(T, nacc, pass == 0 ? 1 : 0, pl.ksu);
-        if (!v) return umnn_fail(UMNN_EUNSUPPORTED, "backward: no kernel variant for this width");
-        a.l_lo = l_next;
-        a.scratch_per_wave = (nacc + 1) * T * 256;
-        const size_t lds_bytes = pl.lds_bytes_for(nacc, pl.wpb);
-        if (lds_bytes > 160 * 1024) return umnn_fail(UMNN_EUNSUPPORTED, "backward: weight images exceed 160 KiB of LDS");
-        if (int rc = umnn_allow_lds((const void*)v->fn, lds_bytes)) return rc;
-        umnn_prof_begin(stream);
-        hipLaunchKernelGGL(v->fn, dim3(pl.nblocks), dim3(64 * pl.wpb), lds_bytes, stream, a);
-        umnn_prof_end(stream, pass == 0 ? 3.0 * umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI : 0.0, UMNN_PROF_BACKWARD);
-        umnn_note_launch(v->name);
-        if (int rc = umnn_check(hipGetLastError(), "cc_bwd launch")) return rc;
-        l_next += nacc;
-    }
+    const int ns_used = rt.ns, nslices = rt.nslices;     // (node-range split in force; d_theta slices the main pass wrote: the reduction reads no more)
 
     // ---- finishing kernels
     umnn_prof_begin(stream);

@@ -26,10 +26,7 @@
 // This file builds twice: as it is (two bf16 pieces in the delta chain and the dW products: bwd_precision = bf16x3), and through
 // cc_backward_front_p3.hip with UMNN_BWD_NPB = 3 (three pieces / six cross terms everywhere: fp32-level, what bwd_precision = fp32
 // gets for this family -- no workgroup pipeline there, the one-pass middle kernel).
-#include "cc_bwd_bf16_kernel.h"
-#if UMNN_BWD_NPB == 2
-#include "cc_bwd_ws16_kernel.h"      // (the workgroup pipelines; the fp16 helpers of stage A on fp16 pieces)
-#endif
+#include "cc_bwd_plan.h"      // (with the kernel headers: two-piece build, also the workgroup pipelines and the fp16 helpers of stage A on fp16 pieces)
 
 namespace UMNN_BWD_NS {
 struct FrontArgs {
@@ -809,99 +806,51 @@ __global__ __launch_bounds__(2 * UMNN_BLOCK, 1) void cc_front_bwd16_kernel(const
 
 // ------------------------------------------------------------------------------------------ host side
 typedef void (*front_kernel_t)(const FrontArgs);
-typedef void (*mid_kernel_t)(const BwdBf16Args);
-#if UMNN_BWD_NPB == 2
 struct FrontVariant { int t1, nl2; front_kernel_t fwd, bwd, fwd16, bwd2, bwd16; };
+#if UMNN_BWD_NPB == 2
 #define FRONT_VARIANT(T, N) {T, N, cc_front_fwd_kernel<T, N>, cc_front_bwd_kernel<T, N>, cc_front_fwd16_kernel<T, N>, cc_front_bwd2_kernel<T, N>, cc_front_bwd16_kernel<T, N>}
 #else
-struct FrontVariant { int t1, nl2; front_kernel_t fwd, bwd, fwd16, bwd2, bwd16; };
 #define FRONT_VARIANT(T, N) {T, N, cc_front_fwd_kernel<T, N>, cc_front_bwd_kernel<T, N>, nullptr, nullptr, nullptr}
 #endif
 static const FrontVariant kFrontVariants[] = {
     FRONT_VARIANT(5, 13), FRONT_VARIANT(6, 13), FRONT_VARIANT(7, 13), FRONT_VARIANT(8, 13),
     FRONT_VARIANT(5, 0), FRONT_VARIANT(6, 0), FRONT_VARIANT(7, 0), FRONT_VARIANT(8, 0),
 };
-struct MidVariant { int lh, nrl; mid_kernel_t fn; const char* name; };
+// the middle stage: the one-pass kernel on the net from hidden layer 2 on, or (two-piece build) the weight-stationary workgroup
+// pipeline of cc_bwd_ws_kernel.h; its build on fp16 pieces is instantiated in cc_backward_bf16.hip under that file's scheduling flags
 #if UMNN_BWD_NPB == 2
-#define MID_VARIANT(LHH, NR) { LHH, NR, cc_bwd_bf16_kernel<LHH, true, NR, true>, "cc_bwd_bf16<L=" #LHH ",EDGE=1,LIVE=" #NR ",FRONT>" }
-#else
-#define MID_VARIANT(LHH, NR) { LHH, NR, cc_bwd_bf16_kernel<LHH, true, NR, true>, "cc_bwd_bf16x6<L=" #LHH ",EDGE=1,LIVE=" #NR ",FRONT>" }
-#endif
-static const MidVariant kMidVariants[] = { MID_VARIANT(4, 13), MID_VARIANT(3, 13), MID_VARIANT(2, 13),
-                                           MID_VARIANT(4, 0), MID_VARIANT(3, 0), MID_VARIANT(2, 0) };
-// the middle stage as a weight-stationary workgroup pipeline (cc_bwd_ws_kernel.h): four hidden layers after the cut, chunks
-// of at least four tiles per workgroup
-#if UMNN_BWD_NPB == 2
-static const MidVariant kMidWsVariants[] = {
-    { 4, 13, cc_bwd_ws_kernel<13, true>, "cc_bwd_bf16<L=4,LIVE=13,WS,FRONT>" },
-    { 4, 0, cc_bwd_ws_kernel<0, true>, "cc_bwd_bf16<L=4,LIVE=0,WS,FRONT>" },
-};
-#endif
-// the same on fp16 pieces (cc_bwd_ws16_kernel.h, instantiated in cc_backward_bf16.hip under that file's scheduling flags):
-// single-chunk calls only -- its d_theta slices are written, not accumulated, so that the bf16 pipeline queued behind it as the
-// overflow fallback can rewrite them
-int umnn_ws16_front_eligible(const BwdArgs& base, int nrl, const char** name);
-int umnn_ws16_front_prepare(const BwdArgs& base, int nblocks_max, hipStream_t stream);
-int umnn_ws16_front_launch(const BwdBf16Args& mid, int nrl, int nblocks, hipStream_t stream);
-
-// Does this net belong to the family?  hidden layer 1: 5..8 tiles; hidden layers 2..L: three or four tiles at most (zero-padded
-// to four), 2..4 of them.
-#if UMNN_BWD_NPB == 2
-int umnn_backward_front_shape(const MlpDev& m) {
-    const int L = m.n_linear - 1;
-    if (L < 3 || L > 5) return 0;
-    if (m.t_out[1] < 5 || m.t_out[1] > 8) return 0;
-    for (int l = 2; l <= L; ++l) if (m.t_out[l] > BT) return 0;
-    return 1;
-}
-
-// bytes of HBM scratch the staged backward wants for B*d integrals (nb_steps is not known when the workspace is sized: the
-// chunking adapts to whatever n the call brings)
-long long umnn_backward_front_scratch_bytes(const MlpDev& m, long long NI) {
-    const long long tiles = (NI + 15) / 16;
-    const long long nl2 = (m.width[2] + 1 + 3) / 4;
-    const long long per_tile = (2LL * 257 + 1) * nl2 * 64 * 4;          // sized for n = 256
-    const long long want = tiles * per_tile, cap = 2LL << 30;
-    return want < cap ? want : cap;
-}
+#define UMNN_FRONT_MID_KIND BWD_KIND_MID
+#define MID_ROW(LHH, NR, ...) { BWD_KIND_MID, LHH, NR, cc_bwd_bf16_kernel<LHH, true, NR, true> },
+#define MID_WS_ROW(LHH, NR, ...) { BWD_KIND_MID_WS, LHH, NR, cc_bwd_ws_kernel<NR, true> },
+static const BwdBf16Variant kMidVariants[] = { UMNN_BWD_LOOP_SHAPES(MID_ROW, ) UMNN_BWD_WS_SHAPES(MID_WS_ROW, ) };
 #define UMNN_FRONT_LAUNCH umnn_launch_backward_front
 #else
-int umnn_backward_front_shape(const MlpDev& m);
+#define UMNN_FRONT_MID_KIND BWD_KIND_MID_P3
+#define MID_ROW(LHH, NR, ...) { BWD_KIND_MID_P3, LHH, NR, cc_bwd_bf16_kernel<LHH, true, NR, true> },
+static const BwdBf16Variant kMidVariants[] = { UMNN_BWD_LOOP_SHAPES(MID_ROW, ) };
 #define UMNN_FRONT_LAUNCH umnn_launch_backward_front_p3
 #endif
 
-// Runs the three stages chunk by chunk.  `base` is the fully populated BwdArgs of umnn_cc_backward (partials zeroed).
-int UMNN_FRONT_LAUNCH(const BwdArgs& base, const umnn_mlp* net, int nblocks_max, void* scratch, long long scratch_bytes,
-                               hipStream_t stream) {
+// Runs the three stages of a BWD_FAMILY_FRONT route chunk by chunk.
+int UMNN_FRONT_LAUNCH(const BwdArgs& base, const umnn_mlp* net, const BwdRoute& rt, void* scratch, hipStream_t stream) {
     const MlpDev& m = base.m;
-    const int L = m.n_linear - 1, n = base.n;
-    if (!umnn_backward_front_shape(m)) return UMNN_EUNSUPPORTED;
-    const int T1 = m.t_out[1], LH = L - 1;
-    const int nl2 = (m.width[2] + 1 + 3) / 4;
+    const BwdFrontRoute& f = rt.front;
+    const int n = base.n, nl2 = f.nl2, LH = rt.L, nblocks_max = rt.nblocks;
     const FrontVariant* fv = nullptr;
-    for (const FrontVariant& v : kFrontVariants) if (v.t1 == T1 && v.nl2 == (nl2 == 13 ? 13 : 0)) fv = &v;
-    int nrl = m.ks_in[2];
-    for (int l = 2; l <= L; ++l) if (m.ks_in[l] != nrl) nrl = 0;
-    if (nrl != 13) nrl = 0;
-    const MidVariant* mv = nullptr;
-    for (const MidVariant& v : kMidVariants) if (v.lh == LH && v.nrl == nrl) { mv = &v; break; }
-    if (!fv || !mv) return UMNN_EUNSUPPORTED;
-
-    const long long tiles = (base.NI + 15) / 16;
-    // (z_2 left by the training forward: the scratch holds delta_2 and the tangent only, stage A runs for the tangent element alone)
-    const bool saved = base.z2_saved != nullptr;
-    const long long per_tile = ((saved ? 1LL : 2LL) * (n + 1) + (base.gfx ? 1 : 0)) * nl2 * 64 * 4;
-    long long chunk = scratch_bytes / per_tile;
-    if (chunk < 1 || !scratch) return UMNN_EUNSUPPORTED;
-    if (chunk > tiles) chunk = tiles;
-    else {
-        // several chunks: equal shares, rounded up to whole rounds of the persistent grid where the scratch allows (a chunk
-        // of 3.06 rounds costs 4)
-        const long long nchunks = (tiles + chunk - 1) / chunk, waves = (long long)nblocks_max * UMNN_WAVES_PER_BLOCK;
-        long long even = (tiles + nchunks - 1) / nchunks;
-        const long long rounded = (even + waves - 1) / waves * waves;
-        chunk = rounded <= chunk ? rounded : even;
-    }
+    for (const FrontVariant& v : kFrontVariants) if (v.t1 == f.T1 && v.nl2 == f.nl2_variant) fv = &v;
+    const bwd_bf16_kernel_t mid_fn = bwd_bf16_fn(kMidVariants, UMNN_FRONT_MID_KIND, LH, rt.nrl);
+    const bwd_bf16_kernel_t ws_fn = f.mid_ws ? bwd_bf16_fn(kMidVariants, BWD_KIND_MID_WS, LH, rt.nrl) : nullptr;
+    const front_kernel_t stage_c = !fv ? nullptr : f.stage_c == BWD_STAGE_C_BWD ? fv->bwd : fv->bwd2;
+    if (rt.family != BWD_FAMILY_FRONT || f.npb != NPB || !fv || !mid_fn || !stage_c || f.chunk < 1 || !scratch || (f.mid_ws && !ws_fn) ||
+        (f.mid_ws16 && !(f.mid_ws && fv->fwd16 && base.scal)) || (f.stage_c == BWD_STAGE_C_BWD16 && !fv->bwd16))
+        return umnn_fail(UMNN_EINVAL, kBwdRouteError);
+    const size_t lds_stage_c = f.stage_c == BWD_STAGE_C_BWD ? f.lds_c : f.lds_c2;
+    if (int rc = umnn_allow_lds((const void*)fv->fwd, f.lds_a)) return rc;
+    if (f.mid_ws16) { if (int rc = umnn_allow_lds((const void*)fv->fwd16, f.lds_a)) return rc; }
+    if (int rc = umnn_allow_lds((const void*)mid_fn, f.lds_mid)) return rc;
+    if (int rc = umnn_allow_lds((const void*)stage_c, lds_stage_c)) return rc;
+    if (f.stage_c == BWD_STAGE_C_BWD16) { if (int rc = umnn_allow_lds((const void*)fv->bwd16, f.lds_c2)) return rc; }
+    if (ws_fn) { if (int rc = umnn_allow_lds((const void*)ws_fn, f.lds_ws)) return rc; }
 
     // ---- the middle stage sees the net from hidden layer 2 on
     BwdBf16Args mid;
@@ -915,104 +864,52 @@ int UMNN_FRONT_LAUNCH(const BwdArgs& base, const umnn_mlp* net, int nblocks_max,
         for (int l = 1; l <= s.n_linear - 1; ++l) { s.t_out[l] = m.t_out[l + 1]; s.ks_in[l] = m.ks_in[l + 1]; s.t_mfma[l] = m.t_mfma[l + 1]; }
         for (int l = 0; l < s.n_linear; ++l) { mid.b.poffW[l] = base.poffW[l + 1]; mid.b.poffb[l] = base.poffb[l + 1]; }
     }
-    int off16 = 0;
-    for (int l = 1; l < LH; ++l) { mid.off_fwd[l] = off16; off16 += BT * BKS * NPF * FRAG; }
-    for (int l = 1; l < LH; ++l) { mid.off_tr[l] = off16; off16 += BT * BKS * NPB * FRAG; }
-    mid.off_trtile = off16;
-    // (waves per workgroup of the one-pass middle kernel: four, or as many as leave room for their transpose tiles next to the weight
-    // images -- the six-term build with four hidden layers after the cut holds two; the grid grows by the same factor, so the
-    // d_theta slices stay one per wave of the plan)
-    int wpb_mid = UMNN_WAVES_PER_BLOCK;
-    while (wpb_mid > 1 && (size_t)(off16 + wpb_mid * NPB * 16 * TRS) * sizeof(unsigned short) > 160 * 1024) wpb_mid >>= 1;
-    off16 += wpb_mid * NPB * 16 * TRS;
-    const size_t lds_mid = (size_t)off16 * sizeof(unsigned short);
-    const size_t lds_a = ((size_t)BT * (T1 / 2) * NPF * FRAG + (T1 & 1 ? BT * NPF * 256 : 0)) * sizeof(unsigned short);
-    const size_t lds_c = (size_t)T1 * BKS * NPB * FRAG * sizeof(unsigned short);
-    if (lds_mid > 160 * 1024 || lds_a > 160 * 1024 || lds_c > 160 * 1024) return UMNN_EUNSUPPORTED;
-    if (int rc = umnn_allow_lds((const void*)fv->fwd, lds_a)) return rc;
-    if (fv->fwd16) { if (int rc = umnn_allow_lds((const void*)fv->fwd16, lds_a)) return rc; }
-    if (int rc = umnn_allow_lds((const void*)mv->fn, lds_mid)) return rc;
-    if (int rc = umnn_allow_lds((const void*)fv->bwd, lds_c)) return rc;
-    // stage C with two waves per tile (two-piece build): UMNN_FRONT_BWD2=0 / option front_bwd2 = 0 keeps one wave per tile
-    const bool c2 = fv->bwd2 != nullptr && umnn_options().front_bwd2 != 0;
-    const size_t lds_c2 = lds_c + (size_t)2 * UMNN_WAVES_PER_BLOCK * 2 * (NPB * 16 * TRS) * sizeof(unsigned short);      // + the waves' operand tiles
-    if (c2) { if (lds_c2 > 160 * 1024) return UMNN_EUNSUPPORTED; if (int rc = umnn_allow_lds((const void*)fv->bwd2, lds_c2)) return rc; }
-    // ... and on fp16 pieces behind the fp16 middle stage (front_bwd2 = 2 keeps bf16 pieces there)
-    const bool c16 = c2 && fv->bwd16 != nullptr && umnn_options().front_bwd2 == 1;
-    if (c16) { if (int rc = umnn_allow_lds((const void*)fv->bwd16, lds_c2)) return rc; }
-    const MidVariant* wv = nullptr;
-    size_t lds_ws = 0;
-#if UMNN_BWD_NPB == 2
-    if (umnn_options().bwd_ws && LH == 4)
-        for (const MidVariant& v : kMidWsVariants) if (v.nrl == nrl) { wv = &v; break; }
-    lds_ws = (size_t)WS_LDS_USHORTS * sizeof(unsigned short);
-    if (wv) { if (int rc = umnn_allow_lds((const void*)wv->fn, lds_ws)) return rc; }
-#endif
-    bool used_ws = false;
-    // fp16 pieces for the middle stage: the rule of umnn_launch_backward_bf16 (bwd_ws16 = 1: large launches only; here from 2^21 node
-    // evaluations, the middle stage recomputes one layer less than the whole-net pipeline; 2: whenever eligible), one chunk
-    const char* hv = nullptr;
-    {
-        const int w16 = umnn_options().bwd_ws16;
-        const bool size_ok = w16 == 2 || (w16 == 1 && base.NI * (long long)(n + 1) >= (1LL << 21));
-        if (wv && size_ok && chunk == tiles && tiles >= 4LL * nblocks_max)
-            if (int rc = umnn_ws16_front_eligible(base, nrl, &hv)) return rc;
-    }
-
+    bwd_onepass_images(LH, NPB, &mid);
     FrontArgs fa;
     fa.b = base;
     fa.only_if = nullptr;
-    fa.tz_only = saved ? 1 : 0;
+    fa.tz_only = f.saved ? 1 : 0;
     fa.b.ns = 1;
     mid.b.ns = 1;
     mid.b.l_lo = 1;
     fa.nl2 = mid.nl2 = nl2;
     // (the scalar memset + cotangent-scale pre-pass first: an error return must not leave a profiling bracket open)
-    if (hv) { if (int rc = umnn_ws16_front_prepare(base, nblocks_max, stream)) return rc; }
-    umnn_prof_begin(stream);
-    for (long long t0 = 0; t0 < tiles; t0 += chunk) {
-        const long long nt = tiles - t0 < chunk ? tiles - t0 : chunk;
-        float* z2 = saved ? const_cast<float*>(base.z2_saved) + (size_t)t0 * (n + 1) * nl2 * 64 : (float*)scratch;
-        float* d2 = saved ? (float*)scratch : z2 + (size_t)nt * (n + 1) * nl2 * 64;
-        const bool run_a = !saved || base.gfx != nullptr;      // stage A: everything, or (z_2 saved) the tangent element of the g_fx term
-        float* tz2 = base.gfx ? d2 + (size_t)nt * (n + 1) * nl2 * 64 : nullptr;
-        int nblocks = nblocks_max;
-        if ((long long)nblocks * UMNN_WAVES_PER_BLOCK > nt) nblocks = (int)((nt + UMNN_WAVES_PER_BLOCK - 1) / UMNN_WAVES_PER_BLOCK);
-        if (nblocks < 1) nblocks = 1;
-        fa.z2 = z2; fa.d2 = d2; fa.tz2 = tz2; fa.grp0 = (unsigned)t0; fa.b.ngroups = (unsigned)nt; fa.accumulate = t0 > 0;
-        mid.z2 = z2; mid.d2 = d2; mid.tz2 = tz2; mid.grp0 = (unsigned)t0; mid.b.ngroups = (unsigned)nt; mid.accumulate = t0 > 0;
-#if UMNN_BWD_NPB == 2
-        if (hv) {
-            // (stages A and B on fp16 pieces, then their bf16 builds behind them that only run if a piece overflowed -- the launch
-            // flag, raised by the checks of stage B, which also see a non-finite z_2 from stage A: same outputs, rewritten)
-            if (run_a) hipLaunchKernelGGL(fv->fwd16, dim3(2 * nblocks), dim3(UMNN_BLOCK), lds_a, stream, fa);      // (two workgroups per CU)
-            mid.scal = base.scal; mid.only_if = nullptr;
-            if (int rc = umnn_ws16_front_launch(mid, nrl, nblocks_max, stream)) { umnn_prof_end(stream, 0.0, UMNN_PROF_BACKWARD); return rc; }
-            fa.only_if = mid.only_if = base.scal + 3;            // (Ws16Scal::flag)
-            if (run_a) hipLaunchKernelGGL(fv->fwd, dim3(nblocks), dim3(UMNN_BLOCK), lds_a, stream, fa);
-            hipLaunchKernelGGL(wv->fn, dim3(nblocks_max), dim3(64 * WS_WAVES), lds_ws, stream, mid);
+    if (f.mid_ws16) { if (int rc = umnn_ws16_prepare(base, rt.cotmax_blocks, stream)) return rc; }
+    int rc_mid = 0;
+    const int rc = umnn_bwd_launch(stream, umnn_bwd_flops(net, n, base.NI), rt.name, "cc_bwd front launch", [&] {
+        for (long long t0 = 0; t0 < f.tiles && !rc_mid; t0 += f.chunk) {
+            const long long nt = f.tiles - t0 < f.chunk ? f.tiles - t0 : f.chunk;
+            float* z2 = f.saved ? const_cast<float*>(base.z2_saved) + (size_t)t0 * (n + 1) * nl2 * 64 : (float*)scratch;
+            float* d2 = f.saved ? (float*)scratch : z2 + (size_t)nt * (n + 1) * nl2 * 64;
+            const bool run_a = !f.saved || base.gfx != nullptr;      // stage A: everything, or (z_2 saved) the tangent element of the g_fx term
+            float* tz2 = base.gfx ? d2 + (size_t)nt * (n + 1) * nl2 * 64 : nullptr;
+            const int nblocks = bwd_clamp_blocks(nblocks_max, nt, UMNN_WAVES_PER_BLOCK);
+            fa.z2 = z2; fa.d2 = d2; fa.tz2 = tz2; fa.grp0 = (unsigned)t0; fa.b.ngroups = (unsigned)nt; fa.accumulate = t0 > 0;
+            mid.z2 = z2; mid.d2 = d2; mid.tz2 = tz2; mid.grp0 = (unsigned)t0; mid.b.ngroups = (unsigned)nt; mid.accumulate = t0 > 0;
+            const int stage_b = f.mid_stage(nt, nblocks_max);
+            if (stage_b == BWD_MID_WS16) {
+                // (stages A and B on fp16 pieces, then their bf16 builds behind them that only run if a piece overflowed -- the launch
+                // flag, raised by the checks of stage B, which also see a non-finite z_2 from stage A: same outputs, rewritten)
+                if (run_a) hipLaunchKernelGGL(fv->fwd16, dim3(2 * nblocks), dim3(UMNN_BLOCK), f.lds_a, stream, fa);      // (two workgroups per CU)
+                mid.scal = base.scal; mid.only_if = nullptr;
+                if ((rc_mid = umnn_ws16_mid_launch(mid, rt.nrl, nblocks_max, f.lds_ws16, stream))) break;
+                fa.only_if = mid.only_if = base.scal + 3;            // (Ws16Scal::flag)
+            }
+            if (run_a) hipLaunchKernelGGL(fv->fwd, dim3(nblocks), dim3(UMNN_BLOCK), f.lds_a, stream, fa);
+            if (stage_b == BWD_MID_LOOP)
+                hipLaunchKernelGGL(mid_fn, dim3(nblocks * (UMNN_WAVES_PER_BLOCK / f.wpb_mid)), dim3(64 * f.wpb_mid), f.lds_mid, stream, mid);
+            else
+                hipLaunchKernelGGL(ws_fn, dim3(nblocks_max), dim3(64 * f.wpb_ws), f.lds_ws, stream, mid);
             fa.only_if = nullptr;
-            used_ws = true;
-        } else if (wv && nt >= 4LL * nblocks_max) {
-            if (run_a) hipLaunchKernelGGL(fv->fwd, dim3(nblocks), dim3(UMNN_BLOCK), lds_a, stream, fa);
-            hipLaunchKernelGGL(wv->fn, dim3(nblocks_max), dim3(64 * WS_WAVES), lds_ws, stream, mid);
-            used_ws = true;
-        } else
-#endif
-        {
-            if (run_a) hipLaunchKernelGGL(fv->fwd, dim3(nblocks), dim3(UMNN_BLOCK), lds_a, stream, fa);
-            hipLaunchKernelGGL(mv->fn, dim3(nblocks * (UMNN_WAVES_PER_BLOCK / wpb_mid)), dim3(64 * wpb_mid), lds_mid, stream, mid);
+            if (f.stage_c == BWD_STAGE_C_BWD16) {
+                // (fp16 pieces, then the bf16 build that only runs if the launch flag is up -- raised by stage B's checks or by this stage's own)
+                hipLaunchKernelGGL(fv->bwd16, dim3(nblocks), dim3(2 * UMNN_BLOCK), f.lds_c2, stream, fa);
+                fa.only_if = base.scal + 3;            // (Ws16Scal::flag)
+            }
+            if (f.stage_c == BWD_STAGE_C_BWD) hipLaunchKernelGGL(fv->bwd, dim3(nblocks), dim3(UMNN_BLOCK), f.lds_c, stream, fa);
+            else hipLaunchKernelGGL(fv->bwd2, dim3(nblocks), dim3(2 * UMNN_BLOCK), f.lds_c2, stream, fa);
+            fa.only_if = nullptr;
         }
-        if (c16 && hv && used_ws) {
-            // (fp16 pieces, then the bf16 build that only runs if the launch flag is up -- raised by stage B's checks or by this stage's own)
-            hipLaunchKernelGGL(fv->bwd16, dim3(nblocks), dim3(2 * UMNN_BLOCK), lds_c2, stream, fa);
-            fa.only_if = base.scal + 3;            // (Ws16Scal::flag)
-            hipLaunchKernelGGL(fv->bwd2, dim3(nblocks), dim3(2 * UMNN_BLOCK), lds_c2, stream, fa);
-            fa.only_if = nullptr;
-        } else if (c2) hipLaunchKernelGGL(fv->bwd2, dim3(nblocks), dim3(2 * UMNN_BLOCK), lds_c2, stream, fa);
-        else hipLaunchKernelGGL(fv->bwd, dim3(nblocks), dim3(UMNN_BLOCK), lds_c, stream, fa);
-    }
-    umnn_prof_end(stream, 3.0 * umnn_cc_forward_flops_per_integral(net, n) * (double)base.NI, UMNN_PROF_BACKWARD);
-    umnn_note_launch(hv ? hv : used_ws ? wv->name : mv->name);
-    return umnn_check(hipGetLastError(), "cc_bwd front launch");
+    });
+    return rc_mid ? rc_mid : rc;
 }

@@ -40,11 +40,14 @@ struct BwdArgs {
 __device__ __forceinline__ int perm16(int rho) { return 4 * (rho & 3) + (rho >> 2); }
 
 
-// staged backward for nets with a wide first hidden layer (cc_backward_front.hip)
-int umnn_backward_front_shape(const MlpDev& m);
-long long umnn_backward_front_scratch_bytes(const MlpDev& m, long long NI);
-int umnn_launch_backward_front(const BwdArgs& base, const umnn_mlp* net, int nblocks_max, void* scratch, long long scratch_bytes,
-                               hipStream_t stream);
-// (the same with three pieces in every product: cc_backward_front_p3.hip, bwd_precision = fp32)
-int umnn_launch_backward_front_p3(const BwdArgs& base, const umnn_mlp* net, int nblocks_max, void* scratch, long long scratch_bytes,
-                                  hipStream_t stream);
+// One main-pass launch of the backward: profiling bracket (flops: 3 x the forward's for the pass that does the work), the launch
+// itself, its name for umnn_last_kernel_name_of(UMNN_PROF_BACKWARD), the launch check.
+template <class Launch>
+inline int umnn_bwd_launch(hipStream_t stream, double flops, const char* name, const char* what, Launch&& launch) {
+    umnn_prof_begin(stream);
+    launch();
+    umnn_prof_end(stream, flops, UMNN_PROF_BACKWARD);
+    umnn_note_launch(name);
+    return umnn_check(hipGetLastError(), what);
+}
+inline double umnn_bwd_flops(const umnn_mlp* net, int n, long long NI) { return 3.0 * umnn_cc_forward_flops_per_integral(net, n) * (double)NI; }
