@@ -273,7 +273,7 @@ double umnn_cc_forward_flops_per_integral(const umnn_mlp* net, int nb_steps);
 const char* umnn_last_error(void);
 int umnn_version(void);
 long long umnn_launch_count(void);          /* quadrature kernels (forward / backward / finishing) launched by this process so far */
-long long umnn_made_launch_count(void);     /* launches of the fused conditioner kernel (umnn_made_mlp_forward) so far */
+long long umnn_made_launch_count(void);     /* launches of the conditioner kernels (umnn_made_mlp_forward, umnn_made_linear_forward, umnn_made_step) so far */
 const char* umnn_last_made_kernel_name(void);
 const char* umnn_last_kernel_name(void);    /* variant picked by the last forward/backward */
 /* Times `reps` back-to-back umnn_cc_forward launches with hipEvents recorded on `stream`
@@ -433,6 +433,32 @@ int umnn_made_linear_forward(const void* W_frag, const float* bias, int K, int N
  * of scratch, row_blocks from umnn_made_relu_bwd_bias_row_blocks(B, N). */
 int umnn_made_relu_bwd_bias_row_blocks(long long B, int N);
 int umnn_made_relu_bwd_bias(float* g, const float* relu_out, long long B, int N, float* partial, int row_blocks, float* gb, void* stream);
+
+/* One step of the PROGRESSIVE conditioner of the sequential sampling walk (csrc/made_step.hip; the reference re-runs the whole MADE
+ * before every dimension, UMNNMAF.py:195-231).  With the natural input order a hidden unit of degree m is final once the inputs of
+ * degree <= m are, so it is computed once per block and kept in a standing buffer.  The plan holds every hidden layer SORTED BY
+ * DEGREE (stable): W[l] [width[l], ldk[l]] the masked fp32 weight (mask * weight, exact zeros kept) permuted on both sides into that
+ * order, K axis zero-padded to ldk[l] (a multiple of 4; ldk[0] >= c + d with columns [context | x], ldk[l] >= width[l - 1]); b[l] the
+ * permuted bias; W[n_hidden] [d][E][ldk[n_hidden]] / b[n_hidden] [d][E] the output layer regrouped by flow dimension (kept dimensions
+ * only for a conditional MADE: c context inputs, d flow dimensions).  steps: HOST table [d][n_hidden + 1][3] of (first new unit, end
+ * of new units, input prefix length) per step and layer; the output layer's entry is (0, E, prefix).
+ * Step j: for each hidden layer the new units u in [lo, hi):  act[l][b, u] = relu(W[l][u, :prefix] . in[b, :prefix] + b[l][u]) with
+ * in = [context | x[:, :j]] for layer 0 and act[l - 1] after it (row stride ldk[l + 1]); then h[b, e d + j] for e < E -- the layout
+ * umnn_cc_solve reads.  Never reads x[:, j:] nor a unit outside its prefix.  Exact fp32 products, fp32 accumulation in an order that
+ * depends on the prefix only (not on B, the grid or row_tiles: 0 auto | 1 | 2 | 4 tiles of 16 rows per workgroup).
+ * LDS bound: at most UMNN_MADE_STEP_MAX_NEW new units per hidden layer in one step (UMNN_EUNSUPPORTED beyond); B == 0 is a no-op. */
+#define UMNN_MADE_STEP_MAX_NEW 479
+typedef struct umnn_made_plan {
+    int n_hidden;
+    int d, c, E;
+    int width[UMNN_MADE_MAX_LAYERS];
+    int ldk[UMNN_MADE_MAX_LAYERS + 1];
+    const float* W[UMNN_MADE_MAX_LAYERS + 1];
+    const float* b[UMNN_MADE_MAX_LAYERS + 1];
+    const int* steps;
+} umnn_made_plan;
+int umnn_made_step(const umnn_made_plan* plan, int j, const float* context, const float* x, float* const* act, float* h,
+                   long long B, int row_tiles, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,7 +6,7 @@ stronger coupling between the dimensions, more Jacobi sweeps) --, and ``Monotoni
 of the g5 fixtures.  The jacobi rows carry the sweep count and the largest evaluation count of every sweep.
 
     python tools/invert_bench.py [--repeats 5] [--warmup 1] [--root TREE] [--out FILE.json] [--only c3,mnist,c3_made3,mnist_made3,monotonic,toy]
-                                 [--methods bracket,newton,jacobi]
+                                 [--methods bracket,newton,newton_progressive,jacobi] [--conditioner full|progressive]
 
 Device-synchronised wall time of whole calls (conditioner passes included), ``--warmup`` untimed calls of every method first, then
 ``--repeats`` rounds that alternate the methods, so drift hits both alike; every figure comes with its min / max / standard
@@ -24,6 +24,10 @@ the 2-D toy flow of bench.py (case ``toy``: 4096 x 2, one block); the jacobi pai
 sweep count eager jacobi needed with its default stop rule (row field ``sweeps``), ``capture_ms`` is the one-time cost of building the
 sampler (warm-up + capture).  Per-launch kernel time is
 a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/invert_bench.py --repeats 1 --only c3
+Row ``newton_progressive`` is ``invert(method="newton", conditioner="progressive")`` (under ``--graph`` also ``newton_progressive_graph``,
+its ``GraphedSampler`` replay); ``--conditioner`` sets the conditioner of the ``bracket`` and ``newton`` rows themselves (default "full").
+Every row carries ``made_launches``, the conditioner-kernel launches of its last call (progressive: d per block).  A tree without the
+option (``--root``) gives the other rows only.
 """
 import argparse
 import inspect
@@ -43,6 +47,7 @@ def main():
     ap.add_argument("--only", default=ap_default_only)
     ap.add_argument("--methods", default=ap_default_methods)
     ap.add_argument("--label", default="")
+    ap.add_argument("--conditioner", default="full", choices=["full", "progressive"], help="conditioner of the bracket and newton rows")
     ap.add_argument("--adj-tol", type=float, default=None, help="--grad: adj_tol of the rsample_backward row (default: the method's own)")
     ap.add_argument("--grad", action="store_true", help="time rsample + backward and the adjoint sweeps instead of the solves")
     ap.add_argument("--graph", action="store_true", help="time eager invert against GraphedSampler replays (newton and fixed-sweep jacobi)")
@@ -55,6 +60,10 @@ def main():
     dev = torch.device("cuda:0")
     has_newton = "method" in inspect.signature(umnn_amd.UMNNMAF.invert).parameters
     has_jacobi = "sweep_tol" in inspect.signature(umnn_amd.UMNNMAF.invert).parameters
+    has_progressive = "conditioner" in inspect.signature(umnn_amd.UMNNMAF.invert).parameters
+    if args.conditioner != "full" and not has_progressive:
+        raise SystemExit("--conditioner: this tree's invert has no such option")
+    cond = dict(conditioner=args.conditioner) if args.conditioner != "full" else {}
     only = set(args.only.split(","))
     methods = set(args.methods.split(","))
 
@@ -71,18 +80,20 @@ def main():
             for fn in fns.values():
                 sync_time(fn)
         ms = {k: [] for k in fns}
-        launches, kernels, outs = {}, {}, {}
+        launches, made_launches, kernels, outs = {}, {}, {}, {}
         for _ in range(args.repeats):
             for k, fn in fns.items():
-                n0 = _lib.lib().umnn_launch_count()
+                n0, m0 = _lib.lib().umnn_launch_count(), _lib.lib().umnn_made_launch_count()
                 t, outs[k] = sync_time(fn)
                 ms[k].append(t)
                 launches[k] = _lib.lib().umnn_launch_count() - n0
+                made_launches[k] = _lib.lib().umnn_made_launch_count() - m0
                 kernels[k] = _lib.lib().umnn_last_kernel_name().decode()
         rows = []
         for k, v in ms.items():
             rows.append(dict(case=case, method=k, label=args.label, mean_ms=statistics.mean(v), min_ms=min(v), max_ms=max(v),
-                             std_ms=statistics.pstdev(v), repeats=len(v), launches=launches[k], kernel=kernels[k], **extra(k, outs)))
+                             std_ms=statistics.pstdev(v), repeats=len(v), launches=launches[k], made_launches=made_launches[k],
+                             kernel=kernels[k], **extra(k, outs)))
             print(json.dumps(rows[-1]), flush=True)
         return rows
 
@@ -94,7 +105,7 @@ def main():
         only = set()
     if args.graph:
         results += graph_mode(args, umnn_amd, torch, dev, shapes, only if args.only != ap_default_only else {"c3", "mnist", "toy"},
-                              methods, measure, sync_time)
+                              methods, measure, sync_time, has_progressive, cond)
         only = set()
     with torch.no_grad():
         for case, c in [(name + tag, dict(c, made_gain=gain)) for name, c in shapes.items() for tag, gain in (("", 1.), ("_made3", 3.))]:
@@ -113,9 +124,11 @@ def main():
             z = blk(x)
             fns, state = {}, {}
             if "bracket" in methods:
-                fns["bracket"] = lambda: blk.invert(z, iter=10)
+                fns["bracket"] = lambda: blk.invert(z, iter=10, **cond)
             if has_newton and "newton" in methods:
-                fns["newton"] = lambda: blk.invert(z, method="newton")
+                fns["newton"] = lambda: blk.invert(z, method="newton", **cond)
+            if has_progressive and "newton_progressive" in methods:
+                fns["newton_progressive"] = lambda: blk.invert(z, method="newton", conditioner="progressive")
             if has_jacobi and "jacobi" in methods:
                 def jacobi():
                     xi, state["info"] = blk.invert(z, method="jacobi", return_info=True)
@@ -155,11 +168,11 @@ def main():
                            has_newton=has_newton, results=results), f, indent=1)
 
 
-ap_default_methods = "bracket,newton,jacobi"
+ap_default_methods = "bracket,newton,newton_progressive,jacobi"
 ap_default_only = "c3,mnist,c3_made3,mnist_made3,monotonic"
 
 
-def graph_mode(args, umnn_amd, torch, dev, shapes, only, methods, measure, sync_time):
+def graph_mode(args, umnn_amd, torch, dev, shapes, only, methods, measure, sync_time, has_progressive=False, cond={}):
     """The ``--graph`` rows: eager ``invert`` and the replay of a ``GraphedSampler`` on the same z, per method."""
     results = []
     shapes = dict(shapes, toy=dict(d=2, hd=[100] * 4, he=[100] * 4, E=10, n=50, B=4096))
@@ -174,10 +187,15 @@ def graph_mode(args, umnn_amd, torch, dev, shapes, only, methods, measure, sync_
             z = flow(x)
             fns, meta = {}, {}
             if "newton" in methods:
-                ms, sampler = sync_time(lambda: umnn_amd.GraphedSampler(flow, c["B"], method="newton"))
+                ms, sampler = sync_time(lambda: umnn_amd.GraphedSampler(flow, c["B"], method="newton", **cond))
                 meta["newton_graph"] = dict(capture_ms=ms)
-                fns["newton"] = lambda: flow.invert(z, method="newton")
+                fns["newton"] = lambda: flow.invert(z, method="newton", **cond)
                 fns["newton_graph"] = lambda sampler=sampler: sampler(z=z)
+            if has_progressive and "newton_progressive" in methods:
+                ms, psampler = sync_time(lambda: umnn_amd.GraphedSampler(flow, c["B"], method="newton", conditioner="progressive"))
+                meta["newton_progressive_graph"] = dict(capture_ms=ms)
+                fns["newton_progressive"] = lambda: flow.invert(z, method="newton", conditioner="progressive")
+                fns["newton_progressive_graph"] = lambda psampler=psampler: psampler(z=z)
             if "jacobi" in methods:
                 _, info = flow.invert(z, method="jacobi", return_info=True)
                 K = max(info["sweeps"])

@@ -118,6 +118,7 @@ SIGNATURES = {
     "umnn_made_mlp_forward_ex": (ctypes.c_int, [ctypes.c_void_p, _fp, _ll, _fp, ctypes.c_int, ctypes.c_int, _fp]),
     "umnn_made_linear_forward": (ctypes.c_int, [_fp, _fp, ctypes.c_int, ctypes.c_int, _fp, _fp, ctypes.c_int, _ll, ctypes.c_int, _fp,
                                                 ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp]),
+    "umnn_made_step": (ctypes.c_int, [ctypes.c_void_p, ctypes.c_int, _fp, _fp, ctypes.c_void_p, _fp, _ll, ctypes.c_int, _fp]),
 }
 
 MADE_MAX_LAYERS = 8
@@ -127,6 +128,17 @@ class MadeNet(ctypes.Structure):
     """struct umnn_made_net (include/umnn_cc.h)."""
     _fields_ = [("n_layers", ctypes.c_int), ("widths", ctypes.c_int * (MADE_MAX_LAYERS + 1)),
                 ("W", ctypes.c_void_p * MADE_MAX_LAYERS), ("b", ctypes.c_void_p * MADE_MAX_LAYERS)]
+
+
+class MadePlan(ctypes.Structure):
+    """struct umnn_made_plan (include/umnn_cc.h): the progressive conditioner's plan; ``steps`` is a HOST int32 table."""
+    _fields_ = [("n_hidden", ctypes.c_int), ("d", ctypes.c_int), ("c", ctypes.c_int), ("E", ctypes.c_int),
+                ("width", ctypes.c_int * MADE_MAX_LAYERS), ("ldk", ctypes.c_int * (MADE_MAX_LAYERS + 1)),
+                ("W", ctypes.c_void_p * (MADE_MAX_LAYERS + 1)), ("b", ctypes.c_void_p * (MADE_MAX_LAYERS + 1)),
+                ("steps", ctypes.c_void_p)]
+
+
+MADE_STEP_MAX_NEW = 479
 
 PRECISIONS = {"fp32": 0, "bf16x3": 1, "bf16x6": 2, "f16x3": 3}
 PROF_FORWARD, PROF_BACKWARD, PROF_FINISH = 0, 1, 2

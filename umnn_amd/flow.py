@@ -113,22 +113,27 @@ def _invert_recorded(cls, blocks, z, context, method, tol, max_iter, max_sweeps,
     return z, {"sweeps": K, "status": status[0], "last_move": moves[0]}
 
 
-def _invert_dispatch(cls, flow, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info):
+def _invert_dispatch(cls, flow, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info, conditioner="full"):
     """``cls.invert`` of UMNNMAF and UMNNMAFFlow: checks the options and runs ``cls._invert`` / ``_invert_newton`` / ``_invert_jacobi``.
     While torch.compile / torch.export trace, "newton" and fixed-sweep "jacobi" on the HIP path are recorded (``_invert_recorded``);
     every other call there is an eager call the graph breaks at, and torch.jit.trace raises."""
     if method not in ("bracket", "newton", "jacobi"):
         raise ValueError(f"umnn_amd: unknown inversion method {method!r}; expected 'bracket', 'newton' or 'jacobi'")
+    if conditioner not in ("full", "progressive"):
+        raise ValueError(f"umnn_amd: unknown conditioner {conditioner!r}; expected 'full' or 'progressive'")
+    if method == "jacobi" and conditioner != "full":
+        raise ValueError("umnn_amd: conditioner='progressive' belongs to the dimension-by-dimension walks (method 'newton' or 'bracket'); "
+                         "a Jacobi sweep needs the whole conditioner")
     if torch.jit.is_tracing():
         raise RuntimeError(f"umnn_amd: {cls.__name__}.invert cannot be traced by torch.jit.trace (data-dependent bracket search); "
                            "call it eagerly")
     if return_info and method != "jacobi":
         raise ValueError("umnn_amd: return_info is an option of invert(method='jacobi')")
-    if torch.compiler.is_compiling():
+    if torch.compiler.is_compiling() and conditioner == "full":      # (the progressive walk is an eager call, like "bracket")
         blocks = _recorded_blocks(cls, flow, z, method, sweep_tol, max_sweeps)
         if blocks is not None:
             return _invert_recorded(cls, blocks, z, context, method, tol, max_iter, max_sweeps, return_info)
-    fn, args = {"bracket": (cls._invert, (z, iter, context)), "newton": (cls._invert_newton, (z, context, tol, max_iter)),
+    fn, args = {"bracket": (cls._invert, (z, iter, context, conditioner)), "newton": (cls._invert_newton, (z, context, tol, max_iter, conditioner)),
                 "jacobi": (cls._invert_jacobi, (z, context, tol, max_iter, sweep_tol, max_sweeps, return_info))}[method]
     if torch.compiler.is_compiling():
         # (applied here, not as a decorator: torch.compiler.disable imports torch._dynamo, ~1 s at every package import)
@@ -279,7 +284,7 @@ class UMNNMAF(nn.Module):
                                    torch.zeros_like(cand), cand, h_j, self.nb_steps)
 
     def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None,
-               return_info=False):
+               return_info=False, conditioner="full"):
         """Dimension-by-dimension bracket search: 10 candidates per round on [left,right] (starting at +-50), keep
         the sub-interval next to the candidate whose image is closest to the target (UMNNMAF.py:182-232).  Under torch.compile /
         torch.export the search is an eager call (a graph break); under torch.jit.trace ``invert`` raises.  On the HIP path
@@ -292,20 +297,45 @@ class UMNNMAF(nn.Module):
         ``method="jacobi"`` (an extension; ``iter`` is ignored): the Jacobi iteration of ``_invert_jacobi`` -- every sweep is one full
         conditioner pass and ONE solve of all d dimensions under that embedding (``umnn_cc_solve_block``), warm-started from the previous
         sweep; stops when no entry moved by more than ``sweep_tol * max(1, |x|)`` or after ``max_sweeps`` sweeps (default d, where the
-        result is the sequential one by construction).  ``return_info=True`` (jacobi only) -> (x, info)."""
-        return _invert_dispatch(UMNNMAF, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info)
+        result is the sequential one by construction).  ``return_info=True`` (jacobi only) -> (x, info).
+        ``conditioner="progressive"`` (an extension, "newton" and "bracket"; default "full"): the walk keeps every hidden unit of the
+        conditioner once it is final (``MADE.progressive_plan``) and per dimension computes only the units that became ready and the E
+        outputs of that dimension -- on the HIP path ONE ``umnn_made_step`` launch, so a dimension is two launches; host tensors and
+        nets that kernel refuses run the same walk in torch ops.  Conditioners it does not apply to (random input order, several masks,
+        other weight dtypes, a bf16 embedding) run "full", announced once.  An eager call under torch.compile / torch.export."""
+        return _invert_dispatch(UMNNMAF, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info, conditioner)
 
-    def _dim_embedding(self, x_inv, context, rows_ok):
+    def _dim_embedding(self, x_inv, context, rows_ok, conditioner="full"):
         """The conditioner pass of the dimension-by-dimension sampling loops -> ``embed(j, widen)``: the embedding h [B, E*d] that
         dimension j is solved under, from ``x_inv``'s current contents.  Dimension j reads E of the E*d embedding entries.  Wide
         unconditional conditioners compute only those columns of their last layer (MADE.raw_rows: for d = 784 that layer is 23 520 rows
         of which 30 are read) into a standing buffer, where ``rows_ok`` (the in-kernel path) and the conditioner allow it; otherwise a
         full pass, with ``widen`` as contiguous fp32 -- exact for a bf16 embedding (set_embedding_dtype, autocast), which the fp32-only
-        entry points would misread."""
+        entry points would misread.
+        ``conditioner="progressive"``: ``embed(j, widen)`` is one step of ``made.ProgressiveWalk`` into its standing embedding buffer --
+        on the HIP path (``rows_ok``, fp32 x_inv on the weights' device) one ``umnn_made_step`` launch, else the same walk in torch ops."""
         made = self.net.made
         B, d = x_inv.shape
         dev = x_inv.device
         E = made.nout // made.nin
+        if conditioner == "progressive":
+            plan = made.progressive_plan(dev) if self.net.embedding_dtype in (None, torch.float32) and not torch.is_autocast_enabled() else None
+            if plan is None:
+                _I._warn_once("progressive-ineligible",
+                              "umnn_amd: conditioner='progressive' needs a MADE with the natural input order, one mask, fp32 weights on "
+                              "the tensors' device and an fp32 embedding; this one runs conditioner='full'.")
+            else:
+                use_kernel = bool(rows_ok and x_inv.is_cuda and x_inv.dtype == torch.float32 and x_inv.is_contiguous())
+                if rows_ok and x_inv.is_cuda and plan.desc is None:
+                    _I._warn_once("progressive-torch", "umnn_amd: umnn_made_step does not cover this conditioner (weight dtype, more than 8 "
+                                  "hidden layers or more new units in one step than its LDS hand-off holds): the progressive walk runs in "
+                                  "torch ops.")
+                walk = plan.walk(x_inv, context, use_kernel)
+
+                def embed_progressive(j, widen):
+                    h = walk.step(j)
+                    return h.float().contiguous() if widen and h.dtype != torch.float32 else h
+                return embed_progressive
         restrict = (rows_ok and context is None and not isinstance(made, ConditionnalMADE)
                     and self.net.embedding_dtype in (None, torch.float32) and os.environ.get("UMNN_INVERT_ROWS", "1") != "0")
         rows_all = (torch.arange(E, device=dev) * d).view(1, E) + torch.arange(d, device=dev).view(d, 1) if restrict else None
@@ -324,7 +354,7 @@ class UMNNMAF(nn.Module):
             return h.float().contiguous() if widen else h
         return embed
 
-    def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
+    def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64, conditioner="full"):
         """``invert(method="newton")``.  HIP path: d x (conditioner + ONE launch), the whole solve of a dimension inside the kernel,
         writing x_inv[:, j] in place; nets the solve kernels do not cover, host tensors and other dtypes run the same iteration
         from the host (``integral.newton_solve``), one quadrature launch (or ATen quadrature) per iteration."""
@@ -337,7 +367,7 @@ class UMNNMAF(nn.Module):
             z = z.contiguous()
             x_inv = torch.zeros(B, d, device=dev, dtype=z.dtype)
             scaling = self.scaling.detach().float().contiguous()
-            embed = self._dim_embedding(x_inv, context, in_kernel)
+            embed = self._dim_embedding(x_inv, context, in_kernel, conditioner)
             for j in range(self.input_size):
                 h = embed(j, in_kernel)             # (umnn_cc_solve reads an fp32 embedding)
                 if in_kernel:
@@ -468,7 +498,7 @@ class UMNNMAF(nn.Module):
         return _inv.inverse([self], False, "UMNNMAF.inverse", z, context, method, tol, max_iter, sweep_tol, max_sweeps, adj_tol,
                             max_adj_sweeps, return_info)
 
-    def _invert(self, z, iter=10, context=None):
+    def _invert(self, z, iter=10, context=None, conditioner="full"):
         K = 10
         B, d = z.shape
         dev = z.device
@@ -481,7 +511,7 @@ class UMNNMAF(nn.Module):
                 x_inv = torch.zeros(B, d, device=dev)
                 scaling = self.scaling.detach().float().contiguous()
                 done = True
-                embed = self._dim_embedding(x_inv, context, True)
+                embed = self._dim_embedding(x_inv, context, True, conditioner)
                 for j in range(self.input_size):
                     h = embed(j, True)              # (umnn_flow_invert_dim reads an fp32 embedding: it has no umnn_io descriptor)
                     if not _I.hip_invert_dim(spec, h, z, scaling, self.nb_steps, j, iter, x_inv):
@@ -494,8 +524,9 @@ class UMNNMAF(nn.Module):
         scale = torch.exp(self.scaling)
         rows = torch.arange(B, device=dev)
         with torch.no_grad():
+            embed = self._dim_embedding(x_inv, context, False, conditioner) if conditioner != "full" else None
             for j in range(self.input_size):
-                h = self.net.make_embeding(x_inv, context)
+                h = self.net.make_embeding(x_inv, context) if embed is None else embed(j, False)
                 h3 = h.view(B, -1, d)
                 h_j = h3[:, :, j]                                   # [B,E]; row 0 doubles as the offset
                 offset = h_j[:, 0]
@@ -576,19 +607,19 @@ class UMNNMAFFlow(nn.Module):
         return self._stack(x, context, False)[0]
 
     def invert(self, z, iter=10, context=None, method="bracket", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None,
-               return_info=False):
+               return_info=False, conditioner="full"):
         """Sampling direction, block by block.  ``method="bracket"`` (default): the reference's search, ``iter`` rounds.
         ``method="newton"``: the in-kernel Newton solve (``UMNNMAF.invert``), exactly nb_flow x d solve launches; ``iter`` is ignored.
         ``method="jacobi"``: the Jacobi iteration of ``UMNNMAF.invert`` in every block, one solve launch per sweep;
         ``return_info=True`` -> (x, info) with info's entries as lists over the blocks in flow order.
         torch.compile / torch.export record "newton" and fixed-sweep "jacobi" (``sweep_tol=0``, ``max_sweeps=K``) on the HIP path, see
-        ``UMNNMAF.invert``; everything else stays an eager call there."""
-        return _invert_dispatch(UMNNMAFFlow, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info)
+        ``UMNNMAF.invert``; everything else stays an eager call there.  ``conditioner``: see ``UMNNMAF.invert``."""
+        return _invert_dispatch(UMNNMAFFlow, self, z, iter, context, method, tol, max_iter, sweep_tol, max_sweeps, return_info, conditioner)
 
-    def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64):
+    def _invert_newton(self, z, context=None, tol=1e-6, max_iter=64, conditioner="full"):
         z = torch.flip(z, [1])
         for i in range(len(self.nets) - 1, -1, -1):
-            z = self.nets[i].invert(torch.flip(z, [1]), context=context, method="newton", tol=tol, max_iter=max_iter)
+            z = self.nets[i].invert(torch.flip(z, [1]), context=context, method="newton", tol=tol, max_iter=max_iter, conditioner=conditioner)
         return z
 
     def _invert_jacobi(self, z, context=None, tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None, want_info=False, moves=None):
@@ -630,10 +661,10 @@ class UMNNMAFFlow(nn.Module):
     def log_prob(self, x, context=None):
         return self.compute_ll(x, context)[0]
 
-    def _invert(self, z, iter=10, context=None):
+    def _invert(self, z, iter=10, context=None, conditioner="full"):
         z = torch.flip(z, [1])
         for i in range(len(self.nets) - 1, -1, -1):
-            z = self.nets[i].invert(torch.flip(z, [1]), iter, context=context)
+            z = self.nets[i].invert(torch.flip(z, [1]), iter, context=context, conditioner=conditioner)
         return z
 
     def compute_log_jac(self, x, context=None):

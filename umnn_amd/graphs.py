@@ -15,7 +15,7 @@ def _capture_mode():
     return "thread_local" if dist.is_available() and dist.is_initialized() else "global"
 
 
-def _prime_for_capture(model, x):
+def _prime_for_capture(model, x, progressive=False):
     """What must exist BEFORE a capture whatever ``warmup`` is: the library probe of the conditioner's GEMM route (run for the first
     time inside a capture, hipBLASLt would initialise under capture and abort), the quadrature tables of every block (their host
     -> device upload is not capturable) and ConditionnalMADE's kept-row indices (a pageable host -> device copy).  Warm-up runs
@@ -29,6 +29,8 @@ def _prime_for_capture(model, x):
             quadrature.device_tables(n, x.device)
         if isinstance(mod, made.ConditionnalMADE):
             mod._kept_rows(x.device)
+        if progressive and isinstance(mod, made.MADE):
+            mod.progressive_plan(x.device)      # (the plan's index tensors are host -> device copies; its weights enter the cache here)
 
 
 class GraphedLL:
@@ -106,7 +108,8 @@ class GraphedSampler:
     removes the host's share of it (measured: profiles/graph_sampling/; where the solve launches themselves fill the time the
     graph buys little).
 
-    ``method="newton"`` (``tol``, ``max_iter``) or ``method="jacobi"`` with ``sweep_tol=0`` and an explicit ``max_sweeps=K`` (else
+    ``method="newton"`` (``tol``, ``max_iter``, ``conditioner`` = "full" | "progressive": the plan of the progressive conditioner is built
+    before the capture starts and its standing buffers belong to the graph's pool) or ``method="jacobi"`` with ``sweep_tol=0`` and an explicit ``max_sweeps=K`` (else
     ValueError: the stop test of the sweeps is a device-to-host read, which a graph cannot hold); ``sampler.last_move`` is then the
     0-dim device tensor max |x_K - x_{K-1}| / max(1, |x_K|) over the blocks, for the caller to test afterwards.  ``"bracket"`` is
     refused.  Nets the in-kernel solve does not cover are refused as well (their Newton loop is driven from the host).
@@ -123,6 +126,8 @@ class GraphedSampler:
         if method not in ("newton", "jacobi"):
             raise ValueError(f"umnn_amd: GraphedSampler records method 'newton' or 'jacobi', not {method!r}")
         opts = dict(tol=1e-6, max_iter=64)
+        if method == "newton":
+            opts.update(conditioner="full")
         if method == "jacobi":
             opts.update(sweep_tol=1e-6, max_sweeps=None)
         unknown = set(solve_opts) - set(opts)
@@ -149,7 +154,8 @@ class GraphedSampler:
     def _run(self):
         o = self.opts
         if self.method == "newton":
-            return self.model.invert(self.z, context=self.context, method="newton", tol=o["tol"], max_iter=o["max_iter"]), None
+            return self.model.invert(self.z, context=self.context, method="newton", tol=o["tol"], max_iter=o["max_iter"],
+                                     conditioner=o["conditioner"]), None
         moves = []
         x, _ = self.model._invert_jacobi(self.z, self.context, o["tol"], o["max_iter"], 0., int(o["max_sweeps"]), False, moves)
         return x, torch.stack(moves).max()
@@ -168,7 +174,7 @@ class GraphedSampler:
             if integral._state.host_solve or integral.path_taken() != "hip":
                 raise ValueError("umnn_amd: GraphedSampler needs the in-kernel solve (HIP path, an integrand the solve kernels cover): "
                                  "the host-driven Newton loop reads the device every iteration and cannot be captured")
-            _prime_for_capture(self.model, self.z)
+            _prime_for_capture(self.model, self.z, progressive=self.opts.get("conditioner", "full") == "progressive")
             self.graph = torch.cuda.CUDAGraph()
             with made.capture_may_cache(), torch.cuda.graph(self.graph, capture_error_mode=_capture_mode()):
                 self.out, self.last_move = self._run()

@@ -50,6 +50,7 @@ class MaskedLinear(nn.Linear):
         self._cache = None      # (weight version, weight data_ptr, masked weight)
         self._packed = None     # (key, bf16 [Wh|Wh|Wl|bh|bl] operand)
         self._frags = None      # (key, (bf16 MFMA fragments, fp32 bias)) for the fused conditioner kernel
+        self._epoch = 0         # bumped by set_mask / invalidate_caches: part of the key of MADE.progressive_plan
 
     def set_mask(self, mask):
         # mask arrives [in, out] (numpy, bool); stored [out, in] like the weight
@@ -57,6 +58,7 @@ class MaskedLinear(nn.Linear):
         self._cache = None
         self._packed = None
         self._frags = None
+        self._epoch += 1
 
     def invalidate_caches(self):
         """Drop the cached masked / packed weights.  The caches are keyed on tensor versions; writes through ``.data``
@@ -65,6 +67,7 @@ class MaskedLinear(nn.Linear):
         self._cache = None
         self._packed = None
         self._frags = None
+        self._epoch += 1
 
     @staticmethod
     def _capturing(t):
@@ -454,6 +457,93 @@ def _to_weight_dtype(x, layer):
     return x
 
 
+class ProgressivePlan:
+    """What ``MADE.progressive_plan`` returns: every hidden layer sorted by degree (stable), the masked weights permuted into that
+    order, the output layer regrouped by flow dimension and the per-step table (see ``MADE.progressive_plan``).
+      c, d, E, widths [H_l], ldk [K stride of W[l], a multiple of 4], orders [int64 device index per hidden layer],
+      steps  int32 numpy [d][L + 1][3]: (first new unit, end of new units, input prefix length) per step and layer,
+      W[l] [H_l, ldk[l]] / b[l] [H_l] for l < L; W[L] [d, E, ldk[L]] / b[L] [d, E]  (the weights' dtype, K axis zero-padded),
+      max_new: the widest new-unit slice of one step, desc: the ``umnn_made_plan`` of ``umnn_made_step`` (None where the kernel does
+      not apply: host tensors, non-fp32 weights, more layers or a wider slice than it holds)."""
+
+    def __init__(self, static, W, b):
+        self.__dict__.update(static)
+        self.W, self.b = W, b
+        self.desc = None
+        dev = W[0].device
+        if (dev.type == "cuda" and W[0].dtype == torch.float32 and len(self.widths) <= 8 and self.max_new <= 479):
+            from . import _lib
+            desc = _lib.MadePlan()
+            desc.n_hidden, desc.d, desc.c, desc.E = len(self.widths), self.d, self.c, self.E
+            for l, w in enumerate(self.widths):
+                desc.width[l] = w
+            for l in range(len(self.widths) + 1):
+                desc.ldk[l] = self.ldk[l]
+                desc.W[l], desc.b[l] = _ptr(W[l]), _ptr(b[l])
+            desc.steps = self.steps.ctypes.data
+            self.desc = desc
+
+    def walk(self, x, context, use_kernel):
+        return ProgressiveWalk(self, x, context, use_kernel)
+
+    # (the descriptor holds raw pointers: a copied or pickled module rebuilds its plan on first use)
+    def __deepcopy__(self, memo):
+        return None
+
+    def __reduce__(self):
+        return (type(None), ())
+
+
+class ProgressiveWalk:
+    """The standing state of one block's progressive walk over ``x`` [B, d] (filled in place by the caller, column j final before
+    ``step(j + 1)``): the activation buffers of the hidden layers in degree order and the embedding buffer h [B, E*d].
+    ``step(j)`` computes the units that became ready and the E outputs of dimension j -> h (columns e*d + j written).
+    ``use_kernel``: one ``umnn_made_step`` launch per step; otherwise the same walk as ``F.linear`` on the slices."""
+
+    def __init__(self, plan, x, context, use_kernel):
+        self.plan, self.x = plan, x
+        B, dev = x.shape[0], x.device
+        self.kernel = bool(use_kernel and plan.desc is not None and B > 0)
+        dt = torch.float32 if self.kernel else plan.W[0].dtype
+        if context is not None and (context.dtype != dt or not context.is_contiguous()):
+            context = context.to(dt).contiguous()
+        self.context = context
+        self.row_tiles = 0          # umnn_made_step's row_tiles (0: automatic); the result does not depend on it
+        L = len(plan.widths)
+        self.acts = [torch.zeros(B, plan.ldk[l + 1], device=dev, dtype=dt) for l in range(L)]
+        self.h = torch.zeros(B, plan.E * plan.d, device=dev, dtype=dt)
+        if self.kernel:
+            self._act_ptrs = (ctypes.c_void_p * 8)(*[_ptr(a) for a in self.acts])
+
+    def step(self, j):
+        p = self.plan
+        B = self.x.shape[0]
+        if self.kernel:
+            from . import _lib
+            with torch.cuda.device(self.x.device):
+                _lib.check(_lib.lib().umnn_made_step(ctypes.byref(p.desc), int(j), None if self.context is None else _ptr(self.context),
+                                                     _ptr(self.x), self._act_ptrs, _ptr(self.h), B, int(self.row_tiles),
+                                                     _stream(self.x.device)),
+                           "umnn_made_step")
+            return self.h
+        L = len(p.widths)
+        dt = p.W[0].dtype
+        for l in range(L):
+            lo, hi, pre = (int(v) for v in p.steps[j, l])
+            if hi <= lo:
+                continue
+            if l == 0:
+                a = self.x[:, :pre - p.c].to(dt)
+                if p.c:
+                    a = torch.cat((self.context, a), 1)
+            else:
+                a = self.acts[l - 1][:, :pre]
+            self.acts[l][:, lo:hi] = torch.relu(F.linear(a, p.W[l][lo:hi, :pre], p.b[l][lo:hi]))
+        pre = int(p.steps[j, L, 2])
+        self.h.view(B, p.E, p.d)[:, :, j] = F.linear(self.acts[L - 1][:, :pre], p.W[L][j][:, :pre], p.b[L][j])
+        return self.h
+
+
 class MADE(nn.Module):
     def __init__(self, nin, hidden_sizes, nout, num_masks=1, natural_ordering=False, random=False, device="cpu"):
         super().__init__()
@@ -470,6 +560,8 @@ class MADE(nn.Module):
         self.net = nn.Sequential(*layers).to(device)
         self.natural_ordering, self.num_masks, self.seed = natural_ordering, num_masks, 0
         self.m = {}
+        self._prog_static = None    # (key, device-resident index tensors + host step table) of progressive_plan
+        self._prog = None           # (key, ProgressivePlan)
         self.update_masks()
 
     def _degrees(self):
@@ -500,6 +592,85 @@ class MADE(nn.Module):
         for layer, mask in zip((l for l in self.net if isinstance(l, MaskedLinear)), masks):
             layer.set_mask(mask)
         self.i_map = np.argsort(self.m[-1])
+
+    # ---- progressive conditioner of the sequential sampling walk -----------------------------------------------------------------
+    def _masked_layers(self):
+        return [l for l in self.net if isinstance(l, MaskedLinear)]
+
+    def _progressive_static(self, device):
+        """The part of the plan that depends on the degrees only: orders, output rows, the step table.  None when ineligible."""
+        layers = self._masked_layers()
+        key = (str(device), tuple(l._epoch for l in layers))
+        if self._prog_static is not None and self._prog_static[0] == key:
+            return self._prog_static[1]
+        nin, L = self.nin, len(self.hidden_sizes)
+        c = getattr(self, "cond_in", 0)
+        d, E = nin - c, self.nout // nin
+        static = None
+        if self.num_masks == 1 and L >= 1 and d >= 1 and np.array_equal(np.asarray(self.m[-1]), np.arange(nin)):
+            if device.type == "cuda" and torch.cuda.is_current_stream_capturing():
+                # (pageable host -> device copies cannot be recorded: graphs.GraphedSampler builds the plan before it captures)
+                raise RuntimeError("MADE.progressive_plan: the plan tables must exist before a stream capture starts "
+                                   "(umnn_amd.GraphedSampler primes them; call flow.invert(..., conditioner='progressive') once eagerly)")
+            orders = [np.argsort(np.asarray(self.m[l]), kind="stable") for l in range(L)]
+            sdeg = [np.asarray(self.m[l])[orders[l]] for l in range(L)]
+            steps = np.zeros((d, L + 1, 3), dtype=np.int32)
+            prev_hi = [0] * L
+            for j in range(d):
+                T = c + j - 1                       # units of degree <= T are final once x_0..x_{j-1} are
+                for l in range(L):
+                    hi = int(np.searchsorted(sdeg[l], T, side="right"))
+                    steps[j, l] = (prev_hi[l], hi, c + j if l == 0 else steps[j, l - 1, 1])
+                    prev_hi[l] = hi
+                steps[j, L] = (0, E, steps[j, L - 1, 1])
+            widths = [int(h) for h in self.hidden_sizes]
+            ldk = [-(-k // 4) * 4 for k in [nin] + widths]
+            out_rows = (np.arange(d)[:, None] + c + nin * np.arange(E)[None, :]).reshape(-1)       # [d][E] -> row e*nin + c + j
+            static = dict(c=c, d=d, E=E, widths=widths, ldk=ldk, steps=steps,
+                          max_new=int((steps[:, :L, 1] - steps[:, :L, 0]).max()),
+                          orders=[torch.from_numpy(o).to(device) for o in orders], out_rows=torch.from_numpy(out_rows).to(device))
+        self._prog_static = (key, static)
+        return static
+
+    def progressive_plan(self, device):
+        """The plan of the progressive conditioner (``ProgressivePlan``), or None when this conditioner is not eligible: it needs the
+        natural input order (m[-1] == arange(nin): the order ``UMNNMAF.invert`` walks), ``num_masks == 1`` and fp32 (or fp64) weights.
+        By MADE's construction (``update_masks``) a hidden unit of degree m reads inputs of degree <= m and an output of dimension i
+        hidden units of degree < i, so with c = cond_in (0 for MADE) step j of the walk computes every not-yet-computed unit of degree
+        <= c + j - 1 (step 0 of a conditional block: all units of degree < c at once); a hidden layer's prefix is the count of previous
+        -layer units of degree <= c + j - 1, the output's the count of last-hidden units of degree < c + j, layer 0's the c + j input
+        columns; units of degree >= nin - 1 are never computed.  The permuted weights stay MASKED: their exact zeros make a prefix longer
+        than one unit's own mask still exact.  Cached like the packed weights: keyed on weight / mask / bias versions and pointers,
+        dropped by ``invalidate_caches`` and ``set_mask``; nothing produced during a stream capture is stored."""
+        layers = self._masked_layers()
+        w0 = layers[0].weight
+        if w0.dtype not in (torch.float32, torch.float64) or w0.device != device or any(l.bias is None for l in layers):
+            return None
+        static = self._progressive_static(device)
+        if static is None:
+            return None
+        key = (str(device), w0.dtype) + tuple((l._epoch, l.weight._version, l.weight.data_ptr(), l.mask._version, l.mask.data_ptr(),
+                                               l.bias._version, l.bias.data_ptr()) for l in layers)
+        capturing = MaskedLinear._capturing(w0)         # see MaskedLinear.masked_weight: recompute inside the graph, never cache
+        if not capturing and self._prog is not None and self._prog[0] == key and self._prog[1] is not None:
+            return self._prog[1]
+        L = len(self.hidden_sizes)
+        with torch.no_grad():
+            W, b = [], []
+            for l in range(L):
+                w = (layers[l].mask * layers[l].weight).index_select(0, static["orders"][l])
+                if l > 0:
+                    w = w.index_select(1, static["orders"][l - 1])
+                W.append(F.pad(w, (0, static["ldk"][l] - w.shape[1])).contiguous())
+                b.append(layers[l].bias.index_select(0, static["orders"][l]).contiguous())
+            w = (layers[L].mask * layers[L].weight).index_select(0, static["out_rows"]).index_select(1, static["orders"][L - 1])
+            W.append(F.pad(w, (0, static["ldk"][L] - w.shape[1])).view(static["d"], static["E"], static["ldk"][L]).contiguous())
+            b.append(layers[L].bias.index_select(0, static["out_rows"]).view(static["d"], static["E"]).contiguous())
+        plan = ProgressivePlan(static, W, b)
+        if capturing or not MaskedLinear._may_store(w0):
+            return plan
+        self._prog = (key, plan)
+        return plan
 
     def raw(self, x, out_dtype=None):
         """The masked MLP itself (what the flow's EmbeddingNetwork needs, whatever nout is)."""
