@@ -290,7 +290,7 @@ int umnn_cc_forward_timed(const umnn_mlp* net, const float* x0, const float* x, 
  * term, the output dot product, ELU and the quadrature sum are fp32 in every mode).
  *   F16X3   (default since round 5)  operands split in two fp16 pieces (11 bits each), 3 cross terms on v_mfma_f32_16x16x32_f16,
  *           fp32 accumulation: fp32-level accuracy at the cost of BF16X3.  fp16's exponent range is handled by an overflow
- *           protocol (umnn_amd/csrc/cc_forward_bf16.hip): a tile group (16 or 32 integrals) whose quadrature sum is not finite --
+ *           protocol (umnn_amd/csrc/cc_fwd_launch.h): a tile group (16 or 32 integrals) whose quadrature sum is not finite --
  *           where an overflowed piece always ends -- writes only a NaN marker into its slots of F (z for the flow entry points,
  *           x_inv[:, j] for umnn_flow_invert_dim), and the BF16X3 build of the same kernel, queued behind every launch on the
  *           same stream, recomputes exactly the marked groups (one scalar load per workgroup when nothing overflowed).  Those
@@ -351,6 +351,29 @@ int umnn_cc_backward_kind(const umnn_mlp* net, int E);
 #define UMNN_PLAN_X_BF16 8           /* umnn_io::x_dtype = UMNN_DTYPE_BF16 */
 #define UMNN_PLAN_H_BF16 16          /* umnn_io::h_dtype = UMNN_DTYPE_BF16 */
 const char* umnn_cc_backward_plan_name(const umnn_mlp* net, long long B, int d, int E, int nb_steps, int flags);
+/* The launch plan of a forward, bracket-search or Newton-solve call of this net and shape under the current options: what
+ * umnn_last_kernel_name() would hold afterwards, and the quantities the name does not show (P and ns decide the summation order,
+ * hence the bits).  kind: UMNN_PLAN_FORWARD (umnn_cc_forward*, umnn_flow_*_forward*: B x d integrals), UMNN_PLAN_SEARCH
+ * (umnn_flow_invert_dim: B samples), UMNN_PLAN_SOLVE (umnn_cc_solve: B rows), UMNN_PLAN_SOLVE_BLOCK (umnn_cc_solve_block: B x d rows).
+ * flags (forward only): UMNN_PLAN_Z2_SAVED (umnn_flow_stack_block_forward_save*), UMNN_PLAN_MARKER_ALIASED (F, or z for the flow entry
+ * points, aliases x, x0 or h); the storage flags UMNN_PLAN_X_BF16 / UMNN_PLAN_H_BF16 are accepted and do not route.  Returns 0 and
+ * fills *out (all zero, name "", for B = 0), or the code -- with the text in umnn_last_error() -- the entry point itself would return
+ * for this net and shape, leaving name "".  Read-only: the plan (csrc/cc_fwd_plan.h) is evaluated and nothing is launched, so it also
+ * answers without a device (as for 256 CUs). */
+#define UMNN_PLAN_FORWARD 0
+#define UMNN_PLAN_SEARCH 1
+#define UMNN_PLAN_SOLVE 2
+#define UMNN_PLAN_SOLVE_BLOCK 3
+#define UMNN_PLAN_MARKER_ALIASED 32  /* the marker output of a forward call aliases one of its inputs */
+typedef struct umnn_launch_plan_info {
+    const char* name;        /* kernel name (static storage) */
+    int pieces;              /* 16-bit pieces per operand: 2 or 3; 0 = fp32 MFMA */
+    int P, ns;               /* point tiles per wave; node-range split */
+    int waves_per_block;
+    long long blocks, lds_bytes;
+    int fallback;            /* 1: the bf16 build of the same variant is queued behind the launch (fp16 pieces) */
+} umnn_launch_plan_info;
+int umnn_cc_launch_plan(const umnn_mlp* net, int kind, long long B, int d, int E, int nb_steps, int flags, umnn_launch_plan_info* out);
 int umnn_set_backward_precision(int mode);
 int umnn_get_backward_precision(void);
 

@@ -1,7 +1,7 @@
 """Round 5: the fp16-piece forward as the library DEFAULT, with its queued bf16x3 overflow fallback.
 
 Reference arithmetic being matched: models/UMNN/ParallelNeuralIntegral.py:49-65 (forward quadrature), UMNNMAFFlow.py:109-119
-(compute_ll).  Protocol under test: umnn_amd/csrc/cc_forward_bf16.hip ("overflow protocol"), cc_fwd_shared.h (epilogue).
+(compute_ll).  Protocol under test: umnn_amd/csrc/cc_fwd_launch.h ("overflow protocol"), cc_fwd_shared.h (epilogue).
 """
 import os
 

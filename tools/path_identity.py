@@ -9,9 +9,11 @@ flow.py / integral.py / ops.py -- eagerly and under the compile backends tests/t
 case; Inductor, where Triton is installed, for the two kinds of graph that file compiles with it), and records per case every
 output and gradient tensor, ``path_taken()``, ``backward_path_taken()``, ``umnn_last_kernel_name()``, the last kernel of the
 backward's main pass (``umnn_last_kernel_name_of(PROF_BACKWARD)``) and the ``umnn_launch_count()`` delta.  The list ends with the
-GPU cases of tests/_bwd_plan_cases.py: one ``integral.hip_backward`` call per kernel family and option of the backward's launch plan.  A case that raises is recorded by its exception type.  ``compare`` wants ``torch.equal`` on every
+GPU cases of tests/_bwd_plan_cases.py (one ``integral.hip_backward`` call per kernel family and option of the backward's launch plan)
+and of tests/_fwd_plan_cases.py (forward, flow block, ll block, bracket search and Newton solves per family and rule of the forward's;
+``invert`` bracket / newton / jacobi are further up).  A case that raises is recorded by its exception type.  ``compare`` wants ``torch.equal`` on every
 tensor and equality of every string and count; it prints (and writes to REPORT) the number of tensors, the number of mismatches and
-the kernel names seen, and exits non-zero on any mismatch.  Only the public API is used, so the file runs in older checkouts too (with tests/_bwd_plan_cases.py copied along)."""
+the kernel names seen, and exits non-zero on any mismatch.  Only the public API is used, so the file runs in older checkouts too (with tests/_bwd_plan_cases.py and tests/_fwd_plan_cases.py copied along)."""
 import os
 import sys
 import warnings
@@ -193,6 +195,31 @@ def _backward_plan_cases():
     return [(f"backward plan: {c['id']}", EAGER, _backward_plan_case(c)) for c in _bwd_plan_cases.GPU_CASES]
 
 
+def _forward_plan_case(c):
+    def make(dev):
+        from tests import _fwd_plan_cases
+        return None, (lambda: _fwd_plan_cases.run(c, dev)), (), None
+    return make
+
+
+def _forward_plan_cases():
+    from tests import _fwd_plan_cases
+    return [(f"forward plan: {c['id']}", EAGER, _forward_plan_case(c)) for c in _fwd_plan_cases.GPU_CASES]
+
+
+def _plan_block_case(ll):
+    """A flow block through the launch plan's forward cases: the block forward (z, log_jac) or the one-pass log-likelihood"""
+    def make(dev):
+        flow = _flow(dev, nb_flow=1)
+        x = _x(dev, 3)
+
+        def fn(x):
+            with torch.no_grad():
+                return flow.compute_ll(x) if ll else flow.nets[0].compute_log_jac(x)
+        return flow, fn, (x,), None
+    return make
+
+
 EAGER, COMPILED, INDUCTOR = ("eager",), ("eager", "aot_eager"), ("eager", "aot_eager", "inductor")
 WIDE_FIRST = dict(d=8, E=10, hidden=(100, 50, 50, 50, 50))           # the z_2 hand-off from the training forward to the backward
 DEEP_WIDE = dict(d=2, E=4, hidden=(100, 72, 80, 96, 70), n=10)       # no shape-exact HIP backward: the ATen backward
@@ -217,7 +244,9 @@ CASES = [
     ("MonotonicNN.inverse", COMPILED, _monotonic(True)),
     ("InverseNeuralIntegral, gradients to h and the parameters", COMPILED, _inverse_integral),
 ] + [(f"flow.invert {method}{', context' if cond else ' (raw_rows)'}", COMPILED, _invert(method, cond))
-     for method in ("bracket", "newton", "jacobi") for cond in (False, True)] + _backward_plan_cases()
+     for method in ("bracket", "newton", "jacobi") for cond in (False, True)] + _backward_plan_cases() + [
+    ("forward plan: flow block", EAGER, _plan_block_case(False)), ("forward plan: ll block", EAGER, _plan_block_case(True)),
+] + _forward_plan_cases()
 
 
 def _flat(out):

@@ -38,6 +38,16 @@ class IoDesc(ctypes.Structure):
 
 DTYPE_F32, DTYPE_BF16 = 0, 1
 PLAN_INV_F, PLAN_G_FX, PLAN_Z2_SAVED, PLAN_X_BF16, PLAN_H_BF16 = 1, 2, 4, 8, 16      # flags of umnn_cc_backward_plan_name
+PLAN_MARKER_ALIASED = 32                                                             # ... and of umnn_cc_launch_plan, whose kinds are
+PLAN_FORWARD, PLAN_SEARCH, PLAN_SOLVE, PLAN_SOLVE_BLOCK = 0, 1, 2, 3
+
+
+class LaunchPlanInfo(ctypes.Structure):
+    """struct umnn_launch_plan_info"""
+    _fields_ = [("name", ctypes.c_char_p), ("pieces", ctypes.c_int), ("P", ctypes.c_int), ("ns", ctypes.c_int),
+                ("waves_per_block", ctypes.c_int), ("blocks", ctypes.c_longlong), ("lds_bytes", ctypes.c_longlong),
+                ("fallback", ctypes.c_int)]
+
 
 # name -> (restype, argtypes); must list every symbol include/umnn_cc.h declares
 SIGNATURES = {
@@ -83,6 +93,8 @@ SIGNATURES = {
     "umnn_get_forward_precision": (ctypes.c_int, []),
     "umnn_cc_backward_kind": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int]),
     "umnn_cc_backward_plan_name": (ctypes.c_char_p, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]),
+    "umnn_cc_launch_plan": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.c_int, _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                           ctypes.POINTER(LaunchPlanInfo)]),
     "umnn_set_backward_precision": (ctypes.c_int, [ctypes.c_int]),
     "umnn_get_backward_precision": (ctypes.c_int, []),
     "umnn_profile_enable": (ctypes.c_int, [ctypes.c_int]),

@@ -61,7 +61,7 @@ int umnn_num_cus() {
     return v;
 }
 
-// Flag words of the forward overflow protocol (cc_forward_bf16.hip): 256 zeroed 64-bit words per device, allocated on the first
+// Flag words of the forward overflow protocol (cc_fwd_launch.h): 256 zeroed 64-bit words per device, allocated on the first
 // fp16-piece launch of that device (in relaxed capture mode, should that launch be recorded into a hipGraph); every launch takes
 // the next generation number and the word generation % 256.
 int umnn_ovf_slot(unsigned long long** flag, unsigned long long* gen) {

@@ -14,7 +14,7 @@
 #include "cc_bwd_ws16_kernel.h"      // (the pipelines' sizes; the _p3 build of the three-stage family executes a route, it decides nothing)
 #endif
 
-constexpr size_t BWD_LDS_LIMIT = 160 * 1024;      // bytes of LDS one workgroup may take (gfx950: 160 KiB per CU)
+constexpr size_t BWD_LDS_LIMIT = UMNN_LDS_LIMIT;      // (cc_host.h: shared with the forward plan)
 
 struct BwdOptions { int bwd_precision, bwd_ws, bwd_ws16, bwd_swp, bwd_ns, front_bwd2; };
 

@@ -221,26 +221,19 @@ __global__ __launch_bounds__(UMNN_BLOCK) void cc_fwd_kernel(const FwdArgs a) {
 // ------------------------------------------------------------------------------------------
 #include <cstring>
 
-#include "cc_host.h"
+#include "cc_fwd_launch.h"
 
 typedef void (*fwd_kernel_t)(const FwdArgs);
+#define FWD_FP32_KERNEL(T, K, PP, TL, NT) cc_fwd_kernel<T, K, PP, TL, NT>,
+static const fwd_kernel_t kFwdFp32Kernels[] = { UMNN_FWD_FP32_VARIANTS(FWD_FP32_KERNEL) };
+static_assert(sizeof(kFwdFp32Kernels) / sizeof(kFwdFp32Kernels[0]) == kFwdFp32Count, "one kernel per variant");
 
-struct FwdVariant { int tmax, ksc, p, tail, nt; fwd_kernel_t fn; const char* name; };
+// the piece families execute a plan in their own translation units (cc_forward_bf16.hip and its fp16 build, cc_forward_p32.hip)
+int umnn_launch_forward_bf16(const FwdPlan& pl, const FwdArgs& a, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
+int umnn_launch_forward_f16(const FwdPlan& pl, const FwdArgs& a, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
+int umnn_launch_forward_p32(const FwdPlan& pl, const FwdArgs& a, double flops, hipStream_t stream);
 
-#define FWD_VARIANT(T, K, PP, TL, NT) { T, K, PP, TL, NT, cc_fwd_kernel<T, K, PP, TL, NT>, "cc_fwd<T=" #T ",KS=" #K ",P=" #PP ",TAIL=" #TL ">" }
-static const FwdVariant kFwdVariants[] = {
-    FWD_VARIANT(4, 13, 1, 1, 2), FWD_VARIANT(4, 13, 2, 1, 2),   // hidden width 50 (UCI / VAE nets): VALU tail for 48,49
-    FWD_VARIANT(4, 13, 1, 0, 0), FWD_VARIANT(4, 13, 2, 0, 0),   // widths 48..51, all four tiles on MFMA
-    FWD_VARIANT(7, 26, 1, 0, 0), FWD_VARIANT(7, 26, 2, 0, 0),   // hidden width 100 (toy / MonotonicMLP nets)
-    FWD_VARIANT(2, 0, 1, 0, 0),  FWD_VARIANT(2, 0, 2, 0, 0),    // generic, hidden widths <= 31
-    FWD_VARIANT(4, 0, 1, 0, 0),  FWD_VARIANT(4, 0, 2, 0, 0),    // generic, <= 63
-    FWD_VARIANT(8, 0, 1, 0, 0),  FWD_VARIANT(8, 0, 2, 0, 0),    // generic, <= 127
-};
-
-struct FwdOvfPlan;        // cc_forward_bf16.hip: the queued-fallback plan of an fp16-piece launch (null = a plain launch)
-int umnn_launch_forward_bf16(FwdArgs& a, const umnn_mlp* net, int nparts, int P, int ns, int nb_steps, hipStream_t stream, const FwdOvfPlan* ovf);
-int umnn_launch_forward_f16(FwdArgs& a, const umnn_mlp* net, int nparts, int P, int ns, int nb_steps, hipStream_t stream, const FwdOvfPlan* ovf);     // cc_forward_f16.hip
-
+// Validates, fills the operands, asks for the plan (cc_fwd_plan.h) and executes it.
 static int launch_forward(const umnn_mlp* net, const float* x0, const float* x, const float* h,
                           const float* scaling, const float* cc_w, const float* cc_s, int nb_steps,
                           long long B, int d, int E, int inv_f,
@@ -267,87 +260,40 @@ static int launch_forward(const umnn_mlp* net, const float* x0, const float* x, 
     a.inv_z = nullptr; a.inv_x = nullptr; a.inv_j = 0; a.inv_iters = 0;
     if (ll && a.x_bf16) return umnn_fail(UMNN_EINVAL, "flow ll forward: z / log_jac scratch must be fp32");
     a.NI = B * (long long)d; a.d = d; a.E = E; a.n = nb_steps; a.inv_f = inv_f;
-    a.ovf_mode = 0; a.ovf_flag = nullptr; a.ovf_gen = 0;
     a.z2_save = z2_save; a.z2_nl2 = z2_save ? (net->widths[2] + 1 + 3) / 4 : 0;
 
-    // ---- choose the variant: exact (compile-time K-steps) when all hidden layers share a width we
-    // instantiated, otherwise the smallest generic tile count that fits
-    const long long tiles16 = (a.NI + 15) / 16;
-    const int simd_slots = umnn_num_cus() * 4;
-    int P = tiles16 >= 8LL * simd_slots ? 2 : 1;
-    int ns = 1;
-    if (tiles16 < 2LL * simd_slots) ns = tiles16 * 2 <= 2LL * simd_slots ? 4 : 2;
-    if (ns > nb_steps + 1) ns = 1;
-    const UmnnOptions& opt = umnn_options();
-    const int opt_p = opt.fwd_p, opt_ns = opt.fwd_ns, opt_tail = opt.fwd_tail;
-    if (opt_p > 0) P = opt_p;
-    if (opt_ns > 0) ns = opt_ns;
-
-    if (z2_save && (opt.fwd_precision == UMNN_PRECISION_FP32 || opt.fwd_precision == UMNN_PRECISION_BF16X6))
-        return umnn_fail(UMNN_EUNSUPPORTED, "forward (z_2 saved): two-piece arithmetic modes only");
-    // bf16-split kernels (default): hidden GEMMs on the bf16 matrix cores; falls through to fp32 MFMA when the
-    // shape does not fit them (a single hidden layer has no hidden->hidden GEMM at all)
-    const int prec = opt.fwd_precision;
-    if (prec != UMNN_PRECISION_FP32 && a.m.n_linear - 1 >= 2) {
-        a.ns = ns;
-        // f16x3 (default): two fp16 pieces, three cross terms (fp32-level), the bf16x3 build queued behind it for tile groups whose
-        // pieces overflow (cc_forward_bf16.hip).  The deferred groups are marked IN the output (F, or z), so a launch whose marker
-        // output aliases one of its inputs runs bf16x3 outright -- the arithmetic its overflowing groups would get anyway.  Shapes
-        // that family does not cover fall through to the three-piece bf16 kernels (the same accuracy class), then to fp32 MFMA.
-        if (prec == UMNN_PRECISION_F16X3) {
-            const float* marker = F ? F : z;
-            if (marker == x || marker == x0 || marker == h) {
-                const int rc2 = umnn_launch_forward_bf16(a, net, 2, P, ns, nb_steps, stream, nullptr);
-                if (rc2 != UMNN_EUNSUPPORTED) return rc2;
-            } else {
-                const int rc16 = umnn_launch_forward_f16(a, net, 2, P, ns, nb_steps, stream, nullptr);
-                if (rc16 != UMNN_EUNSUPPORTED) return rc16;
-            }
-        }
-        const int rc = umnn_launch_forward_bf16(a, net, prec == UMNN_PRECISION_BF16X3 ? 2 : 3, P, ns, nb_steps, stream, nullptr);
-        if (rc != UMNN_EUNSUPPORTED) return rc;
+    const float* marker = F ? F : z;       // (where an fp16-piece launch marks its deferred groups: cc_fwd_launch.h)
+    const FwdCall call = fwd_call_forward(a.NI, nb_steps, marker == x || marker == x0 || marker == h, z2_save != nullptr);
+    const FwdPlan pl = fwd_plan(a.m, tmax, ksu, call, umnn_fwd_options(), umnn_num_cus());
+    if (pl.error) return umnn_fail(pl.error, pl.error_text);
+    const double flops = umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI;
+    switch (pl.family) {
+    case FWD_FAMILY_FP32: return umnn_fwd_launch(kFwdFp32Kernels[pl.variant], pl, a, a, flops, "cc_fwd launch", stream, nullptr, umnn_fwd_no_fallback);
+    case FWD_FAMILY_P32: return umnn_launch_forward_p32(pl, a, flops, stream);
+    default: return (pl.f16 ? umnn_launch_forward_f16 : umnn_launch_forward_bf16)(pl, a, flops, stream, nullptr);
     }
-    if (z2_save) return umnn_fail(UMNN_EUNSUPPORTED, "forward (z_2 saved): this net / launch is not served by the wide-first kernels");
-    // TAIL is possible when every hidden layer has the same width H with 16(T-1) <= H <= 16(T-1)+3
-    const int H1w = net->widths[1];
-    int want_tail = (ksu && ksu == 4 * (tmax - 1) + 1 && H1w - 16 * (tmax - 1) >= 0 && H1w - 16 * (tmax - 1) <= 3) ? 1 : 0;
-    if (opt_tail >= 0) want_tail = want_tail && opt_tail != 0;
-    const FwdVariant* pick = nullptr;
-    for (int tl = want_tail; tl >= 0 && !pick; --tl)
-        for (const FwdVariant& v : kFwdVariants)
-            if (v.ksc && v.ksc == ksu && v.tmax == tmax && v.p == P && v.tail == tl &&
-                (!tl || v.nt == H1w - 16 * (tmax - 1))) { pick = &v; break; }
-    if (!pick)
-        for (const FwdVariant& v : kFwdVariants)
-            if (!v.ksc && v.tmax >= tmax && v.p == P) { pick = &v; break; }
-    if (!pick) return umnn_fail(UMNN_EUNSUPPORTED, "forward: hidden width above UMNN_MAX_HIDDEN_WIDTH");
-    const fwd_kernel_t kfn = pick->fn;
-    const char* kname = pick->name;
+}
 
-    const int L = a.m.n_linear - 1;
-    if (pick->tail) {       // re-lay the LDS plan: T-1 tiles per image, then the tail rows
-        int off = 0;
-        for (int l = 1; l <= L; ++l) a.m.t_mfma[l] = a.m.t_out[l] - 1;
-        for (int l = 1; l < L; ++l) { a.m.lds_off[l] = off; off += a.m.t_mfma[l + 1] * a.m.ks_in[l] * 64; }
-        a.m.tail_off = off;
-        a.m.n_tail = H1w - 16 * (tmax - 1);
-        off += (L - 1) * 3 * 4 * 16;
-        a.m.lds_off[L] = off;
-    }
-    const size_t lds_floats = (size_t)a.m.lds_off[L] + (ns > 1 ? UMNN_WAVES_PER_BLOCK * 3 * P * 16 : 0);
-    const size_t lds_bytes = lds_floats * sizeof(float);
-    if (lds_bytes > 160 * 1024) return umnn_fail(UMNN_EUNSUPPORTED, "forward: weight images exceed 160 KiB of LDS");
-    if (int rc = umnn_allow_lds((const void*)kfn, lds_bytes)) return rc;
-
-    a.ns = ns;
-    a.ngroups = (unsigned)((a.NI + 16 * P - 1) / (16 * P));
-    const unsigned gpb = UMNN_WAVES_PER_BLOCK / ns;
-    const unsigned nblk = (a.ngroups + gpb - 1) / gpb;
-    umnn_prof_begin(stream);
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(UMNN_BLOCK), lds_bytes, stream, a);
-    umnn_prof_end(stream, umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI);
-    umnn_note_launch(kname);
-    return umnn_check(hipGetLastError(), "cc_fwd launch");
+// The plan of a call, nothing launched (include/umnn_cc.h).  Without a device: as for 256 CUs.
+extern "C" int umnn_cc_launch_plan(const umnn_mlp* net, int kind, long long B, int d, int E, int nb_steps, int flags,
+                                   umnn_launch_plan_info* out) {
+    if (!out) return umnn_fail(UMNN_EINVAL, "launch plan: out must be non-null");
+    memset(out, 0, sizeof(*out));
+    out->name = "";
+    if (kind < UMNN_PLAN_FORWARD || kind > UMNN_PLAN_SOLVE_BLOCK) return umnn_fail(UMNN_EINVAL, "launch plan: unknown kind");
+    MlpDev m;
+    int tmax = 0, ksu = 0;
+    if (int rc = umnn_prepare_mlp(net, E, &m, &tmax, &ksu)) return rc;
+    if (nb_steps < 1 || B < 0 || d < 1) return umnn_fail(UMNN_EINVAL, "launch plan: nb_steps >= 1, B >= 0, d >= 1");
+    if (B == 0) return 0;
+    const long long NI = B * (long long)d;
+    const FwdCall call = kind == UMNN_PLAN_FORWARD ? fwd_call_forward(NI, nb_steps, (flags & UMNN_PLAN_MARKER_ALIASED) != 0, (flags & UMNN_PLAN_Z2_SAVED) != 0)
+                         : kind == UMNN_PLAN_SEARCH ? fwd_call_search(B, nb_steps) : fwd_call_solve(kind == UMNN_PLAN_SOLVE ? B : NI, nb_steps);
+    const FwdPlan pl = fwd_plan(m, tmax, ksu, call, umnn_fwd_options(), umnn_num_cus());
+    if (pl.error) return umnn_fail(pl.error, pl.error_text);
+    out->name = pl.name; out->pieces = pl.nparts; out->P = pl.P; out->ns = pl.ns; out->waves_per_block = pl.wpb;
+    out->blocks = (long long)pl.blocks; out->lds_bytes = (long long)pl.lds_bytes; out->fallback = pl.fallback;
+    return 0;
 }
 
 extern "C" int umnn_cc_forward(const umnn_mlp* net, const float* x0, const float* x, const float* h,
@@ -384,8 +330,7 @@ extern "C" long long umnn_cc_forward_z2_floats(const umnn_mlp* net, long long B,
     int tmax = 0, ksu = 0;
     if (umnn_prepare_mlp(net, E, &m, &tmax, &ksu) || B <= 0 || d < 1 || nb_steps < 1) return 0;
     const int L = m.n_linear - 1;
-    if (L < 3 || L > 5 || m.t_out[1] < 5 || m.t_out[1] > 8) return 0;
-    for (int l = 2; l <= L; ++l) if (m.t_out[l] > 4) return 0;
+    if (!fwd_wide_first_shape(m) || L < 3 || L > 5) return 0;      // (the three-stage backward holds 2..4 layers after the cut)
     const UmnnOptions& opt = umnn_options();
     if (opt.fwd_precision == UMNN_PRECISION_FP32 || opt.fwd_precision == UMNN_PRECISION_BF16X6 || opt.bwd_precision != UMNN_PRECISION_BF16X3) return 0;
     const long long tiles = (B * (long long)d + 15) / 16, nl2 = (net->widths[2] + 1 + 3) / 4;

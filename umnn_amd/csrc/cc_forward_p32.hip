@@ -21,6 +21,7 @@
 #endif
 #include "cc_bf16.h"
 #include "cc_fwd_bf16_kernel.h"
+#include "cc_fwd_launch.h"
 using namespace UMNN_FWD_NS;
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
@@ -367,28 +368,12 @@ __global__ __launch_bounds__(UMNN_BLOCK) void cc_fwd_p32_kernel(const FwdBf16Arg
     fwd_epilogue<2>(a, lds, F2, fx2, fx02, ok2, q2, dx2, live, 0, 1, wid, g, p);
 }
 
-// Launches the 32x32x16 kernel when the shape is the flagship one: >= 2 hidden layers, every one 48..51 wide (13 K-steps of 4
-// in the fp32 numbering), bf16x3, one node range per wave.  UMNN_EUNSUPPORTED otherwise (the caller goes on with its own plan).
-int umnn_launch_forward_p32(FwdArgs& a, const umnn_mlp* net, int nb_steps, hipStream_t stream) {
-    const int L = a.m.n_linear - 1;
-    if (L < 2 || L > 5) return UMNN_EUNSUPPORTED;
-    for (int l = 1; l <= L; ++l)
-        if (a.m.ks_in[l] != 13) return UMNN_EUNSUPPORTED;
-    FwdBf16Args args;
+// Executes a plan of the 32x32x16 family (cc_fwd_plan.h: fwd_p32_shape, fwd_images_p32; variant = hidden layers - 2).
+static_assert(P32_IMG == FWD_P32_IMAGE_USHORTS, "the plan sizes the images the kernel stages");
+int umnn_launch_forward_p32(const FwdPlan& pl, const FwdArgs& a, double flops, hipStream_t stream) {
+    static void (*const kFns[])(const FwdBf16Args) = {cc_fwd_p32_kernel<1>, cc_fwd_p32_kernel<2>, cc_fwd_p32_kernel<3>, cc_fwd_p32_kernel<4>};
+    if (pl.family != FWD_FAMILY_P32 || pl.variant < 0 || pl.variant > 3) return umnn_fail(UMNN_EUNSUPPORTED, kFwdPlanError);
+    FwdBf16Args args{};
     args.f = a;
-    const size_t img_bytes = (size_t)(L - 1) * P32_IMG * sizeof(unsigned short);
-    args.f.m.lds_off[L] = (int)((img_bytes / 4 + 3) & ~(size_t)3);
-    const size_t lds_bytes = (size_t)args.f.m.lds_off[L] * sizeof(float);
-    if (lds_bytes > 160 * 1024) return UMNN_EUNSUPPORTED;
-    void (*kfn)(const FwdBf16Args) = L == 2 ? cc_fwd_p32_kernel<1> : L == 3 ? cc_fwd_p32_kernel<2> : L == 4 ? cc_fwd_p32_kernel<3>
-                                                                                                            : cc_fwd_p32_kernel<4>;
-    if (int rc = umnn_allow_lds((const void*)kfn, lds_bytes)) return rc;
-    args.f.ns = 1;
-    args.f.ngroups = (unsigned)((a.NI + 31) / 32);
-    const unsigned nblk = (args.f.ngroups + UMNN_WAVES_PER_BLOCK - 1) / UMNN_WAVES_PER_BLOCK;
-    umnn_prof_begin(stream);
-    hipLaunchKernelGGL(kfn, dim3(nblk), dim3(UMNN_BLOCK), lds_bytes, stream, args);
-    umnn_prof_end(stream, umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI);
-    umnn_note_launch("cc_fwd_bf16<32x32x16,PARTS=2,P=2,EXACT=1,LIVE=26,PIPE32>");
-    return umnn_check(hipGetLastError(), "cc_fwd_p32 launch");
+    return umnn_fwd_launch(kFns[pl.variant], pl, args, args.f, flops, "cc_fwd_p32 launch", stream, nullptr, umnn_fwd_no_fallback);
 }

@@ -30,7 +30,7 @@ struct FwdArgs {
     long long NI;      // B*d integrals
     int d, E, n, ns, inv_f;
     unsigned ngroups;  // tile groups (of 16*P integrals)
-    // fp16-piece launches and their queued bf16 fallback (cc_forward_bf16.hip, "overflow protocol" there).  ovf_mode 0: plain launch.
+    // fp16-piece launches and their queued bf16 fallback (cc_fwd_launch.h, "overflow protocol" there).  ovf_mode 0: plain launch.
     // 1 (the fp16 build): a tile group whose quadrature sum is not finite -- an overflowed fp16 piece always ends there -- writes
     // nothing but a NaN into its slots of the MARKER output (F, or z for the flow entry points), does not count towards the one-pass
     // log-likelihood, and raises *ovf_flag to ovf_gen.  2 (the bf16 build queued right behind it with the same group mapping): returns

@@ -13,6 +13,11 @@ int umnn_check(hipError_t e, const char* what);           // 0 or records + retu
 int umnn_prepare_mlp(const umnn_mlp* net, int E, MlpDev* out, int* tmax, int* ksu);
 int umnn_check_io(const umnn_io* io);                     // 0, or UMNN_EINVAL for an unknown dtype code
 int umnn_num_cus();                                      // CU count of the CURRENT device (cached per device)
+constexpr size_t UMNN_LDS_LIMIT = 160 * 1024;            // bytes of LDS one workgroup may take (gfx950: 160 KiB per CU)
+// Overflow protocol of the fp16-piece launches (cc_fwd_launch.h): mode 1 = the fp16 launch, 2 = the bf16 build queued behind it;
+// the flag word and generation number of the pair come from umnn_ovf_slot (cc_api.hip)
+struct UmnnOvfPlan { int mode; unsigned long long* flag; unsigned long long gen; };
+int umnn_ovf_slot(unsigned long long** flag, unsigned long long* gen);
 
 // Process-wide launch options.  The UMNN_* environment variables are read ONCE (first use, or umnn_reload_env());
 // after that every launch reads plain atomics -- no getenv on the launch path.  -1 = "auto" for the tuning knobs.

@@ -10,45 +10,44 @@
 // Under fwd_precision = fp32 / bf16x6 ("the reference's arithmetic everywhere") nets of up to four tiles per layer run the same
 // search with THREE bf16 pieces and six cross terms (PARTS=3: fp32-level products, ~4e-7 on F -- the matrix-core arithmetic of the
 // bf16x6 forward mode; there is no fp32-MFMA form of this kernel); wider nets, whose three-piece form does not fit the register
-// file (8 tiles x 3 pieces), run the two-fp16-piece search of the f16x3 mode instead (inv_mode, cc_inv_launch.h: tables and launcher, shared with cc_solve.hip).
+// file (8 tiles x 3 pieces), run the two-fp16-piece search of the f16x3 mode instead (fwd_plan_inverse, cc_fwd_plan.h: the launch plan, shared with cc_solve.hip).
 // This file is compiled twice, like cc_forward_bf16.hip: as is (bf16 pieces; exports umnn_flow_invert_dim) and through cc_invert_f16.hip
 // with -DUMNN_FWD_PIECE_F16 (fp16 pieces: the search of the library's default arithmetic, f16x3).  The fp16 build follows the
-// forward's overflow protocol (cc_forward_bf16.hip): a sample for which any candidate integral of any round was not finite gets a NaN
+// forward's overflow protocol (cc_fwd_launch.h): a sample for which any candidate integral of any round was not finite gets a NaN
 // in its slot of x_inv[:, j] and raises the launch's flag word; the two-piece bf16 build of the same search, queued right behind it,
 // returns at once when the flag is down and otherwise redoes exactly the samples whose slot holds the NaN.
 #ifndef UMNN_ASM_TIED
 #define UMNN_ASM_TIED 1      // cc_common.h: inline-assembly outputs tied to inputs in the forward translation units
 #endif
 #ifdef UMNN_FWD_PIECE_F16
-#define INV_KNAME "cc_invert_f16"
+#define INV_ROWS kInvertRowsF16
 #define INV_IMPL umnn_invert_impl_f16
 #else
-#define INV_KNAME "cc_invert_bf16"
+#define INV_ROWS kInvertRowsBf16
 #define INV_IMPL umnn_invert_impl_bf16
 #endif
 #define INV_MODE 1
+#define INV_WHAT "invert"
 #include "cc_inv_launch.h"
-int umnn_invert_impl_bf16(const umnn_mlp* net, const float* h, const float* z, const float* scaling, const float* cc_w, const float* cc_s,
-                          int nb_steps, long long B, int d, int E, int j, int iters, float* x_inv, hipStream_t stream, int nparts,
-                          const InvOvfPlan* ovf);
-int umnn_invert_impl_f16(const umnn_mlp* net, const float* h, const float* z, const float* scaling, const float* cc_w, const float* cc_s,
-                         int nb_steps, long long B, int d, int E, int j, int iters, float* x_inv, hipStream_t stream, int nparts,
-                         const InvOvfPlan* ovf);
+struct InvertCall {     // the operands of umnn_flow_invert_dim
+    const float *h, *z, *scaling, *cc_w, *cc_s;
+    int nb_steps;
+    long long B;
+    int d, E, j, iters;
+    float* x_inv;
+};
+int umnn_invert_impl_bf16(const FwdPlan& pl, const InvertCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
+int umnn_invert_impl_f16(const FwdPlan& pl, const InvertCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
 
 // One launch of the search (see the file header): one tile (= one sample) per wave, or per workgroup.
-int INV_IMPL(const umnn_mlp* net, const float* h, const float* z, const float* scaling, const float* cc_w, const float* cc_s,
-             int nb_steps, long long B, int d, int E, int j, int iters, float* x_inv, hipStream_t stream, int nparts,
-             const InvOvfPlan* ovf) {
+int INV_IMPL(const FwdPlan& pl, const InvertCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf) {
     FwdBf16Args args{};
     FwdArgs& a = args.f;
-    a.h = h; a.ccw = cc_w; a.ccs = cc_s; a.scaling = scaling;
-    a.inv_z = z; a.inv_x = x_inv; a.inv_j = j; a.inv_iters = iters;
-    a.NI = B; a.d = d; a.E = E; a.n = nb_steps;
-    // algorithmic work: iters rounds x 10 candidate integrals per sample
-    const InvJob job{"invert", B, 16, umnn_cc_forward_flops_per_integral(net, nb_steps) * 10.0 * iters * (double)B};
-    return inv_launch(net, args, job, nparts, stream, ovf, [&](const InvOvfPlan* second) {
-        return umnn_invert_impl_bf16(net, h, z, scaling, cc_w, cc_s, nb_steps, B, d, E, j, iters, x_inv, stream, 2, second);
-    });
+    a.h = c.h; a.ccw = c.cc_w; a.ccs = c.cc_s; a.scaling = c.scaling;
+    a.inv_z = c.z; a.inv_x = c.x_inv; a.inv_j = c.j; a.inv_iters = c.iters;
+    a.NI = c.B; a.d = c.d; a.E = c.E; a.n = c.nb_steps;
+    return inv_launch(pl, args, flops, stream, ovf,
+                      [&](const UmnnOvfPlan& second) { return umnn_invert_impl_bf16(pl, c, flops, stream, &second); });
 }
 
 #ifndef UMNN_FWD_PIECE_F16
@@ -63,9 +62,12 @@ extern "C" int umnn_flow_invert_dim(const umnn_mlp* net, const float* h, const f
     if (int rc = umnn_prepare_mlp(net, E, &m, &tmax, &ksu)) return rc;
     if (B == 0) return 0;
     if (!h || !z || !scaling || !cc_w || !cc_s || !x_inv) return umnn_fail(UMNN_EINVAL, "invert: null pointer");
-    if (m.n_linear - 1 < 2) return umnn_fail(UMNN_EUNSUPPORTED, "invert: the matrix-core kernels need at least two hidden layers");
-    const InvMode md = inv_mode(tmax);          // (never a silent ~6e-6 search under fp32 / bf16x6)
-    return (md.f16 ? umnn_invert_impl_f16 : umnn_invert_impl_bf16)(net, h, z, scaling, cc_w, cc_s, nb_steps, B, d, E, j, iters, x_inv,
-                                                                  stream, md.nparts, nullptr);
+    // (build and pieces by fwd_precision -- never a silent ~6e-6 search under fp32 / bf16x6: fwd_plan_inverse)
+    const FwdPlan pl = fwd_plan(m, tmax, ksu, fwd_call_search(B, nb_steps), umnn_fwd_options(), umnn_num_cus());
+    if (pl.error) return umnn_fail(pl.error, pl.error_text);
+    // algorithmic work: iters rounds x 10 candidate integrals per sample
+    const double flops = umnn_cc_forward_flops_per_integral(net, nb_steps) * 10.0 * iters * (double)B;
+    return (pl.f16 ? umnn_invert_impl_f16 : umnn_invert_impl_bf16)(pl, InvertCall{h, z, scaling, cc_w, cc_s, nb_steps, B, d, E, j, iters, x_inv},
+                                                                  flops, stream, nullptr);
 }
 #endif

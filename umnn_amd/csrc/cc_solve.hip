@@ -3,9 +3,9 @@
 // spends 10 x iter quadratures per sample on a tile of its own, this uses what every quadrature already returns -- node 0 is x, so
 // f(x) = dF/dx comes with F -- and converges in a handful of them, with the forward's layout: sixteen rows per tile, lane p = row
 // 16 tile + p, each with its own iterate, bracket and done flag (the INV = 2 variants of cc_fwd_bf16_kernel.h).
-// The variant tables, the launch plan (small batches: one tile per workgroup, where the partial sums and f(x) of the waves meet in LDS
+// The variants, the launch plan (small batches: one tile per workgroup, where the partial sums and f(x) of the waves meet in LDS
 // once per iteration in a fixed order, so every wave sees the same totals and takes the same branch -- 100 x 784 image sampling lives
-// there) and the arithmetic modes are cc_inv_launch.h's, shared with the search: two fp16 pieces by default (this file compiled through
+// there) and the arithmetic modes are cc_fwd_plan.h's (fwd_plan_inverse), shared with the search: two fp16 pieces by default (this file compiled through
 // cc_solve_f16.hip with -DUMNN_FWD_PIECE_F16), two bf16 pieces under bf16x3, three under fp32 / bf16x6 for nets of up to four tiles per
 // layer.  Overflow protocol of the fp16 build: a row one of whose iterates produced a non-finite integral gets a NaN in its x slot and
 // raises the launch's flag word; the two-piece bf16 build, queued right behind, returns at once when the flag is down and otherwise
@@ -16,13 +16,14 @@
 #define UMNN_ASM_TIED 1      // cc_common.h: inline-assembly outputs tied to inputs in the forward translation units
 #endif
 #ifdef UMNN_FWD_PIECE_F16
-#define INV_KNAME "cc_solve_f16"
+#define INV_ROWS kSolveRowsF16
 #define INV_IMPL umnn_solve_impl_f16
 #else
-#define INV_KNAME "cc_solve_bf16"
+#define INV_ROWS kSolveRowsBf16
 #define INV_IMPL umnn_solve_impl_bf16
 #endif
 #define INV_MODE 2
+#define INV_WHAT "solve"
 #include "cc_inv_launch.h"
 struct SolveCall {      // the operands of umnn_cc_solve; umnn_cc_solve_block (block != 0): B = the B d flat rows, strides 1, j = 0
     const float *h, *target, *scale_row, *scaling, *off_row, *cc_w, *cc_s;
@@ -34,11 +35,11 @@ struct SolveCall {      // the operands of umnn_cc_solve; umnn_cc_solve_block (b
     int block;
     const float* x_init;
 };
-int umnn_solve_impl_bf16(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int nparts, const InvOvfPlan* ovf);
-int umnn_solve_impl_f16(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int nparts, const InvOvfPlan* ovf);
+int umnn_solve_impl_bf16(const FwdPlan& pl, const SolveCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
+int umnn_solve_impl_f16(const FwdPlan& pl, const SolveCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
 
 // One launch of the solve (see the file header): one tile (sixteen rows) per wave, or per workgroup.
-int INV_IMPL(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int nparts, const InvOvfPlan* ovf) {
+int INV_IMPL(const FwdPlan& pl, const SolveCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf) {
     FwdBf16Args args{};
     FwdArgs& a = args.f;
     a.x = c.x_init; a.h = c.h; a.ccw = c.cc_w; a.ccs = c.cc_s; a.fx = c.f_x; a.scaling = c.scaling;
@@ -47,15 +48,11 @@ int INV_IMPL(const umnn_mlp* net, const SolveCall& c, hipStream_t stream, int np
     args.sv.off_h0 = c.off_h0; args.sv.status = c.status; args.sv.lo = c.lo; args.sv.hi = c.hi; args.sv.tol = c.tol;
     args.sv.block = c.block;
     a.NI = c.B; a.d = c.d; a.E = c.E; a.n = c.nb_steps;
-    // algorithmic work: the iteration count is decided inside the launch -- booked at four quadratures per row, the typical count
-    // (scratch: the partial sums and f(x) of a split tile)
-    const InvJob job{"solve", (c.B + 15) / 16, 2 * 16, umnn_cc_forward_flops_per_integral(net, c.nb_steps) * 4.0 * (double)c.B};
-    return inv_launch(net, args, job, nparts, stream, ovf,
-                      [&](const InvOvfPlan* second) { return umnn_solve_impl_bf16(net, c, stream, 2, second); });
+    return inv_launch(pl, args, flops, stream, ovf, [&](const UmnnOvfPlan& second) { return umnn_solve_impl_bf16(pl, c, flops, stream, &second); });
 }
 
 #ifndef UMNN_FWD_PIECE_F16
-// Validation and arithmetic mode (inv_mode) of both entry points.
+// Validation and launch plan (build and pieces by fwd_precision: fwd_plan_inverse) of both entry points.
 static int solve_entry(const umnn_mlp* net, const SolveCall& c, hipStream_t stream) {
     if (!net) return umnn_fail(UMNN_EINVAL, "net is null");
     if (c.nb_steps < 1 || c.max_iter < 1 || c.max_iter > UMNN_SOLVE_EVALS_MASK)
@@ -68,9 +65,11 @@ static int solve_entry(const umnn_mlp* net, const SolveCall& c, hipStream_t stre
     if (int rc = umnn_prepare_mlp(net, c.E, &m, &tmax, &ksu)) return rc;
     if (c.B == 0) return 0;
     if (!c.h || !c.target || !c.cc_w || !c.cc_s || !c.x) return umnn_fail(UMNN_EINVAL, "solve: null pointer");
-    if (m.n_linear - 1 < 2) return umnn_fail(UMNN_EUNSUPPORTED, "solve: the matrix-core kernels need at least two hidden layers");
-    const InvMode md = inv_mode(tmax);
-    return (md.f16 ? umnn_solve_impl_f16 : umnn_solve_impl_bf16)(net, c, stream, md.nparts, nullptr);
+    const FwdPlan pl = fwd_plan(m, tmax, ksu, fwd_call_solve(c.B, c.nb_steps), umnn_fwd_options(), umnn_num_cus());
+    if (pl.error) return umnn_fail(pl.error, pl.error_text);
+    // algorithmic work: the iteration count is decided inside the launch -- booked at four quadratures per row, the typical count
+    const double flops = umnn_cc_forward_flops_per_integral(net, c.nb_steps) * 4.0 * (double)c.B;
+    return (pl.f16 ? umnn_solve_impl_f16 : umnn_solve_impl_bf16)(pl, c, flops, stream, nullptr);
 }
 
 extern "C" int umnn_cc_solve(const umnn_mlp* net, const float* h, const float* target, long long t_stride,
