@@ -179,6 +179,22 @@ int umnn_cc_solve(const umnn_mlp* net, const float* h, const float* target, long
                   float lo, float hi, float tol, int max_iter,
                   float* x, long long x_stride, float* f_x, int* status, void* stream);
 
+/* umnn_cc_solve that also accumulates the log-Jacobian of the map at the x it returns -- the density of a sample from the solves that
+ * drew it (UMNNMAFFlow.sample_and_log_prob).  The last quadrature of a row's solve has x as its node 0, so f(x) is in registers:
+ *     lj_row[b] = (lj_first ? 0 : lj_row[b]) + log(f(x_b) + 1e-10) + s,
+ *     s = scaling[j] when scaling is non-null (the stored value), else log(scale_row[b]) when scale_row is, else 0
+ * written by the wave that publishes row b: one writer per row and launch, a plain read-modify-write, bit-reproducible.  Calling it
+ * for j = 0..d-1 with lj_first = 1 on the first call leaves sum_j log|dG_j/dx_j| in lj_row; lj_first = 1 overwrites whatever the
+ * buffer held.  lj_row [B] nullable (then exactly umnn_cc_solve); must not alias the other operands.  A row that ends
+ * UMNN_SOLVE_NONFINITE makes lj_row[b] NaN; UMNN_SOLVE_CLAMPED / _CAPPED rows add the value at the x they return.  Under the
+ * fp16-piece overflow protocol a row the first launch defers adds nothing there and is added by the queued pass: every row is
+ * counted once in every arithmetic mode.  Same kernels, launch plan and launch count as umnn_cc_solve. */
+int umnn_cc_solve_lj(const umnn_mlp* net, const float* h, const float* target, long long t_stride,
+                     const float* scale_row, const float* scaling, const float* off_row, int off_h0,
+                     const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int j,
+                     float lo, float hi, float tol, int max_iter,
+                     float* x, long long x_stride, float* f_x, int* status, float* lj_row, int lj_first, void* stream);
+
 /* The same solve for every (row, dimension) pair of a flow block in ONE launch -- the inverse of a block under a GIVEN embedding, the
  * step of the Jacobi iteration behind invert(method="jacobi"): for every (b, i)
  *     scale_i * (off_bi + int_0^{x_bi} f(t; h[b, :, i]) dt) = target[b, i]        for x_bi in [lo, hi],
@@ -253,6 +269,13 @@ int umnn_flow_block_cotangents(const float* g_z, const float* g_log_jac, const f
                                long long B, int d, int reverse_z, float* gF, float* g_fx, void* stream);
 int umnn_flow_ll_forward(const float* z, const float* log_jac, long long B, int d, float* ll, void* stream);
 int umnn_flow_ll_backward(const float* z, const float* g_ll, long long B, int d, float* g_z, float* g_log_jac, void* stream);
+/* Log-density of a drawn sample (UMNNMAFFlow.sample_and_log_prob), one launch each, one wave per row, fixed summation order.
+ * umnn_flow_sample_lj_rows: lj_row[b] = (first ? 0 : lj_row[b]) + sum_i (log(f_x[b,i] + 1e-10) + scaling[i]) -- a block's log|det J|
+ *   from the f_x [B,d] its last Jacobi sweep (umnn_cc_solve_block) wrote; first is 0 or 1.
+ * umnn_flow_sample_ll: ll[b] = lj_row[b] - 1/2 sum_i (log 2 pi + z[b,i]^2), z [B,d] the noise the sample was drawn from; ll must not
+ *   alias lj_row.  B = 0: no launch. */
+int umnn_flow_sample_lj_rows(const float* f_x, const float* scaling, long long B, int d, int first, float* lj_row, void* stream);
+int umnn_flow_sample_ll(const float* z, const float* lj_row, long long B, int d, float* ll, void* stream);
 /* One adjoint Jacobi sweep's elementwise step (the gradient through a sample x = T^-1(z), umnn_amd/inverse.py): with J = dT/dx lower
  * triangular and D = exp(log_jac) its diagonal, J^T lam = g is iterated as lam <- lam + (g - r) / D, r = J^T lam the block's VJP.
  *     lam_out[q] = lam[q] + (g[q] - r[q]) exp(-log_jac[q])      over the B d entries, all [B,d] fp32; lam_out may be lam.

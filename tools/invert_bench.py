@@ -28,6 +28,11 @@ Row ``newton_progressive`` is ``invert(method="newton", conditioner="progressive
 its ``GraphedSampler`` replay); ``--conditioner`` sets the conditioner of the ``bracket`` and ``newton`` rows themselves (default "full").
 Every row carries ``made_launches``, the conditioner-kernel launches of its last call (progressive: d per block).  A tree without the
 option (``--root``) gives the other rows only.
+``--log-prob`` times the sample WITH its log-density: per method (``newton``, ``newton_progressive``, ``jacobi``) the rows ``<method>_sample``
+(``flow.sample(n)``), ``<method>_sample_and_log_prob`` (``flow.sample_and_log_prob(n)``: the density from the solves that drew the sample)
+and ``<method>_sample_then_log_prob`` (``sample`` followed by ``log_prob(x)``: a second conditioner and quadrature pass), alternating in
+every round on the same seeded noise, at the C3 block (case ``c3``), the five-block C3 flow (``c3_flow``) and the MNIST-shaped block
+(``mnist``); every row carries ``max_abs_dev_log_prob``, its density against ``log_prob(x)`` of its own x.
 """
 import argparse
 import inspect
@@ -51,6 +56,7 @@ def main():
     ap.add_argument("--adj-tol", type=float, default=None, help="--grad: adj_tol of the rsample_backward row (default: the method's own)")
     ap.add_argument("--grad", action="store_true", help="time rsample + backward and the adjoint sweeps instead of the solves")
     ap.add_argument("--graph", action="store_true", help="time eager invert against GraphedSampler replays (newton and fixed-sweep jacobi)")
+    ap.add_argument("--log-prob", action="store_true", help="time sample, sample_and_log_prob and sample + log_prob (newton, both conditioners; jacobi)")
     args = ap.parse_args()
     sys.path.insert(0, os.path.abspath(args.root))
     import torch
@@ -106,6 +112,10 @@ def main():
     if args.graph:
         results += graph_mode(args, umnn_amd, torch, dev, shapes, only if args.only != ap_default_only else {"c3", "mnist", "toy"},
                               methods, measure, sync_time, has_progressive, cond)
+        only = set()
+    if args.log_prob:
+        results += log_prob_mode(args, umnn_amd, torch, dev, shapes, only if args.only != ap_default_only else {"c3", "c3_flow", "mnist"},
+                                 methods, measure)
         only = set()
     with torch.no_grad():
         for case, c in [(name + tag, dict(c, made_gain=gain)) for name, c in shapes.items() for tag, gain in (("", 1.), ("_made3", 3.))]:
@@ -209,6 +219,50 @@ def graph_mode(args, umnn_amd, torch, dev, shapes, only, methods, measure, sync_
                 out = dict(max_abs_err_x=float((outs[k] - x).abs().max()), **meta.get(k, {}))
                 if k == "jacobi_graph":
                     out["last_move"] = float(jsampler.last_move)
+                return out
+            results += measure(case, fns, extra)
+            del flow, fns
+            torch.cuda.empty_cache()
+    return results
+
+
+def log_prob_mode(args, umnn_amd, torch, dev, shapes, only, methods, measure):
+    """The ``--log-prob`` rows: ``sample``, ``sample_and_log_prob`` and ``sample`` + ``log_prob`` per method, on the same seeded noise."""
+    results = []
+    cases = {"c3": dict(shapes["c3"], nb_flow=1), "c3_flow": dict(shapes["c3"], nb_flow=5), "mnist": dict(shapes["mnist"], nb_flow=1)}
+    solve = {"newton": dict(method="newton"), "newton_progressive": dict(method="newton", conditioner="progressive"),
+             "jacobi": dict(method="jacobi")}
+    with torch.no_grad():
+        for case, c in cases.items():
+            if case not in only:
+                continue
+            torch.manual_seed(0)
+            flow = umnn_amd.UMNNMAFFlow(nb_flow=c["nb_flow"], nb_in=c["d"], hidden_derivative=c["hd"], hidden_embedding=c["he"],
+                                        embedding_s=c["E"], nb_steps=c["n"], solver="CCParallel").to(dev).eval()
+            B = c["B"]
+
+            def gen():
+                return torch.Generator(device=dev).manual_seed(1)
+
+            fns = {}
+            for m, o in solve.items():
+                if m not in methods:
+                    continue
+                fns[m + "_sample"] = lambda o=o: (flow.sample(B, generator=gen(), **o), None)
+                fns[m + "_sample_and_log_prob"] = lambda o=o: flow.sample_and_log_prob(B, generator=gen(), **o)
+
+                def two_calls(o=o):
+                    x = flow.sample(B, generator=gen(), **o)
+                    return x, flow.log_prob(x)
+                fns[m + "_sample_then_log_prob"] = two_calls
+
+            def extra(k, outs):
+                x, lp = outs[k]
+                out = dict(nb_flow=c["nb_flow"], B=B, d=c["d"])
+                if lp is not None:
+                    ref = flow.log_prob(x)
+                    out["max_abs_dev_log_prob"] = float((lp - ref).abs().max())
+                    out["max_rel_dev_log_prob"] = float(((lp - ref).abs() / ref.abs().clamp(min=1.)).max())
                 return out
             results += measure(case, fns, extra)
             del flow, fns

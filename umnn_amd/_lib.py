@@ -73,6 +73,9 @@ SIGNATURES = {
     "umnn_cc_solve": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _ll, _fp, _fp, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int,
                                      _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                      ctypes.c_int, _fp, _ll, _fp, _fp, _fp]),
+    "umnn_cc_solve_lj": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _ll, _fp, _fp, _fp, ctypes.c_int, _fp, _fp, ctypes.c_int,
+                                        _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
+                                        ctypes.c_int, _fp, _ll, _fp, _fp, _fp, ctypes.c_int, _fp]),
     "umnn_cc_solve_block": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, ctypes.c_int, _fp, _fp, _fp, ctypes.c_int,
                                            _ll, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_float, ctypes.c_float,
                                            ctypes.c_int, _fp, _fp, _fp, _fp]),
@@ -120,6 +123,8 @@ SIGNATURES = {
     "umnn_flow_block_cotangents": (ctypes.c_int, [_fp, _fp, _fp, _fp, _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp]),
     "umnn_flow_ll_forward": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp]),
     "umnn_flow_ll_backward": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp, _fp]),
+    "umnn_flow_sample_lj_rows": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, ctypes.c_int, _fp, _fp]),
+    "umnn_flow_sample_ll": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp]),
     "umnn_flow_adjoint_update": (ctypes.c_int, [_fp, _fp, _fp, _fp, _ll, ctypes.c_int, ctypes.c_float, _fp, _fp, _fp]),
     "umnn_made_split3": (ctypes.c_int, [_fp, _ll, ctypes.c_int, ctypes.c_int, _fp, ctypes.c_int, _fp]),
     "umnn_made_launch_count": (ctypes.c_longlong, []),

@@ -7,6 +7,9 @@
 //   umnn_flow_ll_backward        its backward: g_log_jac = g_ll, g_z = -z g_ll
 // and of the adjoint Jacobi sweeps behind a differentiable sample (inverse.py FlowBlockInverse.backward):
 //   umnn_flow_adjoint_update     lam <- lam + (g - J^T lam) / D,  D = exp(log_jac), and the convergence / non-finite bits of g - J^T lam
+// and of the log-density of a drawn sample (flow.py sample_and_log_prob):
+//   umnn_flow_sample_lj_rows     lj_row (+)= sum_i (log(f_x + 1e-10) + s_i), the f_x of a Jacobi block's last sweep
+//   umnn_flow_sample_ll          ll = lj_row - 1/2 sum_i (log 2 pi + z_i^2)
 #include "cc_host.h"
 
 __global__ __launch_bounds__(256) void flow_block_cotangents_kernel(const float* __restrict__ g_z, const float* __restrict__ g_lj,
@@ -73,6 +76,54 @@ extern "C" int umnn_flow_ll_backward(const float* z, const float* g_ll, long lon
     hipLaunchKernelGGL(flow_ll_backward_kernel, dim3((unsigned)((NI + 255) / 256)), dim3(256), 0, (hipStream_t)stream, z, g_ll, NI, d, g_z,
                        g_log_jac);
     return umnn_check(hipGetLastError(), "flow_ll_backward launch");
+}
+
+// ---- log-density of a drawn sample from the solves that drew it (UMNNMAFFlow.sample_and_log_prob) ----
+// one wave per row, lane-strided loads, the fixed butterfly of flow_ll_forward_kernel (deterministic)
+//   umnn_flow_sample_lj_rows   lj_row[b] (+)= sum_i (log(f_x[b,i] + 1e-10) + s_i): a block's log|det J| from the f_x of its last Jacobi sweep
+//   umnn_flow_sample_ll        ll[b] = lj_row[b] - 1/2 sum_i (log 2 pi + z[b,i]^2)
+__global__ __launch_bounds__(256) void flow_sample_lj_rows_kernel(const float* __restrict__ f_x, const float* __restrict__ scaling, long long B,
+                                                                  int d, int first, float* __restrict__ lj_row) {
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    float s = 0.f;
+    for (int e = lane; e < d; e += 64) s += __logf(f_x[b * d + e] + 1e-10f) + scaling[e];
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) lj_row[b] = (first ? 0.f : lj_row[b]) + s;
+}
+__global__ __launch_bounds__(256) void flow_sample_ll_kernel(const float* __restrict__ z, const float* __restrict__ lj_row, long long B, int d,
+                                                             float* __restrict__ ll) {
+    const long long b = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;
+    const int lane = threadIdx.x & 63;
+    float s = 0.f;
+    for (int e = lane; e < d; e += 64) {
+        const float zz = z[b * d + e];
+        s += 0.5f * (1.8378770664093453f + zz * zz);
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) s += __shfl_xor(s, o);
+    if (lane == 0) ll[b] = lj_row[b] - s;
+}
+
+extern "C" int umnn_flow_sample_lj_rows(const float* f_x, const float* scaling, long long B, int d, int first, float* lj_row, void* stream) {
+    if (B < 0 || d < 1 || (first != 0 && first != 1)) return umnn_fail(UMNN_EINVAL, "flow sample lj: B >= 0, d >= 1, first is 0 or 1");
+    if (B == 0) return 0;
+    if (!f_x || !scaling || !lj_row) return umnn_fail(UMNN_EINVAL, "flow sample lj: null pointer");
+    if ((B + 3) / 4 > 0x7fffffffLL) return umnn_fail(UMNN_EINVAL, "flow sample lj: B too large for one launch");
+    hipLaunchKernelGGL(flow_sample_lj_rows_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, f_x, scaling, B, d, first,
+                       lj_row);
+    return umnn_check(hipGetLastError(), "flow_sample_lj_rows launch");
+}
+extern "C" int umnn_flow_sample_ll(const float* z, const float* lj_row, long long B, int d, float* ll, void* stream) {
+    if (B < 0 || d < 1) return umnn_fail(UMNN_EINVAL, "flow sample ll: B >= 0, d >= 1");
+    if (B == 0) return 0;
+    if (!z || !lj_row || !ll) return umnn_fail(UMNN_EINVAL, "flow sample ll: null pointer");
+    if ((B + 3) / 4 > 0x7fffffffLL) return umnn_fail(UMNN_EINVAL, "flow sample ll: B too large for one launch");
+    hipLaunchKernelGGL(flow_sample_ll_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, z, lj_row, B, d, ll);
+    return umnn_check(hipGetLastError(), "flow_sample_ll launch");
 }
 
 // lam and lam_out may be the same buffer (each thread reads its own entry before it writes it): no __restrict__ on them

@@ -223,8 +223,13 @@ struct SolveArgs {
     float lo = 0.f, hi = 0.f, tol = 0.f;
     // umnn_cc_solve_block: the rows are the flat [B, d] index q (strides 1, inv_j = 0); row q reads the embedding of sample q / d,
     // dimension q - (q / d) d, and scaling of that dimension -- the forward kernel's mapping.  Read in the per-tile setup only.
-    // (an int in the struct's tail padding: the kernel arguments keep their size, so nothing the other kernels read moves)
     int block = 0;
+    // umnn_cc_solve_lj: the running log-Jacobian of the rows, lj_row[b] = (lj_first ? 0 : lj_row[b]) + log(f(x_b) + 1e-10) + s with
+    // s = scaling[inv_j] | log(scale_row[b]) | 0, written by the wave that publishes the row (one writer per row and launch; a row
+    // the fp16 build defers is added by the queued build).  Null (every other entry point): nothing is read or written.
+    // (last in the last struct of the kernel arguments: nothing the other kernels read moves)
+    float* lj_row = nullptr;
+    int lj_first = 0;
 };
 constexpr int SOLVE_CLAMPED = 1 << 16, SOLVE_CAPPED = 1 << 17, SOLVE_NONFINITE = 1 << 18;      // = UMNN_SOLVE_* of umnn_cc.h
 
@@ -970,6 +975,13 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 if (!defer) {
                     if (a.fx) a.fx[qv[0]] = sv_fx;
                     if (args.sv.status) args.sv.status[qv[0]] = sv_stat;
+                    if (args.sv.lj_row) {
+                        // log|dG/dx| at the returned x (the forward epilogue's form, cc_fwd_shared.h); a non-finite row poisons its sum
+                        const float s = args.sv.scale_row ? __logf(sv_scale) : (a.scaling ? a.scaling[sv_col] : 0.f);
+                        const float lj = sv_bad ? __builtin_nanf("") : __logf(sv_fx + 1e-10f) + s;
+                        float* slot = args.sv.lj_row + qv[0];
+                        *slot = (args.sv.lj_first ? 0.f : *slot) + lj;
+                    }
                 }
             }
             if (__any(defer) && lane == 0 && part == 0) atomicMax(a.ovf_flag, a.ovf_gen);

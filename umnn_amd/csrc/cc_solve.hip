@@ -34,6 +34,8 @@ struct SolveCall {      // the operands of umnn_cc_solve; umnn_cc_solve_block (b
     int* status;
     int block;
     const float* x_init;
+    float* lj_row = nullptr;     // umnn_cc_solve_lj: the rows' running log-Jacobian (SolveArgs::lj_row), null otherwise
+    int lj_first = 0;
 };
 int umnn_solve_impl_bf16(const FwdPlan& pl, const SolveCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
 int umnn_solve_impl_f16(const FwdPlan& pl, const SolveCall& c, double flops, hipStream_t stream, const UmnnOvfPlan* ovf);
@@ -46,7 +48,7 @@ int INV_IMPL(const FwdPlan& pl, const SolveCall& c, double flops, hipStream_t st
     a.inv_z = c.target; a.inv_x = c.x; a.inv_j = c.j; a.inv_iters = c.max_iter;
     args.sv.t_stride = c.t_stride; args.sv.x_stride = c.x_stride; args.sv.scale_row = c.scale_row; args.sv.off_row = c.off_row;
     args.sv.off_h0 = c.off_h0; args.sv.status = c.status; args.sv.lo = c.lo; args.sv.hi = c.hi; args.sv.tol = c.tol;
-    args.sv.block = c.block;
+    args.sv.block = c.block; args.sv.lj_row = c.lj_row; args.sv.lj_first = c.lj_first;
     a.NI = c.B; a.d = c.d; a.E = c.E; a.n = c.nb_steps;
     return inv_launch(pl, args, flops, stream, ovf, [&](const UmnnOvfPlan& second) { return umnn_solve_impl_bf16(pl, c, flops, stream, &second); });
 }
@@ -79,6 +81,19 @@ extern "C" int umnn_cc_solve(const umnn_mlp* net, const float* h, const float* t
                              float* x, long long x_stride, float* f_x, int* status, void* stream_) {
     return solve_entry(net, SolveCall{h, target, scale_row, scaling, off_row, cc_w, cc_s, t_stride, x_stride, B, off_h0, nb_steps, d, E, j,
                                       max_iter, lo, hi, tol, x, f_x, status, 0, nullptr}, (hipStream_t)stream_);
+}
+
+// umnn_cc_solve that also adds the row's log-Jacobian at the returned x to lj_row (include/umnn_cc.h): the same launch, plan and kernel.
+extern "C" int umnn_cc_solve_lj(const umnn_mlp* net, const float* h, const float* target, long long t_stride,
+                                const float* scale_row, const float* scaling, const float* off_row, int off_h0,
+                                const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int j,
+                                float lo, float hi, float tol, int max_iter,
+                                float* x, long long x_stride, float* f_x, int* status, float* lj_row, int lj_first, void* stream_) {
+    if (lj_first != 0 && lj_first != 1) return umnn_fail(UMNN_EINVAL, "solve: lj_first is 0 or 1");
+    SolveCall c{h, target, scale_row, scaling, off_row, cc_w, cc_s, t_stride, x_stride, B, off_h0, nb_steps, d, E, j,
+                max_iter, lo, hi, tol, x, f_x, status, 0, nullptr};
+    c.lj_row = lj_row; c.lj_first = lj_first;
+    return solve_entry(net, c, (hipStream_t)stream_);
 }
 
 // The same solve for every (row, dimension) of a block in ONE launch (include/umnn_cc.h): the rows of the launch are the flat index

@@ -96,12 +96,15 @@ class GraphedLL:
 
 
 class GraphedSampler:
-    """The sampling direction as one hipGraph: ``GraphedSampler(flow, n, context=None, method="newton", warmup=1, **solve_opts)``
+    """The sampling direction as one hipGraph: ``GraphedSampler(flow, n, context=None, method="newton", warmup=1, log_prob=False, **solve_opts)``
     records ``flow.invert(z, method=...)`` -- a ``UMNNMAFFlow`` or a single ``UMNNMAF`` block -- on a static [n, d] noise buffer.
 
         sampler = umnn_amd.GraphedSampler(flow, n)
         x = sampler()                   # fresh N(0, I) noise drawn into the buffer outside the graph, then one replay
         x = sampler(z=z, context=c)     # given noise / context copied in, then one replay
+
+    ``log_prob=True``: the graph also holds the density of the samples (``invert(..., return_log_jac=True)`` and the Gaussian term of
+    ``sample_and_log_prob``: no launch more per dimension), and a replay returns ``(x, log_prob)``, both static buffers.
 
     The returned tensor is the captured output, overwritten by the next call.  Sampling is the most launch-bound thing the package
     does -- per dimension a conditioner-row GEMM chain, a strided copy and a solve launch, d times per block -- and the replay
@@ -121,7 +124,7 @@ class GraphedSampler:
     unless rows overflowed.  The generation numbers of the flag words are constants of the graph, so a replay AFTER one in which
     rows overflowed runs those queued passes without need -- slower, never wrong."""
 
-    def __init__(self, flow, n, context=None, method="newton", warmup=1, **solve_opts):
+    def __init__(self, flow, n, context=None, method="newton", warmup=1, log_prob=False, **solve_opts):
         from . import flow as _flow
         if method not in ("newton", "jacobi"):
             raise ValueError(f"umnn_amd: GraphedSampler records method 'newton' or 'jacobi', not {method!r}")
@@ -140,7 +143,7 @@ class GraphedSampler:
         blk = flow if isinstance(flow, _flow.UMNNMAF) else flow.nets[0]
         dev = blk.scaling.device
         assert dev.type == "cuda", "hipGraph capture needs the model on the device"
-        self.model, self.method, self.opts = flow, method, opts
+        self.model, self.method, self.opts, self.log_prob = flow, method, opts, bool(log_prob)
         self.z = torch.randn(int(n), blk.input_size, device=dev, dtype=torch.float32)
         self.context = context.to(dev).clone() if context is not None else None
         self.warmup = warmup
@@ -152,12 +155,15 @@ class GraphedSampler:
         return tuple(t._version for t in self.model.parameters()) + tuple(t._version for t in self.model.buffers())
 
     def _run(self):
+        from . import integral
         o = self.opts
         if self.method == "newton":
-            return self.model.invert(self.z, context=self.context, method="newton", tol=o["tol"], max_iter=o["max_iter"],
-                                     conditioner=o["conditioner"]), None
+            out = self.model.invert(self.z, context=self.context, method="newton", tol=o["tol"], max_iter=o["max_iter"],
+                                    conditioner=o["conditioner"], return_log_jac=self.log_prob)
+            return ((out[0], integral.sample_ll(self.z, out[1], self.model.pi)) if self.log_prob else out), None
         moves = []
-        x, _ = self.model._invert_jacobi(self.z, self.context, o["tol"], o["max_iter"], 0., int(o["max_sweeps"]), False, moves)
+        out = self.model._invert_jacobi(self.z, self.context, o["tol"], o["max_iter"], 0., int(o["max_sweeps"]), False, moves, self.log_prob)
+        x = (out[0], integral.sample_ll(self.z, out[2], self.model.pi)) if self.log_prob else out[0]
         return x, torch.stack(moves).max()
 
     def _capture(self):
@@ -188,7 +194,8 @@ class GraphedSampler:
         self._capture()
 
     def __call__(self, z=None, context=None):
-        """One replay -> the captured [n, d] samples (overwritten by the next call).  ``z`` None: fresh N(0, I) noise."""
+        """One replay -> the captured [n, d] samples, or (samples, log_prob [n]) with ``log_prob=True`` (overwritten by the next call).
+        ``z`` None: fresh N(0, I) noise."""
         if self._versions() != self._seen:
             self._capture()
         if z is None:

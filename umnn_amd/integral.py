@@ -21,6 +21,7 @@ Two execution paths, chosen per call, never silently:
     need device memory); ``path_taken()`` reports which path the last call used so tests can assert on it.
 """
 import ctypes
+import math
 import os
 import weakref
 import threading
@@ -333,17 +334,27 @@ def _solve_call(fn_name, spec, h, target, nb_steps, x_out, want_info, info_shape
 
 
 def hip_solve(spec, h, target, nb_steps, j=0, scale_row=None, scaling=None, off_row=None, off_h0=False, lo=-50., hi=50., tol=1e-6,
-              max_iter=64, x_out=None, want_info=True):
+              max_iter=64, x_out=None, want_info=True, lj_row=None, lj_first=False):
     """Newton solve of dimension j for every row in ONE launch (umnn_cc_solve), the counterpart of ``hip_invert_dim``:
     scale (off + int_0^x f(t; h[:, :, j]) dt) = target[:, j].  ``target`` [B,d] fp32 contiguous, ``h`` [B,E*d] fp32 contiguous;
     scale = ``scale_row`` [B], else exp(``scaling``[j]), else 1; off = ``off_row`` [B], else embedding row 0 (``off_h0``), else 0.
     Writes ``x_out``[:, j] ([B,d] fp32 contiguous; allocated when None) -> (x_out, f_x [B], status [B] int32), the last two None
-    unless ``want_info``.  Returns None when the library has no kernel for this net: the caller runs ``host_solve``."""
+    unless ``want_info``.  Returns None when the library has no kernel for this net: the caller runs ``host_solve``.
+    ``lj_row`` [B] fp32 contiguous (umnn_cc_solve_lj, the same launch): gets log(f(x) + 1e-10) + s added in place -- s = ``scaling``[j],
+    else log(``scale_row``), else 0 --, or written over whatever it holds when ``lj_first``."""
+    if lj_row is None:
+        return _solve_call(
+            "umnn_cc_solve", spec, h, target, nb_steps, x_out, want_info, target.shape[:1],
+            lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve(
+                desc, _ptr(h), _ptr(target), d, _ptr(scale_row), _ptr(scaling), _ptr(off_row), 1 if off_h0 else 0, w, s, int(nb_steps),
+                B, d, E, int(j), float(lo), float(hi), float(tol), int(max_iter), x, d, fx, status, stream))
+    if lj_row.dtype != torch.float32 or not lj_row.is_contiguous() or lj_row.shape != target.shape[:1] or lj_row.device != target.device:
+        raise ValueError("umnn_amd: hip_solve needs lj_row as a contiguous fp32 [B] tensor on the target's device")
     return _solve_call(
-        "umnn_cc_solve", spec, h, target, nb_steps, x_out, want_info, target.shape[:1],
-        lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve(
+        "umnn_cc_solve_lj", spec, h, target, nb_steps, x_out, want_info, target.shape[:1],
+        lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve_lj(
             desc, _ptr(h), _ptr(target), d, _ptr(scale_row), _ptr(scaling), _ptr(off_row), 1 if off_h0 else 0, w, s, int(nb_steps),
-            B, d, E, int(j), float(lo), float(hi), float(tol), int(max_iter), x, d, fx, status, stream))
+            B, d, E, int(j), float(lo), float(hi), float(tol), int(max_iter), x, d, fx, status, _ptr(lj_row), 1 if lj_first else 0, stream))
 
 
 def hip_solve_block(spec, h, target, nb_steps, scaling=None, off_h0=False, x_init=None, lo=-50., hi=50., tol=1e-6, max_iter=64,
@@ -758,6 +769,46 @@ def hip_flow_ll(z, log_jac):
         rc = _lib.lib().umnn_flow_ll_forward(_ptr(z), _ptr(log_jac), B, d, _ptr(ll), _stream(z.device))
     _lib.check(rc, "umnn_flow_ll_forward")
     return ll
+
+
+def _glue_ok(*tensors):
+    """One launch of a cc_flow_glue kernel serves these tensors: contiguous fp32 on the GPU, outside a recorded graph."""
+    if _graph_mode():       # (first: traced code cannot read the thread-local switch below)
+        return False
+    return (tensors[0].is_cuda and all(t.dtype == torch.float32 and t.is_contiguous() for t in tensors)
+            and not getattr(_state, "force_generic", False))
+
+
+def sample_lj_rows(fx, scaling, lj_row=None):
+    """Row sums of a block's log-Jacobian from the f(x) of its solves: ``lj_row`` [B] += sum_i (log(fx[b,i] + 1e-10) + scaling[i]), or
+    a new tensor when ``lj_row`` is None.  One umnn_flow_sample_lj_rows launch for contiguous fp32 GPU tensors (fixed summation
+    order); the same arithmetic in torch ops, in the tensors' dtype, otherwise.  -> lj_row"""
+    B, d = fx.shape
+    if _glue_ok(fx, scaling) and (lj_row is None or _glue_ok(lj_row)):
+        first = lj_row is None
+        if first:
+            lj_row = torch.empty(B, device=fx.device, dtype=torch.float32)
+        with torch.cuda.device(fx.device):
+            rc = _lib.lib().umnn_flow_sample_lj_rows(_ptr(fx), _ptr(scaling), B, d, 1 if first else 0, _ptr(lj_row), _stream(fx.device))
+        _lib.check(rc, "umnn_flow_sample_lj_rows")
+        return lj_row
+    s = (torch.log(fx + 1e-10) + scaling.to(fx.dtype).unsqueeze(0)).sum(1)
+    return s if lj_row is None else lj_row + s
+
+
+def sample_ll(z, lj_row, pi=None):
+    """Log-density of drawn samples from the noise ``z`` [B,d] they were drawn from and the flow's summed log-Jacobian ``lj_row`` [B]:
+    lj_row - 1/2 sum_i (log 2 pi + z_i^2).  One umnn_flow_sample_ll launch for contiguous fp32 GPU tensors, torch ops otherwise --
+    with the flow's own ``pi`` buffer when given, the constant ``compute_ll`` uses (a float64 flow keeps the fp32-rounded value)."""
+    if _glue_ok(z, lj_row):
+        B, d = z.shape
+        ll = torch.empty(B, device=z.device, dtype=torch.float32)
+        with torch.cuda.device(z.device):
+            rc = _lib.lib().umnn_flow_sample_ll(_ptr(z), _ptr(lj_row), B, d, _ptr(ll), _stream(z.device))
+        _lib.check(rc, "umnn_flow_sample_ll")
+        return ll
+    log_2pi = math.log(2 * math.pi) if pi is None else torch.log(pi.to(z.dtype) * 2)
+    return lj_row - .5 * (log_2pi + z ** 2).sum(1)
 
 
 def hip_flow_ll_backward(z, g_ll, need_z, need_lj):
