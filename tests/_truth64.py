@@ -56,9 +56,9 @@ def backward_reference(net, x0, x, h, g, g_fx, nb_steps, dtype=torch.float64, ch
             if gr is not None:
                 acc += gr
         dhs.append(grads[len(params)])
+        # (inv_f: d_theta and d_h differentiate 1 / f, the Leibniz terms keep f itself -- both branches of the reference's :120-123
+        # are identical, and oracle.integrate_backward and the kernels follow it)
         fxd, fx0d = fx.detach(), netd(x0a, ha).detach()
-        if inv_f:
-            fxd, fx0d = 1.0 / fxd, 1.0 / fx0d
         dxs.append(fxd * ga + (grads[-1] if g_fx is not None else 0))
         dx0s.append(-fx0d * ga)
     return torch.cat(dx0s), torch.cat(dxs), torch.cat(dhs), torch.cat([a.reshape(-1) for a in dth])

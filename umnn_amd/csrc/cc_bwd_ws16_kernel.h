@@ -1157,6 +1157,9 @@ __device__ __forceinline__ void ws16_role_B1p(const BwdBf16Args& args, unsigned 
                 // (the first operand fetch of the step is still in flight behind slot 0: the tail starts at slot 2, a register every
                 // slot and a half)
                 if constexpr (nn >= 2 && nn < 22 && ws_op_of_slot(nn - 2) >= 0) tail_reg(std::integral_constant<int, ws_op_of_slot(nn - 2)>{});
+                // (that schedule places registers 0..13; the all-16-register build takes 14 and 15 in the last two slots -- they fold
+                // away at LIVE = 13, whose instruction stream is unchanged)
+                if constexpr (nn >= 22) tail_reg(std::integral_constant<int, nn - 8>{});
                 __builtin_amdgcn_sched_barrier(0);
             });
         }
