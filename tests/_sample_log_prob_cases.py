@@ -43,3 +43,51 @@ def opts(method, d):
     if o["method"] == "jacobi":
         o["max_sweeps"] = d
     return o
+
+
+def check_one_x(obj, nb_flow, z, ctx, o):
+    """``obj.invert`` (a UMNNMAFFlow of ``nb_flow`` blocks, or a single UMNNMAF: ``nb_flow`` None) returns ONE x whatever else is asked
+    for, in exactly the documented shapes: x, (x, log_jac), and for jacobi (x, info) and (x, info, log_jac) -- info's entries lists over
+    the blocks for a flow, the block's own values for a single block."""
+    B, d = z.shape
+    x = obj.invert(z, context=ctx, **o)
+    assert torch.is_tensor(x) and x.shape == (B, d)
+    out = obj.invert(z, context=ctx, return_log_jac=True, **o)
+    assert type(out) is tuple and len(out) == 2 and torch.equal(out[0], x)
+    assert torch.is_tensor(out[1]) and out[1].shape == (B,)
+    if o["method"] != "jacobi":
+        return
+    with_info = obj.invert(z, context=ctx, return_info=True, **o)
+    both = obj.invert(z, context=ctx, return_info=True, return_log_jac=True, **o)
+    assert type(with_info) is tuple and len(with_info) == 2 and type(both) is tuple and len(both) == 3
+    assert torch.equal(with_info[0], x) and torch.equal(both[0], x) and torch.equal(both[2], out[1])
+    for info in (with_info[1], both[1]):
+        assert type(info) is dict and list(info) == ["sweeps", "converged", "status", "max_evals"]
+        per_block = list(zip(*(info[k] for k in info))) if nb_flow is not None else [tuple(info.values())]
+        if nb_flow is not None:
+            assert all(type(v) is list and len(v) == nb_flow for v in info.values())
+        for sweeps, converged, status, max_evals in per_block:
+            assert type(sweeps) is int and sweeps == o["max_sweeps"] and type(converged) is bool
+            assert torch.is_tensor(status) and status.shape == (B, d) and status.dtype == torch.int32
+            assert type(max_evals) is list and len(max_evals) == sweeps and all(type(e) is int for e in max_evals)
+
+
+def composed(m, z, ctx, o):
+    """The flow's ``invert(..., return_log_jac=True)`` by hand from the blocks' public ``invert`` -> (x, sum of the blocks' log_jac)."""
+    z, lj = torch.flip(z, [1]), 0.
+    for i in reversed(range(len(m.nets))):
+        z, lj_blk = m.nets[i].invert(torch.flip(z, [1]), context=ctx, return_log_jac=True, **o)
+        lj = lj + lj_blk
+    return z, lj
+
+
+def lj_magnitude(truth, x, ctx):
+    """sum over blocks and dimensions of |log_jac| at x [B], from the float64 CPU flow ``truth``: what the rounding of a sum of these terms
+    is relative to, in whatever order they are added."""
+    xi, total = x.detach().cpu().double(), 0.
+    with torch.no_grad():
+        for blk in truth.nets:
+            zz, lj = blk._transform(xi, ctx, want_jac=True)
+            total = total + lj.abs().sum(1)
+            xi = torch.flip(zz, [1])
+    return total

@@ -8,6 +8,7 @@ the fast log's last bits and the fp32 running sum differ: 1e-5 d.  Flow level: a
 is held to the same bar in the same test.  Measured maxima: EXPERIMENTS.md ("Sample with log-density")."""
 import copy
 import ctypes
+import warnings
 
 import pytest
 import torch
@@ -288,6 +289,77 @@ def test_nan_noise_poisons_the_density_of_its_own_sample_only(method):
     keep[2] = False
     assert torch.isnan(ljb[2]) and torch.isnan(xb[2]).any()
     assert torch.equal(xb[keep], x[keep]) and torch.equal(ljb[keep], lj[keep]), "the rows of a batch are independent"
+
+
+ROWS = 17       # one full 16-row tile plus one row
+
+
+def _rows(name):
+    """``_gpu_flow(name)`` with ROWS rows of noise (and context) in place of the shared six."""
+    m, z, ctx, truth = _gpu_flow(name)
+    g = torch.Generator().manual_seed(17)
+    z = torch.randn(ROWS, z.shape[1], generator=g).to(DEV)
+    return m, z, None if ctx is None else torch.randn(ROWS, ctx.shape[1], generator=g).to(DEV), truth
+
+
+@pytest.mark.parametrize("method", list(GPU_METHODS))
+@pytest.mark.parametrize("name", ["f1-d3", "f3-d3", "cond"])
+def test_one_x_whatever_is_asked_for(name, method):
+    m, z, ctx, _ = _rows(name)
+    o = _opts(method, z.shape[1])
+    C.check_one_x(m, len(m.nets), z, ctx, o)
+    C.check_one_x(m.nets[0], None, z, ctx, o)
+    assert umnn_amd.path_taken() == "hip"
+
+
+@pytest.mark.parametrize("method", list(GPU_METHODS))
+@pytest.mark.parametrize("name", ["f2-d3", "f3-d5", "cond"])
+def test_flow_invert_is_the_block_inverts_composed(name, method):
+    """x is the blocks' x bit for bit; log_jac is the same fp32 terms added in another order ("newton": the solve launches of every block
+    add into one running sum; the composition adds per-block sums).  Two orders of adding n = nb_flow d terms differ by at most
+    2 (n - 1) eps sum |terms| (each order is within (n - 1) eps sum |terms| of the exact sum), eps = 1.2e-7 and sum |terms| from the
+    float64 CPU flow's ``_transform`` at x: 1.2e-6 to 3.3e-6 of sum |terms| for these flows.  Measured: 3.8e-8 to 6.7e-8 of sum |terms| ("newton", both conditioners), 0 ("jacobi", "bracket")."""
+    m, z, ctx, truth = _rows(name)
+    o = _opts(method, z.shape[1])
+    with torch.no_grad():
+        x, lj = m.invert(z, context=ctx, return_log_jac=True, **o)
+        xc, ljc = C.composed(m, z, ctx, o)
+    assert torch.equal(xc, x) and umnn_amd.path_taken() == "hip"
+    n = len(m.nets) * z.shape[1]
+    mag = C.lj_magnitude(truth, x, None if ctx is None else ctx.double().cpu())
+    err = ((lj - ljc).abs().double().cpu() / mag).max()
+    print(f"{name} {method}: |lj - composed| / sum |terms| {float(err):.2e} (bound {2 * (n - 1) * torch.finfo(torch.float32).eps:.1e})")
+    assert lj.dtype == ljc.dtype == torch.float32 and float(err) <= 2 * (n - 1) * torch.finfo(torch.float32).eps
+
+
+def test_mid_walk_fallback_keeps_its_density():
+    """An integrand with a single hidden layer: the solve kernels refuse it (UMNN_EUNSUPPORTED at the first dimension of each block), the
+    rest of the block runs the Newton iteration from the host on ``hip_forward`` and the running log_jac goes on in torch ops."""
+    torch.manual_seed(9)
+    d = 3
+    m = umnn_amd.UMNNMAFFlow(nb_flow=2, nb_in=d, hidden_derivative=[50], hidden_embedding=[16, 16], embedding_s=3, nb_steps=20,
+                             solver="CCParallel").eval()
+    with torch.no_grad():
+        for blk in m.nets:
+            blk.scaling.copy_(0.3 * torch.randn(d))
+    for p in m.parameters():
+        p.requires_grad_(False)
+    truth = copy.deepcopy(m).double()
+    m = m.to(DEV)
+    z = torch.randn(ROWS, d).to(DEV)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore", RuntimeWarning)          # (the refusal is announced once)
+        x0 = m.invert(z, method="newton")
+        before = _lib.lib().umnn_launch_count()
+        x, lj = m.invert(z, method="newton", return_log_jac=True)
+        launches = _lib.lib().umnn_launch_count() - before
+    assert umnn_amd.path_taken() == "hip" and torch.equal(x, x0)
+    assert launches > len(m.nets) * d, "the host-driven loop launches one quadrature per iteration"
+    with torch.no_grad():
+        ref = truth.compute_log_jac(x.double().cpu()).sum(1)
+    err = _rel(lj, ref)
+    print(f"fallback: {launches} launches, log_jac against the float64 CPU flow {err:.2e}")
+    assert lj.shape == (ROWS,) and lj.dtype == torch.float32 and err <= TOL
 
 
 # ------------------------------------------------------------------------------------------------------------ 4. launch counts

@@ -295,12 +295,12 @@ def test_default_method_is_the_untouched_bracket_search():
     G, m = _g6()
     z = torch.from_numpy(G["z"])
     with torch.no_grad():
-        ref = m._invert(z, 5, None)
+        ref = umnn_amd.sampling.run(list(m.nets), True, z, None, umnn_amd.sampling.Options(iter=5)).x
         assert torch.equal(m.invert(z, iter=5), ref)
         assert torch.equal(m.invert(z, 5, None), ref)
         assert torch.equal(m.invert(z, iter=5, method="bracket"), ref)
         blk = m.nets[1]
-        assert torch.equal(blk.invert(z, iter=4), blk._invert(z, 4, None))
+        assert torch.equal(blk.invert(z, iter=4), umnn_amd.sampling.invert_bracket(blk, z, None, umnn_amd.sampling.Options(iter=4)).x)
     with pytest.raises(ValueError, match="unknown inversion method"):
         m.invert(z, method="secant")
     with pytest.raises(ValueError, match="unknown inversion method"):

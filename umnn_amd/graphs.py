@@ -125,7 +125,7 @@ class GraphedSampler:
     rows overflowed runs those queued passes without need -- slower, never wrong."""
 
     def __init__(self, flow, n, context=None, method="newton", warmup=1, log_prob=False, **solve_opts):
-        from . import flow as _flow
+        from . import flow as _flow, sampling
         if method not in ("newton", "jacobi"):
             raise ValueError(f"umnn_amd: GraphedSampler records method 'newton' or 'jacobi', not {method!r}")
         opts = dict(tol=1e-6, max_iter=64)
@@ -140,10 +140,15 @@ class GraphedSampler:
         if method == "jacobi" and (opts["sweep_tol"] != 0 or opts["max_sweeps"] is None or int(opts["max_sweeps"]) < 1):
             raise ValueError("umnn_amd: GraphedSampler(method='jacobi') needs sweep_tol=0 and max_sweeps=K >= 1 (a fixed sweep count; "
                              "check sampler.last_move afterwards)")
-        blk = flow if isinstance(flow, _flow.UMNNMAF) else flow.nets[0]
+        self.stacked = not isinstance(flow, _flow.UMNNMAF)
+        self.blocks = [flow.nets[i] for i in range(len(flow.nets))] if self.stacked else [flow]
+        blk = self.blocks[0]
         dev = blk.scaling.device
         assert dev.type == "cuda", "hipGraph capture needs the model on the device"
         self.model, self.method, self.opts, self.log_prob = flow, method, opts, bool(log_prob)
+        # (jacobi: the fixed sweep count checked above, and the last sweep's move as a device tensor -- no host read)
+        self.solve = sampling.Options(method=method, want_lj=self.log_prob, want_move=method == "jacobi", **opts)
+        sampling.check(self.solve, type(flow).__name__)
         self.z = torch.randn(int(n), blk.input_size, device=dev, dtype=torch.float32)
         self.context = context.to(dev).clone() if context is not None else None
         self.warmup = warmup
@@ -155,16 +160,10 @@ class GraphedSampler:
         return tuple(t._version for t in self.model.parameters()) + tuple(t._version for t in self.model.buffers())
 
     def _run(self):
-        from . import integral
-        o = self.opts
-        if self.method == "newton":
-            out = self.model.invert(self.z, context=self.context, method="newton", tol=o["tol"], max_iter=o["max_iter"],
-                                    conditioner=o["conditioner"], return_log_jac=self.log_prob)
-            return ((out[0], integral.sample_ll(self.z, out[1], self.model.pi)) if self.log_prob else out), None
-        moves = []
-        out = self.model._invert_jacobi(self.z, self.context, o["tol"], o["max_iter"], 0., int(o["max_sweeps"]), False, moves, self.log_prob)
-        x = (out[0], integral.sample_ll(self.z, out[2], self.model.pi)) if self.log_prob else out[0]
-        return x, torch.stack(moves).max()
+        from . import integral, sampling
+        out = sampling.run(self.blocks, self.stacked, self.z, self.context, self.solve)
+        x = (out.x, integral.sample_ll(self.z, out.lj, self.model.pi)) if self.log_prob else out.x
+        return x, (torch.stack(out.move).max() if self.method == "jacobi" else None)
 
     def _capture(self):
         from . import integral, made

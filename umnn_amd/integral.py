@@ -428,23 +428,29 @@ def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=None
     return x, fx, evals | flags
 
 
+def quadrature_eval(spec, integrand, h, nb_steps, use_hip, column=False):
+    """``eval_fn(x) -> (F(x), f(x))`` for ``newton_solve``, F = int_0^x f(t; h) dt, whenever the iteration is driven from the host:
+    ``use_hip`` one ``hip_forward`` launch per call (F and f_x together), else the ATen quadrature and one pass of the integrand.
+    ``h`` is used as given (the caller brings it to x's dtype for the ATen form).  ``column``: x is the [B,1] column of one flow
+    dimension and ``h`` its [B,E] embedding rows, which the ATen form evaluates through ``integrand.independant_forward``."""
+    if use_hip:
+        return lambda x: hip_forward(spec, None, x, h, nb_steps)[:2]
+    f = (lambda x, hh: integrand.independant_forward(torch.cat((x, hh), 1))) if column else integrand
+    return lambda x: (aten_forward(f, torch.zeros_like(x), x, h, nb_steps), f(x, h))
+
+
 def host_solve(spec, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0., x_init=None):
     """Host-driven Newton loop over ``hip_forward`` (F and f_x in one launch per iteration): what runs when the library
     answers UMNN_EUNSUPPORTED for the in-kernel solve.  ``target`` [B,d], ``h`` [B,E*d] -> (x, f_x, status), each [B,d]."""
-    def eval_fn(x):
-        F, fx, _ = hip_forward(spec, None, x, h, nb_steps)
-        return F, fx
     with torch.no_grad():
-        return newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=x_init)
+        return newton_solve(quadrature_eval(spec, None, h, nb_steps, True), target, scale, off, lo, hi, tol, max_iter, x_init=x_init)
 
 
 def aten_solve(integrand, h, target, nb_steps, lo, hi, tol, max_iter, scale=1., off=0., x_init=None):
     """Generic ATen path of the inverse (CPU tensors, float64, integrands ``mlp_spec`` does not recognise): the same
     algorithm on ``aten_forward``."""
-    def eval_fn(x):
-        return aten_forward(integrand, torch.zeros_like(x), x, h, nb_steps), integrand(x, h)
     with torch.no_grad():
-        out = newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=x_init)
+        out = newton_solve(quadrature_eval(None, integrand, h, nb_steps, False), target, scale, off, lo, hi, tol, max_iter, x_init=x_init)
     _state.path = "aten"
     return out
 
@@ -1007,6 +1013,9 @@ class NeuralIntegral(torch.autograd.Function):
         nig = ctx.needs_input_grad
         dx0, dx, dh, dtheta = _quad_backward(ctx, grad_output, None, (nig[0], nig[1], nig[4], nig[3]))
         return dx0, dx, None, dtheta, dh, None
+
+
+SOLVERS = {"CC": NeuralIntegral, "CCParallel": ParallelNeuralIntegral}     # the ``solver`` names of a flow block that integrate
 
 
 class IntegralWithJacobian(torch.autograd.Function):

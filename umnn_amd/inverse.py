@@ -24,6 +24,7 @@ from torch.autograd.function import once_differentiable
 from torch.func import functional_call
 
 from . import integral as _I
+from .sampling import Inverted, walk_blocks
 
 METHODS = ("newton", "jacobi")
 
@@ -131,13 +132,11 @@ class FlowBlockInverse(torch.autograd.Function):
 def _inverse(blocks, stacked, z, context, opts, return_info):
     nb = len(blocks)
     info = {"method": opts["method"], "solve": [None] * nb, "adjoint": [None] * nb}
-    if stacked:                      # (the flips of UMNNMAFFlow._invert_newton, as ordinary differentiable ops)
-        z = torch.flip(z, [1])
-    for i in range(nb - 1, -1, -1):
-        if stacked:
-            z = torch.flip(z, [1])
-        z = FlowBlockInverse.apply(z, context, blocks[i], opts, (info, i), *blocks[i].parameters())
-    return (z, info) if return_info else z
+    def step(numbered, z, lj):
+        i, block = numbered
+        return Inverted(FlowBlockInverse.apply(z, context, block, opts, (info, i), *block.parameters()))
+    x = walk_blocks(list(enumerate(blocks)), stacked, z, step).x       # (the walk of ``invert``; its flips are differentiable ops here)
+    return (x, info) if return_info else x
 
 
 def inverse(blocks, stacked, who, z, context=None, method="newton", tol=1e-6, max_iter=64, sweep_tol=1e-6, max_sweeps=None,
