@@ -402,7 +402,8 @@ int umnn_get_backward_precision(void);
 
 /* Launch options.  The UMNN_* environment variables are read once per process -- at first use or on
  * umnn_reload_env() -- and live in atomics afterwards, so the launch path never calls getenv.  Names:
- * "fwd_precision", "bwd_precision" (UMNN_PRECISION_*), "fwd_p" (1|2), "fwd_ns" (1|2|4), "fwd_tail" (0|1), "fwd_pipe"
+ * "fwd_precision", "bwd_precision" (UMNN_PRECISION_*), "fwd_p" (1|2), "fwd_ns" (1|2|4; a split into more parts than
+ * the nb_steps + 1 nodes runs whole, as the automatic rule does), "fwd_tail" (0|1), "fwd_pipe"
  * (0 plain loop | 1 pipelined 16x16x32 loop, default | 2 the 32x32x16 formulation of the 48..51-wide shapes),
  * "fwd_pad", "fwd_pad_min", "bwd_ns" (1..32), "bwd_swp" (1: software-pipelined one-pass bf16 backward, default; 0: the
  * round-2 node loop), "bwd_ws" (1, default: four-hidden-layer nets at large batch take the weight-stationary workgroup

@@ -5,11 +5,14 @@ call really notes) and tools/path_identity.py (bit-identity of two checkouts).
 
 The expectations were derived by hand from the launchers as they stood BEFORE the plan existed (launch_forward in cc_forward.hip,
 umnn_launch_forward_bf16 / _f16 in cc_forward_bf16.hip, umnn_launch_forward_p32, inv_launch and inv_mode in cc_inv_launch.h), for a
-device of 256 CUs (MI355X; also what the library assumes without a device):
+device of 256 CUs (MI355X; also what the library assumes without a device) -- with one rule that is newer than those launchers: a
+forced fwd_ns above n + 1 runs the node range whole, like an automatic one (the launchers took it as given, and part 0 of such a
+split, whose wave publishes f(x), holds no node; tests/_fwd_coverage_cases.py has the cases):
   * forward: tiles = ceil(B d / 16); P = 2 from 8192 tiles (8 per SIMD); below 2048 tiles the node range is split, ns = 4 up to 1024
-    tiles, else 2; ns > n + 1 -> 1; fwd_p / fwd_ns override.  f16x3: the fp16 build (two pieces, bf16 build queued behind it) unless
-    the marker output aliases an input (bf16 build, two pieces); bf16x3: two bf16 pieces; bf16x6: three.  What a build does not serve
-    goes on to three bf16 pieces, then to fp32 MFMA; a single hidden layer and fwd_precision = fp32 are fp32 MFMA at once.
+    tiles, else 2; fwd_p / fwd_ns override; ns > n + 1 -> 1, forced or not.  f16x3: the fp16 build (two pieces, bf16 build queued
+    behind it) unless the marker output aliases an input (bf16 build, two pieces); bf16x3: two bf16 pieces; bf16x6: three.  What a
+    build does not serve goes on to three bf16 pieces, then to fp32 MFMA; a single hidden layer and fwd_precision = fp32 are fp32 MFMA
+    at once.
   * on a build: every hidden layer of the same 5..8 tiles (two pieces only): P = 1 unless fwd_p forces 2, ns = 4 up to 512 tiles, 2
     up to 1024; eight waves per workgroup when two workgroups of images (+ 1 KiB each) exceed 160 KiB.  First hidden layer of 5..8
     tiles over layers of <= 4 (two pieces, P = 1): the wide-first kernels, the same ns rule, LIVE=13 when layers 2..L are 48..51 wide.

@@ -421,7 +421,9 @@ inline FwdPlan fwd_plan(const MlpDev& m0, int tmax, int ksu, const FwdCall& c, c
     int P = tiles16 >= 8 * simd_slots ? 2 : 1;
     int ns = fwd_split(tiles16, simd_slots, 2 * simd_slots - 1, c.n);
     if (o.fwd_p > 0) P = o.fwd_p;
-    if (o.fwd_ns > 0) ns = o.fwd_ns;
+    // (a forced split obeys the same limit as the rule: part 0 of a range cut into more parts than nodes is empty, and the wave
+    // that owns part 0 is the one that publishes f(x))
+    if (o.fwd_ns > 0) ns = o.fwd_ns > c.n + 1 ? 1 : o.fwd_ns;
     const int prec = o.fwd_precision;
     if (c.z2 && (prec == UMNN_PRECISION_FP32 || prec == UMNN_PRECISION_BF16X6)) {
         fwd_plan_fail(pl, "forward (z_2 saved): two-piece arithmetic modes only");
