@@ -181,7 +181,7 @@ def test_hidden_stack_kernel_feeding_the_library_gemm_of_a_wide_output_layer(dev
     output layer's library GEMM (umnn_made_mlp_forward_ex, out_mode 2): two launches per block, same numbers as the per-layer path."""
     import umnn_amd
     from umnn_amd import MADE, ConditionnalMADE, _lib
-    from umnn_amd.made import MaskedLinear, _fused_ok
+    from umnn_amd.made import MaskedLinear
     torch.manual_seed(4 + cond)
     nin, E, B = 63, 30, 777
     if cond:

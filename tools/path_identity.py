@@ -11,8 +11,11 @@ output and gradient tensor, ``path_taken()``, ``backward_path_taken()``, ``umnn_
 backward's main pass (``umnn_last_kernel_name_of(PROF_BACKWARD)``) and the ``umnn_launch_count()`` delta.  The list ends with the
 GPU cases of tests/_bwd_plan_cases.py (one ``integral.hip_backward`` call per kernel family and option of the backward's launch plan)
 and of tests/_fwd_plan_cases.py (forward, flow block, ll block, bracket search and Newton solves per family and rule of the forward's;
-``invert`` bracket / newton / jacobi are further up).  A case that raises is recorded by its exception type.  ``compare`` wants ``torch.equal`` on every
-tensor and equality of every string and count; it prints (and writes to REPORT) the number of tensors, the number of mismatches and
+``invert`` bracket / newton / jacobi are further up) and with the conditioner's cases: one ``raw`` call per route of ``MADE`` and
+``ConditionnalMADE`` with fp32 and bf16 output, ``raw_rows``, a training step through the one-node chain, the progressive conditioner
+of ``invert`` and a ``GraphedLL`` capture with replays; for every case also the conditioner's launch count delta
+(``umnn_made_launch_count()``) and last kernel (``umnn_last_made_kernel_name()``).  A case that raises is recorded by its exception
+type.  ``compare`` wants ``torch.equal`` on every tensor and equality of every string and count; it prints (and writes to REPORT) the number of tensors, the number of mismatches and
 the kernel names seen, and exits non-zero on any mismatch.  Only the public API is used, so the file runs in older checkouts too (with tests/_bwd_plan_cases.py and tests/_fwd_plan_cases.py copied along)."""
 import os
 import sys
@@ -220,6 +223,82 @@ def _plan_block_case(ll):
     return make
 
 
+def _restore_made_switches():
+    """The conditioner's switches as this process started with them: what its environment says (only setters exist in every checkout)."""
+    import umnn_amd
+    env = os.environ.get
+    umnn_amd.set_made_fast_path(env("UMNN_MADE_BF16X3", "1") != "0")
+    umnn_amd.set_made_fused(env("UMNN_MADE_FUSED", "1") != "0", max_rows=int(env("UMNN_MADE_FUSED_MAX_ROWS", "32768")),
+                            wide_out=env("UMNN_MADE_FUSED_WIDE_OUT", "0") == "1", hybrid=env("UMNN_MADE_FUSED_HYBRID", "0") == "1",
+                            layered=env("UMNN_MADE_LAYERED", "1") != "0")
+
+
+def _conditioner(cond, bf16, rows=B, hidden=(37,), E=30, fast=True, fused=True, call="raw", **fused_kw):
+    """One conditioner call (``MADE.raw`` / ``ConditionnalMADE.raw`` / ``raw_rows`` / a training step through ``raw``) under the given
+    switches: with E = 30 the output is 600 columns wide (the routes of wide outputs), with E = 3 it is 60 (the one-launch kernel)."""
+    def make(dev):
+        import umnn_amd
+        torch.manual_seed(20)
+        nin, c = 20, 12
+        if cond:
+            net = umnn_amd.ConditionnalMADE(nin, c, list(hidden), (nin + c) * E, num_masks=1, natural_ordering=True).to(dev)
+        else:
+            net = umnn_amd.MADE(nin, list(hidden), nin * E, num_masks=1, natural_ordering=True).to(dev)
+        args = (_x(dev, nin, seed=21, rows=rows),) + ((_x(dev, c, seed=22, rows=rows),) if cond else ())
+        if call == "train":
+            args = tuple(a.requires_grad_() for a in args)
+        sel = torch.arange(7, nin * E, nin, device=dev)
+
+        def fn(*args):
+            try:
+                umnn_amd.set_made_fast_path(fast)
+                umnn_amd.set_made_fused(fused, **fused_kw)
+                if call == "train":
+                    return net.raw(*args)
+                with torch.no_grad():
+                    return net.raw_rows(args[0], sel) if call == "raw_rows" else net.raw(*args, out_dtype=torch.bfloat16 if bf16 else None)
+            finally:
+                _restore_made_switches()
+        after = (lambda m, out, ts: _grads(m, (out * out).sum(), *ts)) if call == "train" else None
+        return net, fn, args, after
+    return make
+
+
+def _conditioner_cases():
+    routes = [("fast path off (F.linear chain)", dict(fast=False)), ("fused off (split + GEMM)", dict(fused=False)),
+              ("narrow (one launch)", dict(E=3)), ("wide_out (one launch)", dict(wide_out=True)),
+              ("hybrid (hidden stack + GEMM)", dict(hidden=(37, 37), hybrid=True)), ("layered (one launch per layer)", dict()),
+              ("layered, 4097 rows (output layer on the library)", dict(rows=4097)), ("layered off (split + GEMM)", dict(layered=False)),
+              ("max_rows 16 (split + GEMM)", dict(E=3, max_rows=16)), ("513-wide hidden layer (split + GEMM)", dict(hidden=(513, 16)))]
+    cases = [(f"conditioner {'ConditionnalMADE' if cond else 'MADE'} {'bf16' if bf16 else 'fp32'}: {name}", EAGER, _conditioner(cond, bf16, **kw))
+             for name, kw in routes for cond in (False, True) for bf16 in (False, True)]
+    cases.append(("conditioner MADE.raw_rows (4200-row output layer)", EAGER, _conditioner(False, False, E=210, call="raw_rows")))
+    cases += [(f"conditioner {'ConditionnalMADE' if cond else 'MADE'}: training step through the one-node chain", EAGER,
+               _conditioner(cond, False, call="train")) for cond in (False, True)]
+    return cases
+
+
+def _progressive_invert(cond):
+    def make(dev):
+        flow = _flow(dev, cond_in=2 if cond else 0)
+        z = _x(dev, 3, seed=13, scale=1.0)
+        ctx = _x(dev, 2, seed=14) if cond else None
+        return flow, (lambda z: flow.invert(z, context=ctx, method="newton", conditioner="progressive")), (z,), None
+    return make
+
+
+def _graphed_ll(dev):
+    import umnn_amd
+    flow = _flow(dev)
+    xs = _x(dev, 3)
+
+    def fn(xs):
+        graphed = umnn_amd.GraphedLL(flow, xs)
+        first = [t.clone() for t in graphed(xs)]
+        return first + [t.clone() for t in graphed(xs * 0.5)]
+    return flow, fn, (xs,), None
+
+
 EAGER, COMPILED, INDUCTOR = ("eager",), ("eager", "aot_eager"), ("eager", "aot_eager", "inductor")
 WIDE_FIRST = dict(d=8, E=10, hidden=(100, 50, 50, 50, 50))           # the z_2 hand-off from the training forward to the backward
 DEEP_WIDE = dict(d=2, E=4, hidden=(100, 72, 80, 96, 70), n=10)       # no shape-exact HIP backward: the ATen backward
@@ -246,7 +325,11 @@ CASES = [
 ] + [(f"flow.invert {method}{', context' if cond else ' (raw_rows)'}", COMPILED, _invert(method, cond))
      for method in ("bracket", "newton", "jacobi") for cond in (False, True)] + _backward_plan_cases() + [
     ("forward plan: flow block", EAGER, _plan_block_case(False)), ("forward plan: ll block", EAGER, _plan_block_case(True)),
-] + _forward_plan_cases()
+] + _forward_plan_cases() + _conditioner_cases() + [
+    ("flow.invert newton, progressive conditioner", EAGER, _progressive_invert(False)),
+    ("flow.invert newton, progressive conditioner, context", EAGER, _progressive_invert(True)),
+    ("GraphedLL capture and two replays", EAGER, _graphed_ll),
+]
 
 
 def _flat(out):
@@ -285,7 +368,7 @@ def run(out_path):
                 if backend != "eager":
                     fn = torch.compile(fn, backend=backend)
                 torch.cuda.synchronize()
-                n0 = lib.umnn_launch_count()
+                n0, m0 = lib.umnn_launch_count(), lib.umnn_made_launch_count()
                 out = fn(*tensors)
                 outs = _flat(out)
                 more = _flat(after(model, out, tensors)) if after is not None else []
@@ -295,11 +378,12 @@ def run(out_path):
                 rec["path"], rec["backward_path"] = umnn_amd.path_taken(), umnn_amd.backward_path_taken()
                 rec["kernel"] = lib.umnn_last_kernel_name().decode()
                 rec["bwd_kernel"] = lib.umnn_last_kernel_name_of(_lib.PROF_BACKWARD).decode()
+                rec["made_launches"], rec["made_kernel"] = int(lib.umnn_made_launch_count() - m0), lib.umnn_last_made_kernel_name().decode()
             except Exception as e:      # noqa: BLE001  (recorded: both checkouts must fail alike)
                 rec["error"] = type(e).__name__
             records.append(rec)
             print(f"{name} [{backend}]: {len(rec['tensors'])} tensors, {rec.get('launches')} launches, {rec.get('path')} / "
-                  f"{rec.get('backward_path')}, {rec.get('kernel')}, {rec.get('bwd_kernel')}{', ' + rec['error'] if rec['error'] else ''}", flush=True)
+                  f"{rec.get('backward_path')}, {rec.get('kernel')}, {rec.get('bwd_kernel')}, conditioner {rec.get('made_launches')} x {rec.get('made_kernel')}{', ' + rec['error'] if rec['error'] else ''}", flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
     torch.save(records, out_path)
 
@@ -312,7 +396,7 @@ def compare(a_path, b_path, report=None):
         bad += 1
     for ra, rb in zip(a, b):
         where = f"{ra['case']} [{ra['backend']}]"
-        for key in ("error", "launches", "path", "backward_path", "kernel", "bwd_kernel"):
+        for key in ("error", "launches", "path", "backward_path", "kernel", "bwd_kernel", "made_launches", "made_kernel"):
             if ra.get(key) != rb.get(key):
                 bad += 1
                 lines.append(f"MISMATCH {where}: {key} {ra.get(key)!r} != {rb.get(key)!r}")
@@ -327,7 +411,7 @@ def compare(a_path, b_path, report=None):
             if not same:
                 bad += 1
                 lines.append(f"MISMATCH {where}: tensor {i} {tuple(ta.shape)} {ta.dtype} vs {tuple(tb.shape)} {tb.dtype}")
-        kernels.update(k for k in (ra.get("kernel"), ra.get("bwd_kernel")) if k)
+        kernels.update(k for k in (ra.get("kernel"), ra.get("bwd_kernel"), ra.get("made_kernel")) if k)
         if ra["error"]:
             lines.append(f"note {where}: both raised {ra['error']}" if ra["error"] == rb["error"] else "")
     head = [f"cases x backends: {len(a)}", f"tensors compared: {tensors}", f"mismatches: {bad}", "kernel names seen:"]

@@ -12,8 +12,13 @@ pieces): the fp32 hipBLASLt GEMM of the BSDS300 output layer takes 168 us, this 
 range.  The left operand is built by the HIP kernel ``umnn_made_split3`` (csrc/made_split.hip) straight from the
 previous layer's raw output (ReLU fused); the packed weights are cached like the masked weight.  Training (autograd on)
 keeps the fp32 ``F.linear`` chain.
+
+How a call is routed is decided in one place, ``conditioner_route`` (the table is in DESIGN.md, "Conditioner routes"), executed by
+``_run_route``; what may be cached is decided in one place, ``MaskedLinear._cached``; the switches are one record, ``_OPTIONS``.
 """
+import collections
 import ctypes
+import dataclasses
 import math
 import os
 import threading
@@ -47,32 +52,20 @@ class MaskedLinear(nn.Linear):
     def __init__(self, in_features, out_features, bias=True):
         super().__init__(in_features, out_features, bias)
         self.register_buffer('mask', torch.ones(out_features, in_features))
-        self._cache = None      # (weight version, weight data_ptr, masked weight)
-        self._packed = None     # (key, bf16 [Wh|Wh|Wl|bh|bl] operand)
-        self._frags = None      # (key, (bf16 MFMA fragments, fp32 bias)) for the fused conditioner kernel
+        self._slots = {}        # slot -> (key, value) of _cached: "masked", "packed", "frags"; on a MADE's first layer also its "plan"
         self._epoch = 0         # bumped by set_mask / invalidate_caches: part of the key of MADE.progressive_plan
 
     def set_mask(self, mask):
         # mask arrives [in, out] (numpy, bool); stored [out, in] like the weight
         self.mask.data.copy_(torch.from_numpy(np.ascontiguousarray(mask.T).astype(np.float32)))
-        self._cache = None
-        self._packed = None
-        self._frags = None
-        self._epoch += 1
+        self.invalidate_caches()
 
     def invalidate_caches(self):
         """Drop the cached masked / packed weights.  The caches are keyed on tensor versions; writes through ``.data``
         (or any other route that does not bump ``_version``) are invisible to that key, so code doing such writes must
         call this (``umnn_amd.invalidate_caches(model)`` does it for a whole model)."""
-        self._cache = None
-        self._packed = None
-        self._frags = None
+        self._slots = {}
         self._epoch += 1
-
-    @staticmethod
-    def _capturing(t):
-        # a capture that tracks the weights' versions itself (graphs.GraphedLL re-captures when they move) may bake the caches in
-        return t.is_cuda and not getattr(_capture_state, "cache_ok", False) and torch.cuda.is_current_stream_capturing()
 
     @staticmethod
     def _may_store(t):
@@ -82,60 +75,61 @@ class MaskedLinear(nn.Linear):
         run BEFORE it records; a miss inside the capture is then recomputed inside the graph, which is merely slower.)"""
         return not (t.is_cuda and torch.cuda.is_current_stream_capturing())
 
+    def _cached(self, slot, key, build):
+        """The one cache rule: ``build()`` under ``slot`` while ``key`` (tensor versions and pointers) is unchanged.
+          * a hit on an equal key returns the stored object;
+          * inside a hipGraph capture the value must be part of the graph -- a cached tensor would be baked in as a constant and
+            replays after an optimizer step would read stale conditioner weights -- so it is built and not looked up, unless the
+            capture tracks the weights' versions itself (``capture_may_cache``: graphs.GraphedLL re-captures when they move);
+          * nothing built while a stream is capturing is ever stored (``_may_store``)."""
+        may_store = self._may_store(self.weight)
+        if may_store or getattr(_capture_state, "cache_ok", False):
+            hit = self._slots.get(slot)
+            if hit is not None and hit[0] == key:
+                return hit[1]
+        value = build()
+        if may_store:
+            self._slots[slot] = (key, value)
+        return value
+
+    def _weight_key(self):
+        return (self.weight._version, self.weight.data_ptr(), self.mask._version, self.mask.data_ptr())
+
+    def _key(self, rows=None):
+        return self._weight_key() + (self.bias._version, self.bias.data_ptr(), None if rows is None else rows.data_ptr())
+
+    def _masked(self, rows):
+        """(mask * weight, bias), or their ``rows`` only."""
+        W, b = self.mask * self.weight, self.bias
+        return (W, b) if rows is None else (W.index_select(0, rows), b.index_select(0, rows))
+
     def masked_weight(self):
         if torch.is_grad_enabled() and self.weight.requires_grad:
             return self.mask * self.weight
-        if self._capturing(self.weight):
-            # inside a hipGraph capture the product must be part of the graph: a cached tensor would be baked in as
-            # a constant and replays after an optimizer step would read stale conditioner weights
-            return (self.mask * self.weight).detach()
-        key = (self.weight._version, self.weight.data_ptr(), self.mask._version, self.mask.data_ptr())
-        if self._cache is None or self._cache[0] != key:
-            w = (self.mask * self.weight).detach()
-            if not self._may_store(self.weight):
-                return w
-            self._cache = (key, w)
-        return self._cache[1]
+        return self._cached("masked", self._weight_key(), lambda: (self.mask * self.weight).detach())
 
     def packed_bf16(self, rows=None):
         """[Wh | Wh | Wl | bh | bl | 0-pad] as bf16 [N, pad8(3K+2)] for the K-concatenated bf16 GEMM (cached while
         weight, mask and bias are unchanged).  ``rows``: optional output-row selection (ConditionnalMADE)."""
-        key = (self.weight._version, self.weight.data_ptr(), self.mask._version, self.mask.data_ptr(),
-               self.bias._version, self.bias.data_ptr(), None if rows is None else rows.data_ptr())
-        capturing = self._capturing(self.weight)        # see masked_weight: recompute inside the graph, never cache
-        if capturing or self._packed is None or self._packed[0] != key:
+        def build():
             with torch.no_grad():
-                W, b = self.mask * self.weight, self.bias
-                if rows is not None:
-                    W, b = W.index_select(0, rows), b.index_select(0, rows)
+                W, b = self._masked(rows)
                 Wh, bh = W.bfloat16(), b.bfloat16()
                 Wl, bl = (W - Wh.float()).bfloat16(), (b - bh.float()).bfloat16()
-                K = W.shape[1]
-                pad = (-(3 * K + 2)) % 8
-                packed = torch.cat([Wh, Wh, Wl, bh[:, None], bl[:, None],
-                                    torch.zeros(W.shape[0], pad, dtype=torch.bfloat16, device=W.device)], 1).contiguous()
-            if capturing or not self._may_store(self.weight):
-                return packed
-            self._packed = (key, packed)
-        return self._packed[1]
+                pad = (-(3 * W.shape[1] + 2)) % 8
+                return torch.cat([Wh, Wh, Wl, bh[:, None], bl[:, None],
+                                  torch.zeros(W.shape[0], pad, dtype=torch.bfloat16, device=W.device)], 1).contiguous()
+        return self._cached("packed", self._key(rows), build)
 
     def packed_fragments(self, rows=None):
         """(fragments, bias) for ``umnn_made_mlp_forward``: the masked weight as bf16 MFMA fragments
         [tile][K-step][piece hi/lo][lane][8] in the K order of include/umnn_cc.h, and the fp32 bias (cached while weight, mask
         and bias are unchanged).  ``rows``: optional output-row selection (ConditionnalMADE)."""
-        key = (self.weight._version, self.weight.data_ptr(), self.mask._version, self.mask.data_ptr(),
-               self.bias._version, self.bias.data_ptr(), None if rows is None else rows.data_ptr())
-        capturing = self._capturing(self.weight)        # see masked_weight: recompute inside the graph, never cache
-        if capturing or self._frags is None or self._frags[0] != key:
+        def build():
             with torch.no_grad():
-                W, b = self.mask * self.weight, self.bias
-                if rows is not None:
-                    W, b = W.index_select(0, rows), b.index_select(0, rows)
-                packed = (pack_fragments(W.float()), b.float().contiguous())
-            if capturing or not self._may_store(self.weight):
-                return packed
-            self._frags = (key, packed)
-        return self._frags[1]
+                W, b = self._masked(rows)
+                return pack_fragments(W.float()), b.float().contiguous()
+        return self._cached("frags", self._key(rows), build)
 
     def forward(self, input):
         if _graph_mode():           # the reference's composition (made.py:26-27): no cache keyed on versions or pointers
@@ -163,9 +157,7 @@ def pack_fragments(W):
         k = 32 * torch.arange(S, device=W.device).view(1, S, 1, 1) + (16 * (j >> 2) + (j & 3)).view(1, 1, 1, 8) \
             + 4 * g.view(1, 1, 64, 1)                                                                            # [1,S,64,8]
         idx = (n.expand(T, S, 64, 8) * (32 * S) + k.expand(T, S, 64, 8)).reshape(-1)
-        # (never cached from inside a stream capture: the kernels that fill it have only been RECORDED then -- the tensor holds
-        #  nothing until that graph is replayed, and an eager call that found it in the cache would gather with garbage)
-        if not (W.is_cuda and torch.cuda.is_current_stream_capturing()):
+        if MaskedLinear._may_store(W):      # (indices built inside a capture would make an eager call gather with garbage)
             if len(_FRAG_INDEX) > 64:
                 _FRAG_INDEX.clear()
             _FRAG_INDEX[key] = idx
@@ -184,170 +176,211 @@ def invalidate_caches(module):
             m.invalidate_caches()
 
 
-_FAST = {"ok": None, "enabled": os.environ.get("UMNN_MADE_BF16X3", "1") != "0"}
+# ---- the switches ----------------------------------------------------------------------------------------------------------------
+@dataclasses.dataclass
+class MadeOptions:
+    """Every switch of the conditioner, read from the environment once at import (``_OPTIONS``); ``set_made_fast_path`` and
+    ``set_made_fused`` change the first six at run time.  (``UMNN_MADE_LINEAR_RT`` / ``_G``, the tuning knobs of made_linear_kernel,
+    are read per call: tools/made_layered_check.py changes them at run time.)"""
+    fast: bool                      # UMNN_MADE_BF16X3 != 0: the inference fast path
+    fused: bool                     # UMNN_MADE_FUSED != 0: the conditioner kernels (one launch, hidden stack, one per layer)
+    max_rows: int                   # UMNN_MADE_FUSED_MAX_ROWS: the batch size up to which they are used
+    wide_out: bool                  # UMNN_MADE_FUSED_WIDE_OUT == 1: outputs wider than 512 in the one-launch kernel too
+    hybrid: bool                    # UMNN_MADE_FUSED_HYBRID == 1: wide outputs as hidden stack in the kernel + one library GEMM
+    layered: bool                   # UMNN_MADE_LAYERED != 0: wide outputs as one made_linear_kernel launch per masked linear
+    layered_max_rows: int           # UMNN_MADE_LAYERED_MAX_ROWS: ... up to this many rows
+    # above this many rows a wide OUTPUT layer goes back to split + library GEMM (hipBLASLt's large tiles win there: 67 + 9 us against
+    # 97 us at 8192 x 512 x 1890), the hidden layers stay on made_linear_kernel (11-13 us against 9 + 23 us each)
+    layered_lib_out_rows: int       # UMNN_MADE_LAYERED_LIB_OUT_ROWS
+    train_fused: bool               # UMNN_MADE_TRAIN_FUSED != 0: the training chain as one autograd node
+    addmm_act: bool                 # UMNN_MADE_ADDMM_ACT != 0 and torch has _addmm_activation: bias + ReLU in the GEMM epilogue
+    probe: object = None            # None until _probe ran: whether torch.mm(bf16, bf16, out_dtype=float32) works here
+
+
+def _options_from_env(env):
+    return MadeOptions(fast=env.get("UMNN_MADE_BF16X3", "1") != "0", fused=env.get("UMNN_MADE_FUSED", "1") != "0",
+                       max_rows=int(env.get("UMNN_MADE_FUSED_MAX_ROWS", "32768")), wide_out=env.get("UMNN_MADE_FUSED_WIDE_OUT", "0") == "1",
+                       hybrid=env.get("UMNN_MADE_FUSED_HYBRID", "0") == "1", layered=env.get("UMNN_MADE_LAYERED", "1") != "0",
+                       layered_max_rows=int(env.get("UMNN_MADE_LAYERED_MAX_ROWS", "32768")),
+                       layered_lib_out_rows=int(env.get("UMNN_MADE_LAYERED_LIB_OUT_ROWS", "4096")),
+                       train_fused=env.get("UMNN_MADE_TRAIN_FUSED", "1") != "0",
+                       addmm_act=hasattr(torch, "_addmm_activation") and env.get("UMNN_MADE_ADDMM_ACT", "1") != "0")
+
+
+_OPTIONS = _options_from_env(os.environ)
+
+
+class _Switch:
+    """One field of ``_OPTIONS`` under its earlier spelling ``NAME["enabled"]`` (tests/test_gpu_round6.py sets ``_TRAIN_FUSED`` so)."""
+
+    def __init__(self, field):
+        self.field = field
+
+    def __getitem__(self, key):
+        return getattr(_OPTIONS, self.field)
+
+    def __setitem__(self, key, value):
+        setattr(_OPTIONS, self.field, bool(value))
+
+
+_TRAIN_FUSED = _Switch("train_fused")
 
 
 def set_made_fast_path(enabled):
     """Inference conditioner GEMMs as K-concatenated bf16 GEMMs (True, default) or plain fp32 ``F.linear`` (False)."""
-    _FAST["enabled"] = bool(enabled)
+    _OPTIONS.fast = bool(enabled)
 
 
 def get_made_fast_path():
-    return _FAST["enabled"]
-
-
-def _fast_path_ok(x):
-    """bf16x3 GEMM path: CUDA fp32 input, autograd off, HIP library present, torch.mm(out_dtype=) available."""
-    if torch.is_grad_enabled() or not x.is_cuda or x.dtype != torch.float32:
-        return False
-    if not _FAST["enabled"]:
-        return False
-    if _FAST["ok"] is None:
-        from . import _lib
-        _lib.lib()              # a missing HIP library is an error on a GPU box (HipLibraryMissing), never a silent fallback
-        try:
-            a = torch.zeros(8, 8, dtype=torch.bfloat16, device=x.device)
-            torch.mm(a, a.t(), out_dtype=torch.float32)
-            _FAST["ok"] = True
-        except (TypeError, RuntimeError, NotImplementedError) as e:     # a torch build without mm(out_dtype=) on this device
-            _FAST["ok"] = False
-            warnings.warn("umnn_amd: torch.mm(bf16, bf16, out_dtype=float32) is not available here "
-                          f"({type(e).__name__}: {e}); the inference conditioner runs the fp32 F.linear chain instead of the "
-                          "K-concatenated bf16 GEMMs.", RuntimeWarning, stacklevel=3)
-    return _FAST["ok"]
-
-
-def _fast_chain(a, layers, last_rows=None, out_dtype=None):
-    """a [B, K0] fp32 -> output of the MaskedLinear/ReLU chain, every GEMM as one K-concatenated bf16 GEMM (fp32
-    accumulation).  ``out_dtype=torch.bfloat16``: the LAST GEMM writes the embedding straight in bf16 (configuration C4:
-    the [B, E*d] tensor the quadrature kernels then read with bf16 loads -- half the bytes of that round trip)."""
-    from . import _lib
-    lib = _lib.lib()
-    raw = a.contiguous()
-    stream = _stream(a.device)
-    with torch.cuda.device(a.device):
-        for i, layer in enumerate(layers):
-            last = i == len(layers) - 1
-            packed = layer.packed_bf16(last_rows if last else None)
-            op = torch.empty(raw.shape[0], packed.shape[1], dtype=torch.bfloat16, device=a.device)
-            _lib.check(lib.umnn_made_split3(_ptr(raw), raw.shape[0], raw.shape[1], 1 if i > 0 else 0,
-                                            _ptr(op), op.shape[1], stream), "made_split3")
-            if last and out_dtype == torch.bfloat16:
-                raw = torch.mm(op, packed.t())                       # bf16 out, fp32 accumulate inside the GEMM
-            else:
-                raw = torch.mm(op, packed.t(), out_dtype=torch.float32)
-    return raw
-
-
-_FUSED = {"enabled": os.environ.get("UMNN_MADE_FUSED", "1") != "0", "max_rows": int(os.environ.get("UMNN_MADE_FUSED_MAX_ROWS", "32768")),
-          "wide_out": os.environ.get("UMNN_MADE_FUSED_WIDE_OUT", "0") == "1",
-          "hybrid": os.environ.get("UMNN_MADE_FUSED_HYBRID", "0") == "1",
-          "layered": os.environ.get("UMNN_MADE_LAYERED", "1") != "0"}
+    return _OPTIONS.fast
 
 
 def set_made_fused(enabled, max_rows=None, wide_out=None, hybrid=None, layered=None):
     """The whole conditioner of a block as ONE launch (``umnn_made_mlp_forward``) on the inference path when every width is
-    <= 512 (see ``_fused_ok``) and the batch has at most ``max_rows`` rows (default 32768).  ``False``: always the per-layer
+    <= 512 (see ``conditioner_route``) and the batch has at most ``max_rows`` rows (default 32768).  ``False``: always the per-layer
     path.  ``wide_out=True`` lifts the limit on the OUTPUT width (tests / measurements)."""
-    _FUSED["enabled"] = bool(enabled)
+    _OPTIONS.fused = bool(enabled)
     if max_rows is not None:
-        _FUSED["max_rows"] = int(max_rows)
+        _OPTIONS.max_rows = int(max_rows)
     if wide_out is not None:
-        _FUSED["wide_out"] = bool(wide_out)
+        _OPTIONS.wide_out = bool(wide_out)
     if hybrid is not None:           # wide outputs: hidden stack in the kernel, output layer as one library GEMM (measured: no gain)
-        _FUSED["hybrid"] = bool(hybrid)
+        _OPTIONS.hybrid = bool(hybrid)
     if layered is not None:          # wide outputs: one launch of the kernel per masked linear, grid over rows x output tiles
-        _FUSED["layered"] = bool(layered)
+        _OPTIONS.layered = bool(layered)
 
 
-def _fused_ok(a, layers, n_out=None):
-    """-> 0 (split + library GEMM per layer), 1 (whole conditioner in one launch), 2 (hidden stack in one launch + the output
-    layer as ONE library GEMM) or 3 (one launch of ``made_linear_kernel`` per masked linear).  Every input / hidden width must
-    be <= 512.  Measured with bench.py's workloads (tools/bench_fused.sh, tools/made_layered_check.py): narrow outputs (toy 20,
-    POWER 180 columns) win with the whole MLP in the kernel (0.203 -> 0.162 ms, 2.21 -> 2.00 ms per step); wide output layers
-    (BSDS300's 1890, the VAE flow's 1920 columns) lose there (several passes of a kernel that streams its weights at one wave
-    per SIMD: 12.92 vs 13.11 ms, 1.02 vs 1.34 ms), and feeding hipBLASLt's output GEMM from the kernel's hidden stack (mode 2,
-    ``hybrid=True``) does not beat four short launches either (VAE 1.03 vs 1.11 ms, BSDS300 13.55 vs 13.58 ms); one launch per
-    layer with the grid split over output tiles (mode 3) wins at launch-bound batch sizes (VAE at 1024 rows 1.00 -> 0.91 ms) and
-    the hidden layers also at 8192 rows (C3: 140 -> 100 us per block with the 1890-column output layer back on split + hipBLASLt
-    above ``UMNN_MADE_LAYERED_LIB_OUT_ROWS`` = 4096 rows); taken up to ``UMNN_MADE_LAYERED_MAX_ROWS`` rows (32768)."""
-    if not _FUSED["enabled"] or a.shape[0] > _FUSED["max_rows"] or len(layers) > 8:
-        return 0
-    if not all(l.in_features <= 512 for l in layers):
-        return 0
-    n_out = layers[-1].out_features if n_out is None else n_out
-    if n_out <= 512 or _FUSED.get("wide_out", False):
-        return 1
-    if len(layers) >= 2 and _FUSED.get("hybrid", False):
-        return 2
-    return 3 if (_FUSED.get("layered", True) and a.shape[0] <= _LAYERED_MAX_ROWS) else 0
+def _probe(cuda_fp32, device):
+    """The lazy probe of the bf16x3 GEMM path, run once and only where that path could be taken (CUDA fp32 input, autograd off, the
+    switch on): HIP library present, torch.mm(out_dtype=) available."""
+    if torch.is_grad_enabled() or not cuda_fp32 or not _OPTIONS.fast:
+        return False
+    if _OPTIONS.probe is None:
+        from . import _lib
+        _lib.lib()              # a missing HIP library is an error on a GPU box (HipLibraryMissing), never a silent fallback
+        try:
+            a = torch.zeros(8, 8, dtype=torch.bfloat16, device=device)
+            torch.mm(a, a.t(), out_dtype=torch.float32)
+            _OPTIONS.probe = True
+        except (TypeError, RuntimeError, NotImplementedError) as e:     # a torch build without mm(out_dtype=) on this device
+            _OPTIONS.probe = False
+            warnings.warn("umnn_amd: torch.mm(bf16, bf16, out_dtype=float32) is not available here "
+                          f"({type(e).__name__}: {e}); the inference conditioner runs the fp32 F.linear chain instead of the "
+                          "K-concatenated bf16 GEMMs.", RuntimeWarning, stacklevel=4)
+    return _OPTIONS.probe
 
 
-def _fused_chain(a, layers, last_rows=None, out_dtype=None, mode=1):
-    """a [B, K0] fp32 -> conditioner output through the fused kernel (csrc/made_fused.hip): the whole MLP (mode 1) or its
-    hidden stack, whose last ReLU output leaves as the bf16 operand of the output layer's library GEMM (mode 2)."""
+def _fast_path_ok(x):
+    """bf16x3 GEMM path: CUDA fp32 input, autograd off, HIP library present, torch.mm(out_dtype=) available."""
+    return _probe(x.is_cuda and x.dtype == torch.float32, x.device)
+
+
+# ---- the route -------------------------------------------------------------------------------------------------------------------
+Route = collections.namedtuple("Route", "name no_cat lib_out")
+Route.__doc__ = """What one conditioner call does.  ``name``: "graph" | "split" | "fused" | "hybrid" | "layered" | "train" | "linear"
+(the rows of DESIGN.md's route table); ``no_cat``: ConditionnalMADE's two input blocks are read without the cat; ``lib_out``
+("layered" only): the output layer goes to split + library GEMM."""
+_FAST_ROUTES = ("split", "fused", "hybrid", "layered")
+
+
+def conditioner_route(rows, widths, n_out, cuda_fp32, two_fp32_blocks, grad, needs_grad, autocast, graph, probe, opts):
+    """The only route decision: a function of values (no library load, no probe, no device call) -> ``Route``.
+      rows: batch rows; widths: (in_features, out_features) per masked linear; n_out: the output width that survives;
+      cuda_fp32: the chain's input (after ``_to_weight_dtype``) is a CUDA fp32 tensor; two_fp32_blocks: it arrives as two fp32 column
+      blocks on fp32 weights; grad: grad mode; needs_grad: a 2-D input on CUDA fp32 weights with biases of which something requires
+      grad; autocast; graph: ``_graph_mode()``; probe: the result of ``_probe``; opts: a ``MadeOptions``."""
+    if graph:                                   # torch.compile / export / jit.trace: the reference's fp32 F.linear chain
+        return Route("graph", False, False)
+    if not grad and cuda_fp32 and opts.fast and probe:
+        if not opts.fused or rows > opts.max_rows or len(widths) > 8 or any(k > 512 for k, _ in widths):
+            return Route("split", False, False)
+        if n_out <= 512 or opts.wide_out:
+            return Route("fused", False, False)
+        if len(widths) >= 2 and opts.hybrid:
+            return Route("hybrid", False, False)
+        if opts.layered and rows <= opts.layered_max_rows:
+            return Route("layered", two_fp32_blocks, len(widths) > 1 and rows > opts.layered_lib_out_rows and widths[-1][1] > 512)
+        return Route("split", False, False)
+    if opts.train_fused and grad and cuda_fp32 and not autocast and needs_grad:
+        return Route("train", False, False)
+    return Route("linear", False, False)
+
+
+def _split_gemm(lib, stream, raw, relu, packed, bf16, fill=None):
+    """One masked linear as the K-concatenated bf16 GEMM on ``packed`` [N, pad8(3K+2)]: the left operand [xh | xl | xh | 1 | 1] is
+    written by one ``umnn_made_split3`` launch from ``raw`` (ReLU fused if ``relu``) or by ``fill(op)``; the GEMM accumulates in fp32
+    and writes fp32, or bf16 (configuration C4: the [B, E*d] embedding the quadrature kernels then read with bf16 loads)."""
+    from . import _lib
+    op = torch.empty(raw.shape[0], packed.shape[1], dtype=torch.bfloat16, device=raw.device)
+    if fill is None:
+        _lib.check(lib.umnn_made_split3(_ptr(raw), raw.shape[0], raw.shape[1], 1 if relu else 0, _ptr(op), op.shape[1], stream),
+                   "made_split3")
+    else:
+        fill(op)
+    return torch.mm(op, packed.t()) if bf16 else torch.mm(op, packed.t(), out_dtype=torch.float32)
+
+
+def _run_route(route, a, a2, layers, keep, out_dtype, select=None):
+    """Execute ``route`` on a [B, K0] (or its two column blocks a | a2) through the MaskedLinear / ReLU chain ``layers``; ``keep``: the
+    rows of the last layer that are computed (ConditionnalMADE), ``select``: rows taken from its cached FULL packed weight
+    (``raw_rows``).  The fast routes write ``out_dtype`` = bf16 themselves; the others return the chain's dtype.
+      "split":   per layer one split launch + one library GEMM;
+      "fused":   the whole MLP in one launch of the fused kernel (csrc/made_fused.hip);
+      "hybrid":  its hidden stack in one launch, whose last ReLU output leaves as the bf16 operand of the output layer's library GEMM;
+      "layered": one launch of ``made_linear_kernel`` per masked linear (``umnn_made_linear_forward``: grid over row groups x
+                 output-tile groups, the bf16 split and the previous layer's ReLU in the operand load, ConditionnalMADE's two blocks
+                 read without the cat), the output layer as in "split" if ``route.lib_out``;
+      "train":   the one-node training chain; "graph" / "linear": masked ``F.linear`` + ReLU."""
+    name = route.name
+    if name == "train":
+        return _train_chain(a, layers, keep)
+    if name not in _FAST_ROUTES:
+        for layer in layers[:-1]:
+            a = torch.relu(layer(a))
+        if keep is None:
+            return layers[-1](a)
+        return F.linear(a, layers[-1].masked_weight().index_select(0, keep), layers[-1].bias.index_select(0, keep))
     from . import _lib
     lib = _lib.lib()
-    a = a.contiguous()
-    inner = layers if mode == 1 else layers[:-1]
-    net = _lib.MadeNet()
-    net.n_layers = len(inner)
-    net.widths[0] = inner[0].in_features
-    keep = []
-    for i, layer in enumerate(inner):
-        frags, bias = layer.packed_fragments(last_rows if (mode == 1 and i == len(inner) - 1) else None)
-        keep += [frags, bias]
-        net.widths[i + 1] = bias.shape[0]
-        net.W[i], net.b[i] = _ptr(frags), _ptr(bias)
     bf16 = out_dtype == torch.bfloat16
-    with torch.cuda.device(a.device):
-        stream = _stream(a.device)
-        if mode == 1:
-            out = torch.empty(a.shape[0], net.widths[len(inner)], device=a.device, dtype=torch.bfloat16 if bf16 else torch.float32)
-            _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), _ptr(a), a.shape[0], _ptr(out), 1 if bf16 else 0, 0,
-                                                    stream), "umnn_made_mlp_forward")
-            return out
-        packed = layers[-1].packed_bf16(last_rows)                      # [N, pad8(3K+2)]: the per-layer path's weight operand
-        op = torch.empty(a.shape[0], packed.shape[1], dtype=torch.bfloat16, device=a.device)
-        _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), _ptr(a), a.shape[0], _ptr(op), 2, op.shape[1], stream),
-                   "umnn_made_mlp_forward")
-    if bf16:
-        return torch.mm(op, packed.t())                                  # bf16 out, fp32 accumulate inside the GEMM
-    return torch.mm(op, packed.t(), out_dtype=torch.float32)
-
-
-_LAYERED_MAX_ROWS = int(os.environ.get("UMNN_MADE_LAYERED_MAX_ROWS", "32768"))
-# above this many rows a wide OUTPUT layer goes back to split + library GEMM (hipBLASLt's large tiles win there: 67 + 9 us against
-# 97 us at 8192 x 512 x 1890), the hidden layers stay on made_linear_kernel (11-13 us against 9 + 23 us each)
-_LAYERED_LIB_OUT_ROWS = int(os.environ.get("UMNN_MADE_LAYERED_LIB_OUT_ROWS", "4096"))
-
-
-def _layered_chain(a, layers, last_rows=None, out_dtype=None, a2=None):
-    """a [B, K0] fp32 (or the two column blocks a | a2 of it) -> conditioner output, one launch of ``made_linear_kernel`` per
-    masked linear (``umnn_made_linear_forward``: grid over row groups x output-tile groups, the bf16 split and the previous
-    layer's ReLU in the operand load) -- the route of conditioners with a wide output layer at launch-bound batch sizes,
-    replacing split + library GEMM pairs (two launches per layer) and the cat of ConditionnalMADE's two inputs."""
-    from . import _lib
-    lib = _lib.lib()
     cur, cur2 = a.contiguous(), (None if a2 is None else a2.contiguous())
-    B = cur.shape[0]
-    rt, fg = int(os.environ.get("UMNN_MADE_LINEAR_RT", "0")), int(os.environ.get("UMNN_MADE_LINEAR_G", "0"))
-    with torch.cuda.device(a.device):
-        stream = _stream(a.device)
+    B, dev = cur.shape[0], a.device
+    with torch.cuda.device(dev):
+        stream = _stream(dev)
+        if name in ("fused", "hybrid"):
+            inner = layers if name == "fused" else layers[:-1]
+            net, held = _lib.MadeNet(), []
+            net.n_layers = len(inner)
+            net.widths[0] = inner[0].in_features
+            for i, layer in enumerate(inner):
+                frags, bias = layer.packed_fragments(keep if layer is layers[-1] else None)
+                held += [frags, bias]
+                net.widths[i + 1] = bias.shape[0]
+                net.W[i], net.b[i] = _ptr(frags), _ptr(bias)
+
+            def launch(out, mode, ld=0):
+                _lib.check(lib.umnn_made_mlp_forward_ex(ctypes.byref(net), _ptr(cur), B, _ptr(out), mode, ld, stream), "umnn_made_mlp_forward")
+            if name == "hybrid":
+                return _split_gemm(lib, stream, cur, True, layers[-1].packed_bf16(keep), bf16, fill=lambda op: launch(op, 2, op.shape[1]))
+            out = torch.empty(B, net.widths[len(inner)], device=dev, dtype=torch.bfloat16 if bf16 else torch.float32)
+            launch(out, 1 if bf16 else 0)
+            return out
+        # (made_linear_kernel's tuning knobs, read per call: tools/made_layered_check.py changes them at run time)
+        rt, fg = (int(os.environ.get("UMNN_MADE_LINEAR_RT", "0")), int(os.environ.get("UMNN_MADE_LINEAR_G", "0"))) if name == "layered" else (0, 0)
         for i, layer in enumerate(layers):
             last = i == len(layers) - 1
-            bf16 = last and out_dtype == torch.bfloat16
-            if last and i > 0 and B > _LAYERED_LIB_OUT_ROWS and layer.out_features > 512:
-                packed = layer.packed_bf16(last_rows)                   # [N, pad8(3K+2)]: the library route's weight operand
-                op = torch.empty(B, packed.shape[1], dtype=torch.bfloat16, device=a.device)
-                _lib.check(lib.umnn_made_split3(_ptr(cur), B, cur.shape[1], 1, _ptr(op), op.shape[1], stream), "made_split3")
-                return torch.mm(op, packed.t()) if bf16 else torch.mm(op, packed.t(), out_dtype=torch.float32)
-            frags, bias = layer.packed_fragments(last_rows if last else None)
-            out = torch.empty(B, bias.shape[0], device=a.device, dtype=torch.bfloat16 if bf16 else torch.float32)
+            if name == "split" or (last and route.lib_out):
+                packed = layer.packed_bf16(keep if last else None)
+                if last and select is not None:         # (from the cached full weight: a per-call selection never enters the layer's cache)
+                    packed = packed.index_select(0, select)
+                cur = _split_gemm(lib, stream, cur, i > 0, packed, last and bf16)
+                continue
+            frags, bias = layer.packed_fragments(keep if last else None)
+            out = torch.empty(B, bias.shape[0], device=dev, dtype=torch.bfloat16 if last and bf16 else torch.float32)
             K = cur.shape[1] + (0 if cur2 is None else cur2.shape[1])
             _lib.check(lib.umnn_made_linear_forward(_ptr(frags), _ptr(bias), K, bias.shape[0], _ptr(cur),
                                                     None if cur2 is None else _ptr(cur2), cur.shape[1], B, 1 if i > 0 else 0,
-                                                    _ptr(out), 1 if bf16 else 0, rt, fg, stream), "umnn_made_linear_forward")
+                                                    _ptr(out), 1 if last and bf16 else 0, rt, fg, stream), "umnn_made_linear_forward")
             cur, cur2 = out, None
     return cur
 
@@ -359,20 +392,6 @@ def _layered_chain(a, layers, last_rows=None, out_dtype=None, a2=None):
 # runs the same fp32 library GEMMs on the cached masked weight (one product per optimizer step, no autograd node), the ReLU in place;
 # the backward runs, per layer, ONE pass that applies the ReLU mask to the incoming gradient and reduces the bias gradient in a fixed
 # order (umnn_made_relu_bwd_bias: data-parallel replicas stay bit-identical), the two GEMMs, and the mask on the weight gradient in place.
-_TRAIN_FUSED = {"enabled": os.environ.get("UMNN_MADE_TRAIN_FUSED", "1") != "0"}
-_HAS_ADDMM_ACT = hasattr(torch, "_addmm_activation") and os.environ.get("UMNN_MADE_ADDMM_ACT", "1") != "0"
-
-
-def _train_chain_ok(a, layers):
-    if not (_TRAIN_FUSED["enabled"] and torch.is_grad_enabled() and a.is_cuda and a.dtype == torch.float32 and a.dim() == 2):
-        return False
-    if torch.is_autocast_enabled():
-        return False
-    if not all(l.weight.dtype == torch.float32 and l.bias is not None and l.weight.is_cuda for l in layers):
-        return False
-    return a.requires_grad or any(l.weight.requires_grad or l.bias.requires_grad for l in layers)
-
-
 class _MadeTrainChain(torch.autograd.Function):
     """out = MaskedLinear_L(ReLU(... ReLU(MaskedLinear_1(a)))) [rows ``keep`` of the last layer only] as one node.
     apply(a, layers, keep, W_1, b_1, ..., W_L, b_L): ``layers`` the MaskedLinear modules (for their masks / cached masked weights),
@@ -390,7 +409,7 @@ class _MadeTrainChain(torch.autograd.Function):
             weffs.append(W)
             if not last:
                 # bias + ReLU in the GEMM's epilogue (hipBLASLt): no separate activation pass over [B, N]
-                cur = y = torch._addmm_activation(b, cur, W.t(), use_gelu=False) if _HAS_ADDMM_ACT else torch.relu_(torch.addmm(b, cur, W.t()))
+                cur = y = torch._addmm_activation(b, cur, W.t(), use_gelu=False) if _OPTIONS.addmm_act else torch.relu_(torch.addmm(b, cur, W.t()))
                 acts.append(cur)
             else:
                 y = torch.addmm(b, cur, W.t())
@@ -455,6 +474,10 @@ def _to_weight_dtype(x, layer):
     if x.dtype != layer.weight.dtype and not torch.is_autocast_enabled():
         return x.to(layer.weight.dtype)
     return x
+
+
+def _cast(out, out_dtype):
+    return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
 
 
 class ProgressivePlan:
@@ -561,7 +584,6 @@ class MADE(nn.Module):
         self.natural_ordering, self.num_masks, self.seed = natural_ordering, num_masks, 0
         self.m = {}
         self._prog_static = None    # (key, device-resident index tensors + host step table) of progressive_plan
-        self._prog = None           # (key, ProgressivePlan)
         self.update_masks()
 
     def _degrees(self):
@@ -589,14 +611,14 @@ class MADE(nn.Module):
         masks.append(self.m[L - 1][:, None] < self.m[-1][None, :])                   # output: strict
         if self.nout > self.nin:
             masks[-1] = np.tile(masks[-1], (1, self.nout // self.nin))
-        for layer, mask in zip((l for l in self.net if isinstance(l, MaskedLinear)), masks):
+        for layer, mask in zip(self._masked_layers(), masks):
             layer.set_mask(mask)
         self.i_map = np.argsort(self.m[-1])
 
-    # ---- progressive conditioner of the sequential sampling walk -----------------------------------------------------------------
     def _masked_layers(self):
         return [l for l in self.net if isinstance(l, MaskedLinear)]
 
+    # ---- progressive conditioner of the sequential sampling walk -----------------------------------------------------------------
     def _progressive_static(self, device):
         """The part of the plan that depends on the degrees only: orders, output rows, the step table.  None when ineligible."""
         layers = self._masked_layers()
@@ -640,8 +662,8 @@ class MADE(nn.Module):
         <= c + j - 1 (step 0 of a conditional block: all units of degree < c at once); a hidden layer's prefix is the count of previous
         -layer units of degree <= c + j - 1, the output's the count of last-hidden units of degree < c + j, layer 0's the c + j input
         columns; units of degree >= nin - 1 are never computed.  The permuted weights stay MASKED: their exact zeros make a prefix longer
-        than one unit's own mask still exact.  Cached like the packed weights: keyed on weight / mask / bias versions and pointers,
-        dropped by ``invalidate_caches`` and ``set_mask``; nothing produced during a stream capture is stored."""
+        than one unit's own mask still exact.  Cached like the packed weights (``MaskedLinear._cached``, in the first layer's slots):
+        keyed on weight / mask / bias versions and pointers, dropped by ``invalidate_caches`` and ``set_mask``."""
         layers = self._masked_layers()
         w0 = layers[0].weight
         if w0.dtype not in (torch.float32, torch.float64) or w0.device != device or any(l.bias is None for l in layers):
@@ -649,54 +671,64 @@ class MADE(nn.Module):
         static = self._progressive_static(device)
         if static is None:
             return None
-        key = (str(device), w0.dtype) + tuple((l._epoch, l.weight._version, l.weight.data_ptr(), l.mask._version, l.mask.data_ptr(),
-                                               l.bias._version, l.bias.data_ptr()) for l in layers)
-        capturing = MaskedLinear._capturing(w0)         # see MaskedLinear.masked_weight: recompute inside the graph, never cache
-        if not capturing and self._prog is not None and self._prog[0] == key and self._prog[1] is not None:
-            return self._prog[1]
         L = len(self.hidden_sizes)
-        with torch.no_grad():
-            W, b = [], []
-            for l in range(L):
-                w = (layers[l].mask * layers[l].weight).index_select(0, static["orders"][l])
-                if l > 0:
-                    w = w.index_select(1, static["orders"][l - 1])
-                W.append(F.pad(w, (0, static["ldk"][l] - w.shape[1])).contiguous())
-                b.append(layers[l].bias.index_select(0, static["orders"][l]).contiguous())
-            w = (layers[L].mask * layers[L].weight).index_select(0, static["out_rows"]).index_select(1, static["orders"][L - 1])
-            W.append(F.pad(w, (0, static["ldk"][L] - w.shape[1])).view(static["d"], static["E"], static["ldk"][L]).contiguous())
-            b.append(layers[L].bias.index_select(0, static["out_rows"]).view(static["d"], static["E"]).contiguous())
-        plan = ProgressivePlan(static, W, b)
-        if capturing or not MaskedLinear._may_store(w0):
-            return plan
-        self._prog = (key, plan)
-        return plan
+
+        def build():
+            with torch.no_grad():
+                W, b = [], []
+                for l in range(L):
+                    w = (layers[l].mask * layers[l].weight).index_select(0, static["orders"][l])
+                    if l > 0:
+                        w = w.index_select(1, static["orders"][l - 1])
+                    W.append(F.pad(w, (0, static["ldk"][l] - w.shape[1])).contiguous())
+                    b.append(layers[l].bias.index_select(0, static["orders"][l]).contiguous())
+                w = (layers[L].mask * layers[L].weight).index_select(0, static["out_rows"]).index_select(1, static["orders"][L - 1])
+                W.append(F.pad(w, (0, static["ldk"][L] - w.shape[1])).view(static["d"], static["E"], static["ldk"][L]).contiguous())
+                b.append(layers[L].bias.index_select(0, static["out_rows"]).view(static["d"], static["E"]).contiguous())
+            return ProgressivePlan(static, W, b)
+        return layers[0]._cached("plan", (str(device), w0.dtype) + tuple((l._epoch,) + l._key()[:6] for l in layers), build)
+
+    # ---- the conditioner call: gather the inputs, ask for the route, run it ------------------------------------------------------
+    def _kept_rows(self, device):
+        return None                 # MADE keeps every output row
+
+    def _drop_context(self, out):
+        return out                  # ... and every output column
+
+    def _raw(self, x, context, n_out, out_dtype):
+        layers = self._masked_layers()
+        w = layers[0].weight
+        grad, autocast, graph = torch.is_grad_enabled(), torch.is_autocast_enabled(), _graph_mode()
+        cuda_fp32 = x.is_cuda and (x.dtype if autocast else w.dtype) == torch.float32       # (of the input after _to_weight_dtype)
+        needs_grad = (grad and not graph and x.dim() == 2 and all(l.weight.dtype == torch.float32 and l.bias is not None and l.weight.is_cuda for l in layers)
+                      and (x.requires_grad or (context is not None and context.requires_grad)
+                           or any(l.weight.requires_grad or l.bias.requires_grad for l in layers)))
+        route = conditioner_route(x.shape[0], [(l.in_features, l.out_features) for l in layers], n_out, cuda_fp32,
+                                  context is not None and x.dtype == torch.float32 == w.dtype, grad, needs_grad, autocast, graph,
+                                  not graph and _probe(cuda_fp32, x.device), _OPTIONS)
+        if context is None:
+            a, a2 = _to_weight_dtype(x, layers[0]), None
+        elif route.no_cat:                      # the kernel reads both blocks
+            a, a2 = context, x
+        else:
+            a, a2 = _to_weight_dtype(torch.cat((context, x), 1), layers[0]), None
+        # (graph mode computes every row and drops the context columns, as the reference does: no index tensor enters the graph)
+        out = _run_route(route, a, a2, layers, None if graph else self._kept_rows(x.device), out_dtype)
+        if route.name in _FAST_ROUTES:
+            return out
+        return _cast(self._drop_context(out) if graph else out, out_dtype)
 
     def raw(self, x, out_dtype=None):
         """The masked MLP itself (what the flow's EmbeddingNetwork needs, whatever nout is)."""
-        x = _to_weight_dtype(x, self.net[0])
-        if _graph_mode():           # torch.compile / export / jit.trace: fp32 F.linear + ReLU, as the reference composes it
-            out = self.net(x)
-            return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
-        if _fast_path_ok(x):
-            layers = [l for l in self.net if isinstance(l, MaskedLinear)]
-            mode = _fused_ok(x, layers)
-            if mode == 3:
-                return _layered_chain(x, layers, out_dtype=out_dtype)
-            if mode:
-                return _fused_chain(x, layers, out_dtype=out_dtype, mode=mode)
-            return _fast_chain(x, layers, out_dtype=out_dtype)
-        layers = [l for l in self.net if isinstance(l, MaskedLinear)]
-        out = _train_chain(x, layers) if _train_chain_ok(x, layers) else self.net(x)
-        return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
+        return self._raw(x, None, self.nout, out_dtype)
 
     def graph_weights(self):
         """[mask * weight] of every masked linear, formed by ordinary torch ops: what a recorded caller that runs the conditioner
         many times on unchanged weights (the sampling loops of ``UMNNMAF.invert``) forms once and hands to ``raw_graph``."""
-        return [l.mask * l.weight for l in self.net if isinstance(l, MaskedLinear)]
+        return [l.mask * l.weight for l in self._masked_layers()]
 
     def _graph_chain(self, a, weights):
-        layers = [l for l in self.net if isinstance(l, MaskedLinear)]
+        layers = self._masked_layers()
         for i, (layer, w) in enumerate(zip(layers, weights)):
             a = F.linear(a, w, layer.bias)
             if i + 1 < len(layers):
@@ -705,8 +737,7 @@ class MADE(nn.Module):
 
     def raw_graph(self, x, weights, out_dtype=None):
         """``raw(x)`` in its graph-mode composition (fp32 F.linear + ReLU) on the masked weights of ``graph_weights()``."""
-        out = self._graph_chain(_to_weight_dtype(x, self.net[0]), weights)
-        return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
+        return _cast(self._graph_chain(_to_weight_dtype(x, self.net[0]), weights), out_dtype)
 
     def raw_rows(self, x, rows):
         """Output COLUMNS ``rows`` (an int64 device tensor) of ``raw(x)`` only -> [B, len(rows)] fp32, or None when this
@@ -715,25 +746,11 @@ class MADE(nn.Module):
         dimension): for d = 784 the last masked linear is 23 520 rows of which 30 are read.  Inference path only (K-concatenated
         bf16 GEMMs): hidden layers as in ``raw``, the last layer as [B, 3K+2] x [3K+2, len(rows)] on the selected rows of its cached
         packed weight."""
-        layers = [l for l in self.net if isinstance(l, MaskedLinear)]
-        x = _to_weight_dtype(x, self.net[0])
+        layers = self._masked_layers()
+        x = _to_weight_dtype(x, layers[0])
         if len(layers) < 2 or layers[-1].out_features < 4096 or not _fast_path_ok(x):
             return None
-        from . import _lib
-        lib = _lib.lib()
-        raw = x.contiguous()
-        stream = _stream(x.device)
-        with torch.cuda.device(x.device):
-            for i, layer in enumerate(layers):
-                last = i == len(layers) - 1
-                packed = layer.packed_bf16(None)
-                if last:
-                    packed = packed.index_select(0, rows)
-                op = torch.empty(raw.shape[0], packed.shape[1], dtype=torch.bfloat16, device=x.device)
-                _lib.check(lib.umnn_made_split3(_ptr(raw), raw.shape[0], raw.shape[1], 1 if i > 0 else 0,
-                                                _ptr(op), op.shape[1], stream), "made_split3")
-                raw = torch.mm(op, packed.t(), out_dtype=torch.float32)
-        return raw
+        return _run_route(Route("split", False, False), x, None, layers, None, None, select=rows)
 
     def forward(self, x, context=None):
         if self.nout == 2:       # reference quirk (made.py:114-118): nout == 2 means "Gaussian MADE"
@@ -781,51 +798,24 @@ class ConditionnalMADE(MADE):
             self._keep = idx.reshape(-1).to(device)
         return self._keep
 
+    def _drop_context(self, out):
+        """The reference's ConditionnalMADE.forward (made.py:165-168): [B, k*nin] -> the non-context columns of every chunk."""
+        return out.view(out.shape[0], out.shape[1] // self.nin, self.nin)[:, :, self.cond_in:].reshape(out.shape[0], -1)
+
     def raw(self, x, context, out_dtype=None):
         if context.dtype != x.dtype:
             context = context.to(x.dtype)
-        if _graph_mode():           # the reference's ConditionnalMADE.forward (made.py:165-168) on the fp32 F.linear chain
-            out = self.net(_to_weight_dtype(torch.cat((context, x), 1), self.net[0]))
-            out = out.view(x.shape[0], out.shape[1] // self.nin, self.nin)[:, :, self.cond_in:].reshape(x.shape[0], -1)
-            return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
-        if x.dtype == context.dtype == torch.float32 == self.net[0].weight.dtype and _fast_path_ok(x):
-            layers = [l for l in self.net if isinstance(l, MaskedLinear)]
-            if _fused_ok(x, layers, self.nin_non_cond * (self.nout // self.nin)) == 3:    # the kernel reads both blocks: no cat
-                return _layered_chain(context, layers, self._kept_rows(x.device), out_dtype, a2=x)
-        a = _to_weight_dtype(torch.cat((context, x), 1), self.net[0])
-        if _fast_path_ok(a):
-            layers = [l for l in self.net if isinstance(l, MaskedLinear)]
-            mode = _fused_ok(a, layers, self.nin_non_cond * (self.nout // self.nin))
-            if mode == 3:
-                return _layered_chain(a, layers, self._kept_rows(a.device), out_dtype)
-            if mode:
-                return _fused_chain(a, layers, self._kept_rows(a.device), out_dtype, mode=mode)
-            return _fast_chain(a, layers, self._kept_rows(a.device), out_dtype)
-        keep = self._kept_rows(a.device)
-        mlayers = [l for l in self.net if isinstance(l, MaskedLinear)]
-        if _train_chain_ok(a, mlayers):
-            out = _train_chain(a, mlayers, keep)
-            return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
-        layers = list(self.net)
-        for layer in layers[:-1]:
-            a = layer(a)
-        last = layers[-1]
-        out = F.linear(a, last.masked_weight().index_select(0, keep), last.bias.index_select(0, keep))
-        return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
+        return self._raw(x, context, self.nin_non_cond * (self.nout // self.nin), out_dtype)
 
     def raw_graph(self, x, context, weights, out_dtype=None):
         if context.dtype != x.dtype:
             context = context.to(x.dtype)
         out = self._graph_chain(_to_weight_dtype(torch.cat((context, x), 1), self.net[0]), weights)
-        out = out.view(x.shape[0], out.shape[1] // self.nin, self.nin)[:, :, self.cond_in:].reshape(x.shape[0], -1)
-        return out.to(out_dtype) if out_dtype is not None and out.dtype != out_dtype else out
+        return _cast(self._drop_context(out), out_dtype)
 
     def forward(self, x, context):
         if self.nout == 2:
-            out = super().forward(torch.cat((context, x), 1))
-            B = x.shape[0]
-            return out.contiguous().view(B, out.shape[1] // self.nin, self.nin)[:, :, self.cond_in:] \
-                .contiguous().view(B, -1)
+            return self._drop_context(super().forward(torch.cat((context, x), 1)))
         return self.raw(x, context)
 
     def computeLL(self, x, context):
