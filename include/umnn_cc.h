@@ -41,6 +41,7 @@ extern "C" {
 
 #define UMNN_MAX_LINEAR 8            /* Linear layers in the integrand MLP (hidden layers + 1) */
 #define UMNN_MAX_HIDDEN_WIDTH 127    /* widest hidden layer the LDS-resident kernels accept */
+#define UMNN_MAX_OUTPUTS 16          /* widest output layer of the multi-output entry points (umnn_cc_forward_multi) */
 
 #define UMNN_ACT_LEAKY_RELU 0        /* nn.LeakyReLU(0.01): IntegrandNetwork, UMNNMAF.py:247 */
 #define UMNN_ACT_RELU 1              /* nn.ReLU: IntegrandNN, MonotonicNN.py:20 */
@@ -53,7 +54,7 @@ extern "C" {
 
 typedef struct umnn_mlp {
     int n_linear;                         /* number of Linear layers */
-    int widths[UMNN_MAX_LINEAR + 1];      /* [1+E, H1, ..., HL, 1] */
+    int widths[UMNN_MAX_LINEAR + 1];      /* [1+E, H1, ..., HL, 1]  (last entry K = 2..UMNN_MAX_OUTPUTS for the *_multi entry points only) */
     const float* W[UMNN_MAX_LINEAR];      /* device pointers */
     const float* b[UMNN_MAX_LINEAR];
     int hidden_act;                       /* UMNN_ACT_* */
@@ -228,6 +229,25 @@ int umnn_cc_backward(const umnn_mlp* net, const float* x0, const float* x, const
                      float* dx0, float* dx, float* dh, float* dtheta,
                      void* workspace, long long workspace_bytes, void* stream);
 long long umnn_cc_backward_workspace_bytes(const umnn_mlp* net, long long B, int d, int E);
+
+/* Multi-output quadrature (cc_multi.hip): K = net->widths[n_linear] in [2, UMNN_MAX_OUTPUTS] integrands f_k(t; h) that share every
+ * hidden layer -- the last Linear is W_L [K, H_L], b_L [K], the output activation is applied per component -- integrated in ONE
+ * launch: F[b,i,k] = int_{x0}^{x} f_k(t; h[b,:,i]) dt.  F, f_x, f_x0 and g are [B, d, K], k minor.  Exact fp32 MFMA and fp32
+ * storage whatever umnn_set_forward_precision / umnn_set_backward_precision say.  x0, f_x, f_x0 and every gradient output may
+ * be NULL as in the single-output entries; B == 0 returns 0.  The backward has the reference's convention summed over k:
+ *   dx[b,i] = sum_k g_k f_k(x), dx0[b,i] = -sum_k g_k f_k(x0)   (f itself under inv_f too, like umnn_cc_backward_io);
+ *   dtheta  flat in parameters() order, W_L as [K, H_L] and b_L as [K]; OVERWRITTEN;  dh [B, E*d].
+ * There is no g_fx input: the f_x output belongs to the flow blocks, which stay single-output.  No float atomics: two runs are
+ * bit-identical.  UMNN_EUNSUPPORTED when the weight images of the net exceed the LDS.  Every other entry point keeps rejecting
+ * widths[n_linear] != 1. */
+int umnn_cc_forward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h,
+                          const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
+                          float* F, float* f_x, float* f_x0, void* stream);
+int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
+                           const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
+                           float* dx0, float* dx, float* dh, float* dtheta,
+                           void* workspace, long long workspace_bytes, void* stream);
+long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E);
 
 /* Training forward / backward pair for nets of the three-stage backward family (first hidden layer of 5..8 sixteen-feature tiles
  * over 2..4 narrower ones: MNISTExperiment's 31-100-50-50-50-50-1, /root/reference MNISTExperiment.py:238).  That backward recomputes

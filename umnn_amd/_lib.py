@@ -11,6 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("UMNN_CC_LIB") or os.path.join(_HERE, "libumnn_cc.so")     # (override: A/B runs of two builds)
 
 MAX_LINEAR = 8
+MAX_OUTPUTS = 16           # UMNN_MAX_OUTPUTS: widest output layer of the *_multi entry points
 EINVAL, EUNSUPPORTED, ENODEVICE = -1, -2, -3
 ACT_LEAKY_RELU, ACT_RELU = 0, 1
 OUT_ELU_PLUS_ONE, OUT_SIGMOID = 0, 1
@@ -82,6 +83,11 @@ SIGNATURES = {
     "umnn_cc_backward": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                         _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),
+    "umnn_cc_forward_multi": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
+                                             _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
+    "umnn_cc_backward_multi": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
+                                              _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
+    "umnn_cc_backward_multi_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),
     "umnn_cc_tables_host": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float)]),
     "umnn_cc_forward_flops_per_integral": (ctypes.c_double, [ctypes.POINTER(MlpDesc), ctypes.c_int]),
@@ -207,7 +213,8 @@ def check(rc, what):
 def set_forward_precision(name):
     """'f16x3' (default: two fp16 pieces, three cross terms -- fp32-level accuracy at the cost of bf16x3; tile groups whose pieces
     overflow fp16's range are recomputed by the queued bf16x3 build), 'fp32' (exact fp32 MFMA), 'bf16x3' (bf16 split, 3 cross terms)
-    or 'bf16x6' (three bf16 pieces: fp32-level accuracy)."""
+    or 'bf16x6' (three bf16 pieces: fp32-level accuracy).  The multi-output kernels (umnn_cc_forward_multi / _backward_multi) are
+    exact fp32 whatever is set here or in ``set_backward_precision``."""
     check(lib().umnn_set_forward_precision(PRECISIONS[name]), "umnn_set_forward_precision")
 
 

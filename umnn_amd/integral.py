@@ -32,7 +32,7 @@ from torch.autograd.function import once_differentiable
 
 from . import _lib
 from ._common import _graph_mode, _ptr, _stream, traced_native_call  # noqa: F401  (the names are part of this module)
-from .nets import graph_spec, mlp_spec
+from .nets import graph_spec, mlp_spec, n_out_of, require_single
 from .quadrature import compute_cc_weights, device_tables
 
 _state = threading.local()           # per-thread: last path taken, force_generic nesting
@@ -87,7 +87,8 @@ def _desc(spec):
     """struct umnn_mlp for the current weights.  The weights are read live (optimizer steps / force_lipschitz write in
     place and are seen through the same pointers); the ctypes struct itself is rebuilt only when a pointer moved."""
     lins = spec.linears
-    key = tuple((lin.weight.data_ptr(), lin.bias.data_ptr()) for lin in lins) + (spec.hidden_act, spec.out_act)
+    # (out_features too: row 0 of a multi-output last layer -- monotonic.OutputRow -- starts at the pointer of the whole matrix)
+    key = tuple((lin.weight.data_ptr(), lin.bias.data_ptr(), lin.out_features) for lin in lins) + (spec.hidden_act, spec.out_act)
     slot = id(lins[0])
     hit = _desc_cache.get(slot)
     if hit is not None and hit[0] == key and hit[3] is lins[0]:
@@ -131,12 +132,47 @@ def _use_hip(spec, x, graph=False):
     return True
 
 
-def _hip_spec(integrand, x, graph=None):
+def _hip_spec(integrand, x, graph=None, multi=False, who="this operator"):
     """The MlpSpec of ``integrand`` when the HIP kernels take this call, else None: THE path decision, eager and recorded (there
-    from ``nets.graph_spec``, which writes no cache onto the module).  ``graph``: ``_graph_mode()``, for callers that ask per block."""
+    from ``nets.graph_spec``, which writes no cache onto the module).  ``graph``: ``_graph_mode()``, for callers that ask per block.
+    ``multi``: the caller integrates a multi-output spec (the quadrature operators); every other caller refuses one, by name
+    (``nets.require_single``), on every device.  Multi-output is defined for x [B,1] only: anything else raises here, on every path."""
     graph = _graph_mode() if graph is None else graph
     spec = graph_spec(integrand) if graph else mlp_spec(integrand)
-    return spec if _use_hip(spec, x, graph) else None
+    if not multi:
+        require_single(spec, who)
+    elif spec is not None and n_out_of(spec) > 1:
+        _check_multi_x(n_out_of(spec), x)
+    if not _use_hip(spec, x, graph):
+        return None
+    if n_out_of(spec) > 1 and not graph and not _multi_kernels_ok(spec):
+        return None                      # (recorded calls: the ops make this choice when they run)
+    return spec
+
+
+def _check_multi_x(n_out, x):
+    if x.dim() != 2 or x.shape[1] != 1:
+        raise RuntimeError(f"umnn_amd: a multi-output integrand (n_out = {n_out}) is integrated over x of shape [B, 1]; got "
+                           f"{tuple(x.shape)}.  Integrate the dimensions one by one, or use n_out = 1.")
+
+
+_multi_ok = {}
+
+
+def _multi_kernels_ok(spec):
+    """False (after a one-time notice) for multi-output nets whose weight images, output image and scratch exceed the LDS: the
+    library answers UMNN_EUNSUPPORTED and the quadrature runs on ATen, like the deep wide single-output nets' backward."""
+    key = tuple((m.in_features, m.out_features) for m in spec.linears)
+    ok = _multi_ok.get(key)
+    if ok is None:
+        desc, keep = _desc(spec)
+        nbytes = _lib.lib().umnn_cc_backward_multi_workspace_bytes(ctypes.byref(desc), 1, 1, spec.linears[0].in_features - 1)
+        ok = _multi_ok[key] = nbytes >= 0
+    if not ok:
+        _warn_once(("multi-aten", key),
+                   f"umnn_amd: no multi-output HIP kernel for integrand widths {[w for _, w in key]} "
+                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): integrating with the generic ATen quadrature on the GPU.")
+    return ok
 
 
 _bwd_kind = {}
@@ -225,6 +261,65 @@ def hip_forward(spec, x0, x, h, nb_steps, inv_f=False):
     if out_dtype != xd:                   # fp16 callers: fp32 inside, their dtype outside
         F, fx, fx0 = F.to(out_dtype), fx.to(out_dtype), fx0.to(out_dtype)
     return F, fx, fx0
+
+
+def hip_forward_multi(spec, x0, x, h, nb_steps, inv_f=False):
+    """Multi-output forward (umnn_cc_forward_multi): x [B,1], h [B,E] -> (F, f_x, f_x0), each [B, n_out] in x's dtype.  Exact fp32
+    kernels and fp32 storage whatever ``set_precision`` says; bf16 / fp16 callers are converted at the boundary."""
+    lib = _lib.lib()
+    K = n_out_of(spec)
+    _check_multi_x(K, x)
+    B, d, E = _shape(spec, x, h)
+    out_dtype = x.dtype
+    x, h, x0 = _f32c(x), _f32c(h), (None if x0 is None else _f32c(x0))
+    w, s = device_tables(nb_steps, x.device)
+    F, fx, fx0 = (torch.empty(B, K, device=x.device, dtype=torch.float32) for _ in range(3))
+    desc, keep = _desc(spec)
+    with torch.cuda.device(x.device):
+        rc = lib.umnn_cc_forward_multi(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps), B, d, E,
+                                       int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0), _stream(x.device))
+    _lib.check(rc, "umnn_cc_forward_multi")
+    _state.path = "hip"
+    if out_dtype != torch.float32:
+        F, fx, fx0 = F.to(out_dtype), fx.to(out_dtype), fx0.to(out_dtype)
+    return F, fx, fx0
+
+
+def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True), inv_f=False):
+    """Multi-output backward (umnn_cc_backward_multi) for the cotangent g [B, n_out] -> (dx0, dx, dh, dtheta_flat), None where
+    ``need`` is False: dx = sum_k g_k f_k(x) and dx0 = -sum_k g_k f_k(x0) are [B,1]; dtheta is flat in parameters() order with
+    the last layer as [n_out, H_L] / [n_out]."""
+    lib = _lib.lib()
+    K = n_out_of(spec)
+    _check_multi_x(K, x)
+    B, d, E = _shape(spec, x, h)
+    if g.shape != (B, K):
+        raise RuntimeError(f"umnn_amd: the cotangent of a multi-output integral has shape {tuple(g.shape)}; expected {(B, K)}")
+    x_dtype, h_dtype = x.dtype, h.dtype
+    x, h, g, x0 = _f32c(x), _f32c(h), _f32c(g), (None if x0 is None else _f32c(x0))
+    w, s = device_tables(nb_steps, x.device)
+    dx0 = torch.empty_like(x) if need[0] else None
+    dx = torch.empty_like(x) if need[1] else None
+    dh = torch.empty_like(h) if need[2] else None
+    n_params = sum(l.weight.numel() + l.bias.numel() for l in spec.linears)
+    dtheta = torch.empty(n_params, device=x.device, dtype=torch.float32) if need[3] else None
+    desc, keep = _desc(spec)
+    with torch.cuda.device(x.device):
+        nbytes = lib.umnn_cc_backward_multi_workspace_bytes(ctypes.byref(desc), B, d, E)
+        if nbytes < 0:
+            _lib.check(_lib.EUNSUPPORTED, "umnn_cc_backward_multi_workspace_bytes")
+        ws = torch.empty(max(int(nbytes), 4), device=x.device, dtype=torch.uint8)
+        rc = lib.umnn_cc_backward_multi(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(g), _ptr(w), _ptr(s), int(nb_steps),
+                                        B, d, E, int(bool(inv_f)), _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta),
+                                        _ptr(ws), int(nbytes), _stream(x.device))
+    _lib.check(rc, "umnn_cc_backward_multi")
+    _state.path = _last_backward["path"] = "hip"
+    if x_dtype != torch.float32:
+        dx0 = dx0.to(x_dtype) if dx0 is not None else None
+        dx = dx.to(x_dtype) if dx is not None else None
+    if h_dtype != torch.float32 and dh is not None:
+        dh = dh.to(h_dtype)
+    return dx0, dx, dh, dtheta
 
 
 # z_2 handed from the training forward to the backward (three-stage family): memory held from forward to backward.  Two caps: per
@@ -575,19 +670,26 @@ def _eval_chunk(integrand, x0, span, h, u):
 
 
 def aten_forward(integrand, x0, x, h, nb_steps, inv_f=False):
+    """[B,d] for an integrand that returns one value per (row, dimension); [B,K] for a multi-output integrand (K values per row,
+    x [B,1]): the CPU implementation of the multi-output feature."""
     w, s = device_tables(nb_steps, x.device)
     w, u = w.to(x.dtype), s.to(x.dtype) + 1
     span = x - x0
-    total = torch.zeros_like(x)
-    B = x.shape[0]
+    total = None
+    B, d = x.shape
     for a, b in _node_chunks(nb_steps, B, h.shape[1] + x.shape[1]):
         t, h_rep = _eval_chunk(integrand, x0, span, h, u[a:b])
         f = integrand(t, h_rep)
         if inv_f:
             f = 1 / f
-        total = total + (f.view(b - a, B, -1) * w[a:b].view(-1, 1, 1)).sum(0)
+        f = f.view(b - a, B, -1)
+        if total is None:
+            if f.shape[2] != d:
+                _check_multi_x(f.shape[2], x)
+            total = torch.zeros(B, f.shape[2], dtype=x.dtype, device=x.device)
+        total = total + (f * w[a:b].view(-1, 1, 1)).sum(0)
     _state.path = "aten"
-    return total * span / 2
+    return total * (span if total.shape[1] == d else span.expand(B, total.shape[1])) / 2
 
 
 def _pure(integrand):
@@ -596,6 +698,8 @@ def _pure(integrand):
     adapter, ``ops.pure_mlp``) as it is."""
     if isinstance(integrand, tuple):
         return integrand
+    if hasattr(integrand, "_umnn_pure"):          # (a module that is a VIEW of another's parameters: monotonic.OutputRow)
+        return integrand._umnn_pure()
     if isinstance(integrand, torch.nn.Module):
         names = [n for n, _ in integrand.named_parameters()]
         return (lambda ps, t, h: torch.func.functional_call(integrand, dict(zip(names, ps)), (t, h)),
@@ -614,8 +718,13 @@ def aten_vjp(integrand, x0, x, h, g, g_fx, nb_steps, inv_f=False, limits=True):
     w, u = w.to(x.dtype), s.to(x.dtype) + 1
     with torch.no_grad():
         span = x - x0
-        cot = g * span / 2
-        B = x.shape[0]
+        B, d = x.shape
+        multi = g.shape[1] != d          # g [B,K] of a multi-output integrand over x [B,1]: dx / dx0 are sums over k
+        if multi:
+            _check_multi_x(g.shape[1], x)
+            if g_fx is not None:
+                raise RuntimeError("umnn_amd: the f_x output belongs to the single-output operators (n_out = 1)")
+        cot = g * (span.expand(B, g.shape[1]) if multi else span) / 2
         d_params = [torch.zeros_like(p) for p in params]
         dh = torch.zeros_like(h)
         for a, e in _node_chunks(nb_steps, B, h.shape[1] + x.shape[1]):
@@ -640,6 +749,8 @@ def aten_vjp(integrand, x0, x, h, g, g_fx, nb_steps, inv_f=False, limits=True):
             dx = f(params, x, h) * g
         if limits:
             dx0 = -f(params, x0, h) * g
+        if multi and limits:
+            dx, dx0 = dx.sum(1, keepdim=True), dx0.sum(1, keepdim=True)
     _state.path = _last_backward["path"] = "aten"
     return dx0, dx, dh, (_flatten(d_params) if d_params else None)
 
@@ -654,7 +765,12 @@ def quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need=(True
     """The quadrature backward of every operator -> (dx0, dx, dh, dtheta_flat), None where ``need`` says so: the HIP kernels when
     ``spec`` (None: the forward ran on ATen) has a backward kernel, else ``aten_vjp`` on ``integrand``.  x0 None: lower limit 0."""
     need = (bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3]))
-    if spec is not None and _hip_backward_ok(spec, x, h):
+    if spec is not None and n_out_of(spec) > 1:
+        if g_fx is not None:
+            raise RuntimeError(f"umnn_amd: the f_x output belongs to the single-output operators; this integrand has n_out = {n_out_of(spec)}")
+        if _multi_kernels_ok(spec):
+            return hip_backward_multi(spec, x0, x, h, g, nb_steps, need, inv_f=inv_f)
+    elif spec is not None and _hip_backward_ok(spec, x, h):
         return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f=inv_f, z2_saved=z2_saved)
     out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
     return tuple(t if n else None for t, n in zip(out, need))
@@ -680,10 +796,13 @@ def spec_args(spec):
 
 
 def cc_forward(spec, x0, x, h, nb_steps, inv_f=False):
-    """-> (F, f_x).  Recorded: ``umnn::cc_forward``, differentiable through the op."""
+    """-> (F, f_x).  Recorded: ``umnn::cc_forward``, differentiable through the op.  A multi-output spec: (F, f_x) [B, n_out] of
+    ``hip_forward_multi`` / ``umnn::cc_forward_multi``."""
+    multi = n_out_of(spec) > 1
     if _graph_mode():
-        return torch.ops.umnn.cc_forward(x0, x, h, *spec_args(spec), int(nb_steps), bool(inv_f))
-    return hip_forward(spec, x0, x, h, nb_steps, inv_f)[:2]
+        op = torch.ops.umnn.cc_forward_multi if multi else torch.ops.umnn.cc_forward
+        return op(x0, x, h, *spec_args(spec), int(nb_steps), bool(inv_f))
+    return (hip_forward_multi if multi else hip_forward)(spec, x0, x, h, nb_steps, inv_f)[:2]
 
 
 def cc_forward_jac(spec, integrand, x0, x, h, nb_steps, no_graph):
@@ -910,7 +1029,7 @@ def integrate(x0, nb_steps, step_sizes, integrand, h, compute_grad=False, x_tot=
     (what the reference's backward consumes).  ``cc_weights``/``steps`` are accepted for signature parity; the
     tables are a pure function of nb_steps and come from the per-device cache."""
     x = x0 + nb_steps * step_sizes
-    spec = _hip_spec(integrand, x)
+    spec = _hip_spec(integrand, x, multi=True)
     if compute_grad:
         if spec is None:
             return aten_backward(integrand, x0, x, h, x_tot, nb_steps, inv_f)
@@ -937,7 +1056,10 @@ def _launch_backward(net, spec, integrand, x0, x, h, g, g_fx, nb_steps, need, in
     if not net:
         return quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need, inv_f)
     need = [bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3])]
-    out = torch.ops.umnn.cc_backward(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
+    if net[0][-1].shape[0] > 1:
+        out = torch.ops.umnn.cc_backward_multi(x0, x, h, g, *net, int(nb_steps), need, bool(inv_f))
+    else:
+        out = torch.ops.umnn.cc_backward(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
     return tuple(t if n else None for t, n in zip(out, need))
 
 
@@ -966,7 +1088,7 @@ def _saved(ctx, n):
 
 def _quad_forward(ctx, who, x0, x, integrand, h, nb_steps, inv_f, jac):
     """forward of the four quadrature operators -> (F, f_x or None).  ``jac``: the operator owns its f_x output (HIP path only)."""
-    spec = _hip_spec(integrand, x)
+    spec = _hip_spec(integrand, x, multi=not jac, who=who)
     if jac and spec is None:
         raise RuntimeError(f"{who} needs an MLP integrand on a GPU")
     ctx.nb_steps, ctx.inv_f, ctx.jac, ctx.x0_none = nb_steps, bool(inv_f), jac, x0 is None      # (x0 None: lower limit 0, nothing to save)
@@ -1068,7 +1190,7 @@ class InverseNeuralIntegral(torch.autograd.Function):
     @staticmethod
     def forward(ctx, t, integrand, flat_params, h, nb_steps=20, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False):
         lo, hi = float(x_range[0]), float(x_range[1])
-        spec = _hip_spec(integrand, t)
+        spec = _hip_spec(integrand, t, who="InverseNeuralIntegral")
         if spec is None:
             x, fx, status = aten_solve(integrand, h.detach(), t.detach(), nb_steps, lo, hi, tol, max_iter)
         elif _graph_mode():

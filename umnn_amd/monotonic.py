@@ -4,21 +4,73 @@ Mirrors models/UMNN/MonotonicNN.py:29-54 (constructor ``MonotonicNN(in_d, hidden
 ``forward(x, h)`` with x [B,1] and h [B,in_d-1], state_dict keys ``integrand.net.*`` / ``net.*``).  The integral is
 the same HIP kernel as the flow's (d = 1, E = in_d-1, ReLU hidden layers).
 
+``n_out=K`` (an extension of this package, last in the signature: the reference's positional arguments and, at ``n_out=1``, its
+state_dict shapes and results are untouched) makes it K monotone functions of the same x under the same covariates -- a CDF per
+class, one curve per risk -- that share every hidden layer of the integrand: ``forward`` returns [B, K], y_k = exp(s_k(h)) *
+int_0^x f_k(t;h) dt + o_k(h), the conditioner ending in 2K units (offsets first, log-scales after).  On GPU tensors the K
+integrals are ONE launch of the multi-output kernels (csrc/cc_multi.hip: exact fp32, whatever ``set_precision`` says).
+
 ``inverse(y, h)`` (an extension of this package: the reference has no such method) returns the x with forward(x, h) = y --
-quantile functions, inverse-CDF sampling, calibration maps -- by the in-kernel Newton solve, differentiable in y, h and every parameter.
+quantile functions, inverse-CDF sampling, calibration maps -- by the in-kernel Newton solve, differentiable in y, h and every parameter;
+``output=k`` picks the function to invert when ``n_out > 1``.
 """
 import torch
 import torch.nn as nn
+import torch.nn.functional as F
 
 from .integral import InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
-from .nets import IntegrandNN  # noqa: F401  (re-exported)
+from .nets import IntegrandNN, MlpSpec, TensorLinear, _spec_from_sequential  # noqa: F401  (IntegrandNN is re-exported)
+
+
+class OutputRow(nn.Module):
+    """Output k of a multi-output ``IntegrandNN`` as a single-output integrand: a VIEW -- the hidden layers themselves and row k of
+    the last layer (``W_L[k:k+1]``, ``b_L[k:k+1]``) -- so the existing single-output solve and backward kernels run on it unchanged.
+    It owns no parameters: ``row_params()`` are the tensors a gradient flows back through (into row k only), in the order of the flat
+    d_theta of its spec."""
+
+    def __init__(self, integrand, k):
+        super().__init__()
+        object.__setattr__(self, "base", integrand)           # (not a submodule: parameters() stays empty)
+        self.k = int(k)
+
+    def _linears(self):
+        return [m for m in self.base.net if isinstance(m, nn.Linear)]
+
+    def row_params(self):
+        lins, k = self._linears(), self.k
+        out = [p for lin in lins[:-1] for p in (lin.weight, lin.bias)]
+        return out + [lins[-1].weight[k:k + 1], lins[-1].bias[k:k + 1]]
+
+    @staticmethod
+    def _mlp(params, x, h):
+        a = torch.cat((x, h), 1)
+        n = len(params) // 2
+        for l in range(n):
+            a = F.linear(a, params[2 * l], params[2 * l + 1])
+            if l + 1 < n:
+                a = F.relu(a)
+        return F.elu(a) + 1.
+
+    def forward(self, x, h):
+        return self._mlp(self.row_params(), x, h)
+
+    def _umnn_pure(self):
+        return (lambda ps, t, h: self._mlp(ps, t, h)), [p.detach() for p in self.row_params()]
+
+    def _umnn_spec(self):
+        spec = _spec_from_sequential(self.base.net, plus_one_outside=True)
+        if spec is None:
+            return None
+        last, k = spec.linears[-1], self.k
+        return MlpSpec(spec.linears[:-1] + [TensorLinear(last.weight[k:k + 1], last.bias[k:k + 1])], spec.hidden_act, spec.out_act)
 
 
 class MonotonicNN(nn.Module):
-    def __init__(self, in_d, hidden_layers, nb_steps=50, dev="cpu"):
+    def __init__(self, in_d, hidden_layers, nb_steps=50, dev="cpu", n_out=1):
         super().__init__()
-        self.integrand = IntegrandNN(in_d, hidden_layers)
-        sizes = [in_d - 1] + list(hidden_layers) + [2]      # conditioner -> (offset, log-scale)
+        self.n_out = int(n_out)
+        self.integrand = IntegrandNN(in_d, hidden_layers, self.n_out)
+        sizes = [in_d - 1] + list(hidden_layers) + [2 * self.n_out]      # conditioner -> (offsets, log-scales)
         layers = []
         for i in range(len(sizes) - 1):
             layers.append(nn.Linear(sizes[i], sizes[i + 1]))
@@ -31,19 +83,33 @@ class MonotonicNN(nn.Module):
     def forward(self, x, h):
         x0 = torch.zeros_like(x)
         out = self.net(h)
-        offset, scaling = out[:, [0]], torch.exp(out[:, [1]])
+        if self.n_out == 1:
+            offset, scaling = out[:, [0]], torch.exp(out[:, [1]])
+        else:
+            offset, scaling = out[:, :self.n_out], torch.exp(out[:, self.n_out:])
         integral = ParallelNeuralIntegral.apply(x0, x, self.integrand, _flatten(self.integrand.parameters()), h,
                                                 self.nb_steps)
         return scaling * integral + offset
 
-    def inverse(self, y, h, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False):
-        """x [B,1] in ``x_range`` with ``forward(x, h) = y``: y is strictly increasing in x, so x is unique.  The residual is
+    def inverse(self, y, h, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False, output=0):
+        """x [B,1] in ``x_range`` with ``forward(x, h) = y`` (``forward(x, h)[:, output] = y`` when ``n_out > 1``): y is strictly
+        increasing in x, so x is unique.  The residual is
         driven to ``tol * max(1, |t|)`` on t = (y - o(h)) exp(-s(h)), the value the integral has to reach; a y outside the image
         of ``x_range`` returns the nearer endpoint.  Gradients reach y, h, the conditioner and the integrand (implicit-function
-        theorem: one backward launch).  ``return_info=True`` -> (x, f(x; h), status): the integrand at the solution
+        theorem: one backward launch; with ``n_out > 1`` the solve and its backward are the single-output kernels on row ``output`` of
+        the integrand's last layer, whose other rows get zero gradient).  ``return_info=True`` -> (x, f(x; h), status): the integrand at the solution
         (dy/dx = exp(s(h)) f) and an int32 word per row, evaluations used in the low 16 bits, above them
         ``umnn_amd.SOLVE_CLAMPED`` (ended on an endpoint), ``SOLVE_CAPPED`` (still running after ``max_iter``) and ``SOLVE_NONFINITE``."""
         out = self.net(h)
-        t = (y - out[:, [0]]) * torch.exp(-out[:, [1]])
-        return InverseNeuralIntegral.apply(t, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
-                                           x_range, tol, max_iter, return_info)
+        if self.n_out == 1:
+            if output != 0:
+                raise IndexError(f"MonotonicNN.inverse: output {output} of a model with n_out = 1")
+            t = (y - out[:, [0]]) * torch.exp(-out[:, [1]])
+            return InverseNeuralIntegral.apply(t, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
+                                               x_range, tol, max_iter, return_info)
+        k = int(output)
+        if not 0 <= k < self.n_out:
+            raise IndexError(f"MonotonicNN.inverse: output {output} of a model with n_out = {self.n_out}")
+        t = (y - out[:, [k]]) * torch.exp(-out[:, [self.n_out + k]])
+        row = OutputRow(self.integrand, k)
+        return InverseNeuralIntegral.apply(t, row, _flatten(row.row_params()), h, self.nb_steps, x_range, tol, max_iter, return_info)

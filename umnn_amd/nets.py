@@ -7,7 +7,13 @@ signatures, attribute names and ``state_dict`` keys (``net.{0,2,...}.{weight,bia
 ``mlp_spec(integrand)`` recognises an integrand whose arithmetic is "Linear -> (LeakyReLU(0.01)|ReLU) -> ... ->
 Linear -> (ELU+1|Sigmoid)" and returns what the C ABI needs; anything else (lambdas, custom modules) yields None
 and is integrated by the generic ATen quadrature in integral.py.
+
+The last Linear may have ``n_out`` = 1..16 outputs (``IntegrandNN(in_d, hidden, n_out=K)``, ``IntegrandNetwork(1, ..., nout=K)``):
+K monotone functions of the same x that share every hidden layer.  Only the quadrature operators and ``MonotonicNN`` integrate
+such a spec (one multi-output launch); every single-output consumer -- flow blocks, the f_x operators, the inverse and the
+sampling paths -- asks for its spec through ``single_spec``, which refuses it by name.
 """
+import warnings
 from collections import namedtuple
 
 import torch
@@ -115,9 +121,12 @@ class IntegrandNetwork(nn.Module):
 
 
 class IntegrandNN(nn.Module):
-    def __init__(self, in_d, hidden_layers):
+    def __init__(self, in_d, hidden_layers, n_out=1):
         super().__init__()
-        sizes = [in_d] + list(hidden_layers) + [1]
+        if int(n_out) < 1:
+            raise ValueError(f"IntegrandNN: n_out must be >= 1 (got {n_out})")
+        self.n_out = int(n_out)
+        sizes = [in_d] + list(hidden_layers) + [self.n_out]
         layers = []
         for i in range(len(sizes) - 1):
             layers.append(nn.Linear(sizes[i], sizes[i + 1]))
@@ -163,12 +172,48 @@ def _spec_from_sequential(seq, plus_one_outside):
                 out = _lib.OUT_SIGMOID
             else:
                 return None
-    if linears[-1].out_features != 1 or len(linears) > _lib.MAX_LINEAR:
+    if len(linears) > _lib.MAX_LINEAR:
+        return None
+    if linears[-1].out_features > MAX_OUTPUTS:
+        _notice_wide(linears[-1].out_features)
         return None
     for a, b in zip(linears, linears[1:]):
         if a.out_features != b.in_features or a.out_features > 127:
             return None
     return MlpSpec(linears, hidden, out)
+
+
+MAX_OUTPUTS = 16          # UMNN_MAX_OUTPUTS of include/umnn_cc.h: the output layer is one 16-row MFMA tile
+_noticed = set()
+
+
+def _notice_wide(n_out):
+    """Once per process: an integrand with more outputs than the multi-output kernels take is integrated by ATen."""
+    if torch.compiler.is_compiling() or "wide" in _noticed:
+        return
+    _noticed.add("wide")
+    warnings.warn(f"umnn_amd: the integrand has n_out = {n_out} outputs; the multi-output HIP kernels take at most {MAX_OUTPUTS} -> "
+                  "generic ATen quadrature.", RuntimeWarning, stacklevel=4)
+
+
+def n_out_of(spec):
+    """Output width of a spec: 1, or the K of a multi-output integrand."""
+    return spec.linears[-1].out_features
+
+
+def require_single(spec, who):
+    """``spec`` (or None) for a consumer whose kernels and formulas are single-output: a multi-output spec raises, by name, before
+    it can reach the C check or fall onto ATen."""
+    if spec is not None and n_out_of(spec) != 1:
+        raise RuntimeError(f"umnn_amd: {who} takes a single-output integrand; this one has n_out = {n_out_of(spec)}. "
+                           "Multi-output integrands are integrated by ParallelNeuralIntegral / NeuralIntegral / MonotonicNN only "
+                           "(MonotonicNN.inverse(..., output=k) inverts one output).")
+    return spec
+
+
+def single_spec(integrand, who):
+    """``mlp_spec`` for the single-output consumers (see ``require_single``)."""
+    return require_single(mlp_spec(integrand), who)
 
 
 def mlp_spec(integrand):

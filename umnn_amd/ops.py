@@ -3,6 +3,8 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
 
     umnn::cc_forward(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)
     umnn::cc_backward(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
+    umnn::cc_forward_multi(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)        x [B,1]; F, f_x [B, n_out]
+    umnn::cc_backward_multi(x0?, x, h, g, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::cc_solve_block(t, h, x_init?, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::flow_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, log_jac_in?) -> (z, log_jac, f_x)
@@ -55,9 +57,10 @@ def _check_tensor(op, name, t, x, shape, dtypes):
         _req(op, t.shape[i] == n, f"{name} has shape {tuple(t.shape)}; expected {tuple(shape)}")
 
 
-def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS):
+def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS, multi=False):
     """x [B,d] and h [B,E*d] on one CUDA device, W[] / b[] an integrand MLP the kernels take (the rules of
-    nets._spec_from_sequential) on that device.  -> (B, d)."""
+    nets._spec_from_sequential) on that device.  ``multi``: the multi-output ops -- a last layer of 2..16 outputs and x [B,1];
+    every other op takes exactly one output.  -> (B, d)."""
     _req(op, x.device.type == "cuda", f"x is on {x.device}; the HIP kernels need CUDA tensors")
     _req(op, x.dim() == 2, f"x has shape {tuple(x.shape)}; expected [B, d]")
     _req(op, x.dtype in x_dtypes, f"x has dtype {x.dtype}; expected {' or '.join(str(d) for d in x_dtypes)}")
@@ -75,7 +78,12 @@ def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_
             _req(op, w.shape[1] == W[l - 1].shape[0], f"layer {l} takes {w.shape[1]} inputs, layer {l - 1} gives {W[l - 1].shape[0]}")
         if l + 1 < len(W):
             _req(op, w.shape[0] <= 127, f"hidden layer {l} has {w.shape[0]} units; the kernels take at most 127")
-    _req(op, W[-1].shape[0] == 1, f"the integrand's last layer has {W[-1].shape[0]} outputs; expected 1")
+    if multi:
+        _req(op, 2 <= W[-1].shape[0] <= _lib.MAX_OUTPUTS,
+             f"the integrand's last layer has n_out = {W[-1].shape[0]} outputs; expected 2 to {_lib.MAX_OUTPUTS}")
+        _req(op, x.shape[1] == 1, f"x has shape {tuple(x.shape)}; a multi-output integrand is integrated over x [B, 1]")
+    else:
+        _req(op, W[-1].shape[0] == 1, f"the integrand's last layer has {W[-1].shape[0]} outputs; expected 1 (n_out = 1)")
     E = W[0].shape[1] - 1
     _req(op, E >= 1, "the integrand's first layer takes fewer than 2 inputs")
     B, d = x.shape
@@ -241,6 +249,105 @@ def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
             h.new_empty(h.shape) if need[2] else _empty(h),
             W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
 
+
+
+# ---------------------------------------------------------------------------------------------------------- multi-output quadrature
+def _check_cc_multi(op, x0, x, h, W, b, hidden_act, out_act, g=None):
+    B, d = _check_net(op, x, h, W, b, hidden_act, out_act, multi=True)
+    if x0 is not None:
+        _check_tensor(op, "x0", x0, x, (B, 1), _FLOATS)
+    if g is not None:
+        _check_tensor(op, "g", g, x, (B, W[-1].shape[0]), _FLOATS)
+
+
+def pure_mlp_multi(W, b, hidden_act, out_act):
+    """``pure_mlp`` for a multi-output integrand over x [B,1]: f(params, x, h) -> [B, n_out]."""
+    L = len(W)
+
+    def f(params, x, h):
+        a = torch.cat((x, h), 1)
+        for l in range(L):
+            a = F.linear(a, params[2 * l], params[2 * l + 1])
+            if l + 1 < L:
+                a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
+        return F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)
+
+    return f, [p.detach() for pair in zip(W, b) for p in pair]
+
+
+@torch.library.custom_op("umnn::cc_forward_multi", mutates_args=(), device_types="cuda")
+def cc_forward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
+                     nb_steps: int, inv_f: bool) -> tuple[Tensor, Tensor]:
+    """``integral.hip_forward_multi`` for an integrand given as tensors -> (F, f_x), each [B, n_out]; for the nets whose images
+    exceed the LDS (``integral._multi_kernels_ok``, decided here at run time) the ATen quadrature on ``pure_mlp_multi``."""
+    _check_cc_multi("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act)
+    spec = spec_from_tensors(W, b, hidden_act, out_act)
+    if _I._multi_kernels_ok(spec):
+        F_, fx, _ = _I.hip_forward_multi(spec, x0, x, h, nb_steps, inv_f)
+        return F_, fx
+    f, params = pure_mlp_multi(W, b, hidden_act, out_act)
+    with torch.no_grad():
+        xd, hd = x.detach(), h.detach()
+        x0d = torch.zeros_like(xd) if x0 is None else x0.detach()
+        return _I.aten_forward(lambda t, hh: f(params, t, hh), x0d, xd, hd, nb_steps, inv_f), f(params, xd, hd)
+
+
+@cc_forward_multi.register_fake
+def _(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
+    _check_cc_multi("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act)
+    shape = (x.shape[0], W[-1].shape[0])
+    return x.new_empty(shape), x.new_empty(shape)
+
+
+def _cc_forward_multi_setup(ctx, inputs, output):
+    x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f = inputs
+    ctx.mark_non_differentiable(output[1])         # (f_x is for inspection: the f_x operators are single-output)
+    ctx.meta = (hidden_act, out_act, nb_steps, inv_f, len(W), x0 is None)
+    ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
+
+
+def _cc_forward_multi_backward(ctx, gF, _gfx):
+    hidden_act, out_act, nb_steps, inv_f, L, x0_none = ctx.meta
+    saved = ctx.saved_tensors
+    x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
+    x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
+    nig = ctx.needs_input_grad
+    need = [bool(nig[0]) and not x0_none, bool(nig[1]), bool(nig[2]), any(nig[3]) or any(nig[4])]
+    dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward_multi(x0, x, h, gF.contiguous(), W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[3], nig[4])
+    return (dx0 if need[0] else None, dx if need[1] else None, dh if need[2] else None, gW, gb,
+            None, None, None, None)
+
+
+cc_forward_multi.register_autograd(_cc_forward_multi_backward, setup_context=_cc_forward_multi_setup)
+
+
+def _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc_multi("cc_backward_multi", x0, x, h, W, b, hidden_act, out_act, g)
+    _check_need("cc_backward_multi", need, 4)
+
+
+@torch.library.custom_op("umnn::cc_backward_multi", mutates_args=(), device_types="cuda")
+def cc_backward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, W: List[Tensor], b: List[Tensor],
+                      hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``integral.quadrature_backward`` of a multi-output integrand given as tensors: the multi-output HIP kernels, or -- decided
+    here at run time -- the one ATen backward on ``pure_mlp_multi``."""
+    _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
+    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp_multi(W, b, hidden_act, out_act), x0, x, h, g, None,
+                                 nb_steps, need, inv_f)
+    like = (x, x, h, W[0])
+    return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
+                 for i, (t, n, l) in enumerate(zip(out, need, like)))
+
+
+@cc_backward_multi.register_fake
+def _(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return (x.new_empty(x.shape) if (need[0] and x0 is not None) else _empty(x),
+            x.new_empty(x.shape) if need[1] else _empty(x),
+            h.new_empty(h.shape) if need[2] else _empty(h),
+            W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
 
 
 # ---------------------------------------------------------------------------------------------------------- inverse (Newton solve)
@@ -455,7 +562,7 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
     return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
 
 
-OPS = ("cc_forward", "cc_backward", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_backward_multi", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
 spec_args = _I.spec_args       # MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it

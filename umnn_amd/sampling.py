@@ -14,7 +14,7 @@ import torch
 
 from . import integral as _I
 from .made import ConditionnalMADE
-from .nets import mlp_spec
+from .nets import single_spec
 
 
 class Inverted(NamedTuple):
@@ -124,7 +124,7 @@ class LogJacSum:
 def _conditional_integral(block, cand, h_j):
     """int_0^cand f(t; h_j) dt for one dimension: cand [R,1], h_j [R,E] -> [R,1]."""
     integrand = block.net.parallel_nets
-    spec = mlp_spec(integrand)
+    spec = single_spec(integrand, "the flow inverse")
     if _I._use_hip(spec, cand):
         return _I.hip_forward(spec, None, cand, h_j, block.nb_steps)[0]
     with torch.no_grad():
@@ -192,7 +192,7 @@ def invert_newton(block, z, context, opts, lj=None):
     B, d = z.shape
     dev = z.device
     integrand = block.net.parallel_nets
-    spec = mlp_spec(integrand)
+    spec = single_spec(integrand, "the flow inverse")
     use_hip = _I._use_hip(spec, z)
     in_kernel = use_hip and z.dtype == torch.float32 and block.nb_steps >= 1 and B > 0 and block.solver in _I.SOLVERS
     with torch.no_grad():
@@ -247,7 +247,7 @@ def invert_jacobi(block, z, context, opts, lj=None):
     B, d = z.shape
     dev = z.device
     integrand = block.net.parallel_nets
-    spec = mlp_spec(integrand)
+    spec = single_spec(integrand, "the flow inverse")
     use_hip = _I._use_hip(spec, z) and block.nb_steps >= 1 and block.solver in _I.SOLVERS and z.dtype == torch.float32
     in_kernel = use_hip and B > 0
     max_sweeps = d if opts.max_sweeps is None else int(opts.max_sweeps)
@@ -336,7 +336,7 @@ def bracket_search(block, z, iter, context, conditioner):
     K = 10
     B, d = z.shape
     dev = z.device
-    spec = mlp_spec(block.net.parallel_nets)
+    spec = single_spec(block.net.parallel_nets, "the flow inverse")
     if (_I._use_hip(spec, z) and z.dtype == torch.float32 and block.nb_steps >= 1 and iter >= 1 and B > 0
             and block.solver in _I.SOLVERS):
         # d x (conditioner + ONE launch): the whole 10-way / `iter`-round search of a dimension runs inside the kernel
