@@ -27,27 +27,11 @@
 __device__ __forceinline__ void stage_rowmajor_images(const BwdArgs& a, float* lds, int tid, int nthreads) {
     const MlpDev& m = a.m;
     const int L = m.n_linear - 1;
-    for (int l = 1; l < L; ++l) {
-        const int Hin = m.width[l], Hout = m.width[l + 1];
-        // rows: only the 4*ks_in[l+1] features the next layer consumes are stored.  Fragment reads of the rows
-        // (and, for W^T fragments, columns) beyond that run into the following image / the zero-initialised
-        // scratch: finite values that only ever reach padding features, whose results are never consumed.
-        const int rows = 4 * m.ks_in[l + 1], LD = a.ld[l];
-        const float* __restrict__ W = m.W[l];
-        const float* __restrict__ b = m.b[l];
-        float* img = lds + a.roff[l];
-        for (int idx = tid; idx < rows * LD; idx += nthreads) {
-            const int fo = idx / LD, fi = idx - fo * LD;
-            float v = 0.f;
-            if (fo < Hout) {
-                if (fi < Hin) v = W[fo * Hin + fi];
-                else if (fi == Hin) v = b[fo];
-            } else if (fo == Hout && fi == Hin) {
-                v = 1.f;
-            }
-            img[idx] = v;
-        }
-    }
+    // rows: only the 4*ks_in[l+1] features the next layer consumes are stored.  Fragment reads of the rows
+    // (and, for W^T fragments, columns) beyond that run into the following image / the zero-initialised
+    // scratch: finite values that only ever reach padding features, whose results are never consumed.
+    for (int l = 1; l < L; ++l)
+        stage_rowmajor_image(lds + a.roff[l], m.W[l], m.b[l], 4 * m.ks_in[l + 1], a.ld[l], m.width[l], m.width[l + 1], true, tid, nthreads);
 }
 
 // out[t] = sum_s W-fragment(t, s) * in[s]   (forward orientation; image row = output feature)
@@ -82,16 +66,6 @@ __device__ __forceinline__ void layer_bwd(const float* wt, int LD, int ks, int t
                 if (KSC || t < to) out[t] = mfma16(wt[4 * s * LD + 16 * t], in[s >> 2][s & 3], out[t]);
         }
     }
-}
-
-template <int TMAX>
-__device__ __forceinline__ unsigned sign_bits(const f32x4 (&v)[TMAX]) {
-    unsigned bits = 0;
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bits |= (v[t][r] > 0.f ? 1u : 0u) << (4 * t + r);
-    return bits;
 }
 
 template <int TMAX, int NACC, bool EDGE, int KSC>
@@ -244,7 +218,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_kernel(const BwdArgs a) 
                 for (int t = 0; t < TMAX; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        ta[t][r] = w1x[t][r] * ((bits[1] >> (4 * t + r)) & 1u ? 1.f : slope);
+                        ta[t][r] = w1x[t][r] * act_grad_bits(bits[1], t, r, slope);
                 for (int l = 1; l < L; ++l) {
                     f32x4 tz[TMAX];
                     layer_fwd<TMAX, KSC>(lds + a.roff[l] + perm16(p) * a.ld[l] + g, a.ld[l], m.ks_in[l], m.t_out[l + 1], ta, tz);
@@ -252,7 +226,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_kernel(const BwdArgs a) 
                     for (int t = 0; t < TMAX; ++t)
 #pragma unroll
                         for (int r = 0; r < 4; ++r)
-                            ta[t][r] = (KSC || t < m.t_out[l + 1]) ? tz[t][r] * ((bits[l + 1] >> (4 * t + r)) & 1u ? 1.f : slope) : 0.f;
+                            ta[t][r] = (KSC || t < m.t_out[l + 1]) ? tz[t][r] * act_grad_bits(bits[l + 1], t, r, slope) : 0.f;
                 }
                 float ds = 0.f;
 #pragma unroll
@@ -272,7 +246,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_kernel(const BwdArgs a) 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     if (EDGE) dwo[t][r] = fmaf(dout, act[t][r], dwo[t][r]);
-                    delta[t][r] = dout * wout[t][r] * ((bits[L] >> (4 * t + r)) & 1u ? 1.f : slope);
+                    delta[t][r] = dout * wout[t][r] * act_grad_bits(bits[L], t, r, slope);
                 }
             for (int l = L - 1; l >= 1; --l) {
                 // dW_l += delta_{l+1} (x) a_l  (contract over the 16 points through the LDS transpose)
@@ -308,7 +282,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_kernel(const BwdArgs a) 
                 for (int t = 0; t < TMAX; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r)
-                        delta[t][r] = (KSC || t < m.t_out[l]) ? nd[t][r] * ((bits[l] >> (4 * t + r)) & 1u ? 1.f : slope) : 0.f;
+                        delta[t][r] = (KSC || t < m.t_out[l]) ? nd[t][r] * act_grad_bits(bits[l], t, r, slope) : 0.f;
             }
             if (EDGE) {
 #pragma unroll
@@ -601,6 +575,16 @@ typedef void (*bwd_kernel_t)(const BwdArgs);
 static const bwd_kernel_t kBwdFp32Kernels[] = { UMNN_BWD_FP32_VARIANTS(BWD_FP32_KERNEL) };
 static_assert(sizeof(kBwdFp32Kernels) / sizeof(kBwdFp32Kernels[0]) == kBwdFp32Count, "one kernel per variant");
 
+// d_h through cc_bwd_dh_kernel (cc_host.h: the multi-output backward finishes with it too).  Notes no launch: that is the caller's.
+int umnn_launch_bwd_dh(const float* dc, const float* W0, float* dh, long long NI, int d, int E, int H1, int h_bf16, hipStream_t stream) {
+    const int qpb = NI / 64 < 2LL * umnn_num_cus() ? 16 : 64;      // integrals per workgroup
+    const size_t sm = ((size_t)H1 * E + qpb * (H1 + 1)) * sizeof(float);
+    const unsigned nb = (unsigned)((NI + qpb - 1) / qpb);
+    if (int rc = umnn_allow_lds((const void*)cc_bwd_dh_kernel, sm)) return rc;
+    hipLaunchKernelGGL(cc_bwd_dh_kernel, dim3(nb), dim3(256), sm, stream, dc, W0, dh, NI, d, E, H1, qpb, h_bf16);
+    return 0;
+}
+
 static BwdOptions bwd_options() {
     const UmnnOptions& o = umnn_options();
     return BwdOptions{o.bwd_precision, o.bwd_ws, o.bwd_ws16, o.bwd_swp, o.bwd_ns, o.front_bwd2};
@@ -778,12 +762,8 @@ static int backward_impl(const umnn_mlp* net, const umnn_io* io, const void* x0_
             hipLaunchKernelGGL(cc_bwd_dh_mfma_kernel, dim3(nb), dim3(256), sm, stream, a.dc, net->W[0], dh, a.NI, d, E, H1, a.h_bf16);
             umnn_note_launch("cc_bwd_dh<mfma>");
         } else {
-        const int qpb = a.NI / 64 < 2LL * umnn_num_cus() ? 16 : 64;      // integrals per workgroup
-        const size_t sm = ((size_t)H1 * E + qpb * (H1 + 1)) * sizeof(float);
-        const unsigned nb = (unsigned)((a.NI + qpb - 1) / qpb);
-        if (int rc = umnn_allow_lds((const void*)cc_bwd_dh_kernel, sm)) return rc;
-        hipLaunchKernelGGL(cc_bwd_dh_kernel, dim3(nb), dim3(256), sm, stream, a.dc, net->W[0], dh, a.NI, d, E, H1, qpb, a.h_bf16);
-        umnn_note_launch("cc_bwd_dh");
+            if (int rc = umnn_launch_bwd_dh(a.dc, net->W[0], dh, a.NI, d, E, H1, a.h_bf16, stream)) return rc;
+            umnn_note_launch("cc_bwd_dh");
         }
     }
     if (dtheta) {

@@ -262,13 +262,8 @@ inline const char* bwd_plan_net(BwdShapePlan* pl, const MlpDev& m0, int tmax0, i
 inline const char* bwd_plan_shape(BwdShapePlan* pl, const MlpDev& m0, int tmax0, int ksu0, long long B, int d, int E, int cus, int bwd_ns) {
     if (const char* err = bwd_plan_net(pl, m0, tmax0, ksu0)) return err;
     BwdArgs& a = pl->a;
-    const int L = a.m.n_linear - 1, H1 = a.m.width[1];
-    int po = 0;
-    for (int l = 0; l <= L; ++l) {
-        a.poffW[l] = po; po += a.m.width[l + 1] * a.m.width[l];
-        a.poffb[l] = po; po += a.m.width[l + 1];
-    }
-    a.n_params = po;
+    const int H1 = a.m.width[1];
+    a.n_params = bwd_param_offsets(a.m, a.poffW, a.poffb);
     a.NI = B * (long long)d; a.d = d; a.E = E;
     a.ngroups = (unsigned)((a.NI + 15) / 16);
     // fewer tiles than waves (the reference's own training batches are 100 samples): share a tile's nodes among

@@ -44,6 +44,10 @@ int umnn_allow_lds(const void* fn, size_t bytes);         // hipFuncSetAttribute
 void umnn_note_launch(const char* kernel_name);
 void umnn_note_made_launch(const char* kernel_name);      // conditioner kernels: separate counter / name
 long long umnn_param_count(const umnn_mlp* net);
+// d_h[b, e d + i] = sum_f W1[f][1 + e] dc[q][f] for every integral q = b d + i: the simple finishing kernel of cc_backward.hip
+// (16 or 64 integrals per workgroup), shared with cc_multi.hip.  dh: fp32, or bf16 when h_bf16.  Launches only: no profiling
+// bracket, no umnn_note_launch.  Returns 0, or the error of umnn_allow_lds.
+int umnn_launch_bwd_dh(const float* dc, const float* W0, float* dh, long long NI, int d, int E, int H1, int h_bf16, hipStream_t stream);
 
 // Optional per-launch timing (umnn_profile_enable): hipEvents recorded on the launch stream around each kernel.
 void umnn_prof_begin(hipStream_t stream);

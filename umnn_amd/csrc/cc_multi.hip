@@ -20,9 +20,17 @@
 // by a last kernel in a fixed order: no float atomics, two runs are bit-identical.  New at the output layer: dout_k =
 // g_k (x - x0)/2 w_j out'(s_k) (times -1/f_k^2 under inv_f), delta_L = act'(z_L) * W_L^T dout (four K-steps against the
 // transposed output image), dW_L / db_L += dout (x) [a_L, 1] through the same LDS trip.
+//
+// Shared with cc_bwd_kernel (cc_backward.hip), in cc_bwd_shared.h: the row-major image staging, perm16, sign_bits / act_grad_bits
+// (the kink convention), the theta offsets and the launch bracket of a pass; d_h is cc_backward.hip's cc_bwd_dh_kernel
+// (umnn_launch_bwd_dh).  Still a copy of cc_bwd_kernel's text, to be changed in both files together: the first-layer hoist, the
+// K-step loops of a layer, parking a tile in the transpose scratch with the dW accumulation, and the d_theta slice write -- as
+// shared helpers they re-scheduled the node loop (profiles/multi_shared/).  Own to this file: the output tile and its dW_L, the
+// x-column in LDS, the pass plan, and the simple dW_1 / reduction kernels (their sums run in another order than
+// cc_backward.hip's, and their workspace layout is this file's).
 #include <cstring>
 
-#include "cc_host.h"
+#include "cc_bwd_shared.h"
 
 struct MultiFamily { int T, KS; };
 // (T tiles, KS K-steps per hidden layer): the smallest that holds the widest hidden layer (H + 1 features with the constant one)
@@ -55,8 +63,6 @@ struct MultiArgs {
     int scratch_off, scratch_per_wave, l_lo, n_params;
     int outw;                       // backward: this pass accumulates the output layer's dW_L / db_L (OUTW variants only)
 };
-
-__device__ __forceinline__ int perm16m(int rho) { return 4 * (rho & 3) + (rho >> 2); }
 
 // ------------------------------------------------------------------------------------------ forward
 template <int TMAX, int KSC, int P>
@@ -237,48 +243,10 @@ __device__ __forceinline__ void stage_multi_rowmajor(const MultiArgs& a, float* 
     const int L = m.n_linear - 1;
     // hidden images: the `rows` features the next layer consumes.  Fragment reads of the rows (W^T fragments: columns) beyond
     // that run into the following image / the zero-initialised scratch: finite values that only ever reach padding features.
-    for (int l = 1; l < L; ++l) {
-        const int Hin = m.width[l], Hout = m.width[l + 1], LD = a.ld[l];
-        const float* __restrict__ W = m.W[l];
-        const float* __restrict__ b = m.b[l];
-        float* img = lds + a.roff[l];
-        for (int idx = tid; idx < rows * LD; idx += nthreads) {
-            const int fo = idx / LD, fi = idx - fo * LD;
-            float v = 0.f;
-            if (fo < Hout) {
-                if (fi < Hin) v = W[fo * Hin + fi];
-                else if (fi == Hin) v = b[fo];
-            } else if (fo == Hout && fi == Hin) {
-                v = 1.f;
-            }
-            img[idx] = v;
-        }
-    }
-    {   // the output image: 16 rows, row k = [W_L[k][:], b_L[k], 0...] for k < K, zero above
-        const int HL = m.width[L], LD = a.ld[L], K = a.K;
-        const float* __restrict__ W = m.W[L];
-        const float* __restrict__ b = m.b[L];
-        float* img = lds + a.roff[L];
-        for (int idx = tid; idx < 16 * LD; idx += nthreads) {
-            const int k = idx / LD, fi = idx - k * LD;
-            float v = 0.f;
-            if (k < K) {
-                if (fi < HL) v = W[k * HL + fi];
-                else if (fi == HL) v = b[k];
-            }
-            img[idx] = v;
-        }
-    }
-}
-
-template <int TMAX>
-__device__ __forceinline__ unsigned multi_sign_bits(const f32x4 (&v)[TMAX]) {
-    unsigned bits = 0;
-#pragma unroll
-    for (int t = 0; t < TMAX; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) bits |= (v[t][r] > 0.f ? 1u : 0u) << (4 * t + r);
-    return bits;
+    for (int l = 1; l < L; ++l)
+        stage_rowmajor_image(lds + a.roff[l], m.W[l], m.b[l], rows, a.ld[l], m.width[l], m.width[l + 1], true, tid, nthreads);
+    // the output image: 16 rows, row k = [W_L[k][:], b_L[k], 0...] for k < K, zero above (no constant-one row: nothing consumes it)
+    stage_rowmajor_image(lds + a.roff[L], m.W[L], m.b[L], 16, a.ld[L], m.width[L], a.K, false, tid, nthreads);
 }
 
 // NACC: hidden images whose dW this pass accumulates (layers l_lo .. l_lo + NACC - 1).  EDGE: the pass that owns what exists
@@ -313,8 +281,8 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
     const float* w1x = lds + a.w1x_off + g;        // first-layer x-column of feature 16t + 4r + g: read per node, not held
     const bool outw = OUTW && a.outw;
     const int ldO = a.ld[L];
-    const float* oimg_f = lds + a.roff[L] + perm16m(p) * ldO + g;      // forward fragments of the output image
-    const float* oimg_b = lds + a.roff[L] + g * ldO + perm16m(p);      // W_L^T fragments
+    const float* oimg_f = lds + a.roff[L] + perm16(p) * ldO + g;       // forward fragments of the output image
+    const float* oimg_b = lds + a.roff[L] + g * ldO + perm16(p);       // W_L^T fragments
 
     f32x4 dW[NA][TMAX][TMAX];
 #pragma unroll
@@ -386,7 +354,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
             for (int t = 0; t < TMAX; ++t)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) act[t][r] = hidden_act_f(fmaf(w1x[16 * t + 4 * r], tk, c[t][r]), slope);
-            bits[1] = multi_sign_bits<TMAX>(act);
+            bits[1] = sign_bits<TMAX>(act);
             for (int l = 1; l < L; ++l) {
 #pragma unroll
                 for (int j = 0; j < NACC; ++j)
@@ -397,7 +365,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                             for (int r = 0; r < 4; ++r) scratch[j * (TMAX * 256) + (16 * t + 4 * r) * 16 + wr_off] = act[t][r];
                     }
                 const int LD = a.ld[l];
-                const float* wf = lds + a.roff[l] + perm16m(p) * LD + g;
+                const float* wf = lds + a.roff[l] + perm16(p) * LD + g;
                 f32x4 acc[TMAX];
 #pragma unroll
                 for (int t = 0; t < TMAX; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -409,7 +377,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                 for (int t = 0; t < TMAX; ++t)
 #pragma unroll
                     for (int r = 0; r < 4; ++r) act[t][r] = hidden_act_f(acc[t][r], slope);
-                bits[l + 1] = multi_sign_bits<TMAX>(act);
+                bits[l + 1] = sign_bits<TMAX>(act);
             }
             // the output tile
             f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -456,7 +424,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
 #pragma unroll
                 for (int t = 0; t < TMAX; ++t)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) delta[t][r] = nd[t][r] * ((bits[L] >> (4 * t + r)) & 1u ? 1.f : slope);
+                    for (int r = 0; r < 4; ++r) delta[t][r] = nd[t][r] * act_grad_bits(bits[L], t, r, slope);
             }
             for (int l = L - 1; l >= 1; --l) {
                 // dW_l += delta_{l+1} (x) a_l  (contract over the 16 points through the LDS transpose)
@@ -482,7 +450,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                     }
                 // delta_l = (W_l^T delta_{l+1}) * act'(z_l)
                 const int LD = a.ld[l];
-                const float* wt = lds + a.roff[l] + g * LD + perm16m(p);
+                const float* wt = lds + a.roff[l] + g * LD + perm16(p);
                 f32x4 nd[TMAX];
 #pragma unroll
                 for (int t = 0; t < TMAX; ++t) nd[t] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -493,7 +461,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
 #pragma unroll
                 for (int t = 0; t < TMAX; ++t)
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) delta[t][r] = nd[t][r] * ((bits[l] >> (4 * t + r)) & 1u ? 1.f : slope);
+                    for (int r = 0; r < 4; ++r) delta[t][r] = nd[t][r] * act_grad_bits(bits[l], t, r, slope);
             }
             if (EDGE) {
 #pragma unroll
@@ -576,31 +544,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
     }
 }
 
-// ---- finishing kernels -------------------------------------------------------------------------------------------------
-// d_h[b, e*d+i] = sum_f W1[f][1+e] dc[q][f]
-__global__ __launch_bounds__(256) void cc_bwd_multi_dh_kernel(const float* __restrict__ dc, const float* __restrict__ W0,
-                                                              float* __restrict__ dh, long long NI, int d, int E, int H1, int qpb) {
-    extern __shared__ __attribute__((aligned(16))) float sm[];
-    float* sW = sm;                       // [H1][E]
-    float* sdc = sm + H1 * E;             // [qpb][H1+1]
-    const int tid = threadIdx.x;
-    for (int i = tid; i < H1 * E; i += 256) { const int f = i / E, e = i - f * E; sW[i] = W0[f * (1 + E) + 1 + e]; }
-    const long long q0 = (long long)blockIdx.x * qpb;
-    const int nq = (int)min((long long)qpb, NI - q0);
-    for (int i = tid; i < nq * H1; i += 256) {
-        const int ql = i / H1, f = i - ql * H1;
-        sdc[ql * (H1 + 1) + f] = dc[q0 * H1 + i];
-    }
-    __syncthreads();
-    for (int o = tid; o < nq * E; o += 256) {
-        const int e = o / nq, ql = o - e * nq;
-        float s = 0.f;
-        for (int f = 0; f < H1; ++f) s = fmaf(sW[f * E + e], sdc[ql * (H1 + 1) + f], s);
-        const long long q = q0 + ql, bi = q / d;
-        dh[bi * ((long long)E * d) + (long long)e * d + (q - bi * d)] = s;
-    }
-}
-
+// ---- finishing kernels (d_h: cc_bwd_dh_kernel of cc_backward.hip, through umnn_launch_bwd_dh) ---------------------------
 // p0[blk][f][e] = sum_{q in the block's range} dc[q][f] * hext[q][e],  hext[q][E] = 1   (-> dW_1[:, 1:], db_1).  A block owns
 // `per` consecutive integrals and a thread one output at a time; fixed summation order.
 __global__ __launch_bounds__(256) void cc_bwd_multi_dw0_kernel(const float* __restrict__ dc, const float* __restrict__ h,
@@ -752,12 +696,7 @@ static int multi_plan(const umnn_mlp* net, int E, MultiPlan* pl) {
     a.ld[L] = multi_ld(cols); a.roff[L] = ro; ro += 16 * a.ld[L]; ro = (ro + 3) & ~3;
     a.w1x_off = ro; ro += 16 * pl->T;
     a.scratch_off = ro;
-    int po = 0;
-    for (int l = 0; l <= L; ++l) {
-        a.poffW[l] = po; po += m.width[l + 1] * m.width[l];
-        a.poffb[l] = po; po += m.width[l + 1];
-    }
-    a.n_params = po;
+    a.n_params = bwd_param_offsets(m, a.poffW, a.poffb);
     // every pass writes its entries of the same d_theta slices, so all passes run the same waves: sized for the largest scratch
     const int nacc_max = pl->T <= 4 ? 3 : 1;
     pl->wpb = 4;
@@ -865,21 +804,13 @@ extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, cons
         a.scratch_per_wave = multi_scratch_per_wave(pl.T, v->nacc);
         const size_t lds = multi_bwd_lds(pl, v->nacc, wpb);
         if (int rc = umnn_allow_lds((const void*)v->fn, lds)) return rc;
-        umnn_prof_begin(stream);
-        hipLaunchKernelGGL(v->fn, dim3(nblocks), dim3(64 * wpb), lds, stream, a);
-        umnn_prof_end(stream, pass == 0 ? 3.0 * umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI : 0.0, UMNN_PROF_BACKWARD);
-        umnn_note_launch(v->name);
-        if (int rc = umnn_check(hipGetLastError(), "cc_bwd_multi launch")) return rc;
+        if (int rc = umnn_bwd_launch(stream, pass == 0 ? umnn_bwd_flops(net, nb_steps, a.NI) : 0.0, v->name, "cc_bwd_multi launch",
+                                     [&] { hipLaunchKernelGGL(v->fn, dim3(nblocks), dim3(64 * wpb), lds, stream, a); })) return rc;
     }
 
     // ---- finishing kernels
-    if (dh) {
-        const int qpb = a.NI / 64 < 2LL * cus ? 16 : 64;
-        const size_t sm = ((size_t)H1 * E + qpb * (H1 + 1)) * sizeof(float);
-        const unsigned nbh = (unsigned)((a.NI + qpb - 1) / qpb);
-        if (int rc = umnn_allow_lds((const void*)cc_bwd_multi_dh_kernel, sm)) return rc;
-        hipLaunchKernelGGL(cc_bwd_multi_dh_kernel, dim3(nbh), dim3(256), sm, stream, a.dc, net->W[0], dh, a.NI, d, E, H1, qpb);
-    }
+    if (dh)
+        if (int rc = umnn_launch_bwd_dh(a.dc, net->W[0], dh, a.NI, d, E, H1, 0, stream)) return rc;
     if (dtheta) {
         const long long np0 = multi_nparts0(a.NI), per = (a.NI + np0 - 1) / np0;
         const int nparts0 = (int)((a.NI + per - 1) / per);
