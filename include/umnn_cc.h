@@ -237,9 +237,14 @@ long long umnn_cc_backward_workspace_bytes(const umnn_mlp* net, long long B, int
  * be NULL as in the single-output entries; B == 0 returns 0.  The backward has the reference's convention summed over k:
  *   dx[b,i] = sum_k g_k f_k(x), dx0[b,i] = -sum_k g_k f_k(x0)   (f itself under inv_f too, like umnn_cc_backward_io);
  *   dtheta  flat in parameters() order, W_L as [K, H_L] and b_L as [K]; OVERWRITTEN;  dh [B, E*d].
- * There is no g_fx input: the f_x output belongs to the flow blocks, which stay single-output.  No float atomics: two runs are
- * bit-identical.  UMNN_EUNSUPPORTED when the weight images of the net exceed the LDS.  Every other entry point keeps rejecting
- * widths[n_linear] != 1. */
+ * umnn_cc_backward_multi_fx also takes g_fx [B, d, K] (k minor; may be NULL), the cotangent of f_x[b,i,k] = f_k(x; h) -- f itself,
+ * also under inv_f, like umnn_cc_backward_io's: the output layer's cotangent at node x gains g_fx,k out'(s_k), which reaches dh and
+ * dtheta through the same sweep, and
+ *   dx[b,i] = sum_k g_k f_k(x) + sum_k g_fx,k df_k/dx (x).
+ * Same workspace (umnn_cc_backward_multi_workspace_bytes), argument checks and launch notes; umnn_cc_backward_multi is that call
+ * with g_fx = NULL and runs the kernels it always ran (a g_fx selects builds of the same passes that carry it).  No float
+ * atomics: two runs are bit-identical.  UMNN_EUNSUPPORTED when the weight images of the net exceed the LDS.  Every other entry
+ * point keeps rejecting widths[n_linear] != 1. */
 int umnn_cc_forward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h,
                           const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
                           float* F, float* f_x, float* f_x0, void* stream);
@@ -247,6 +252,9 @@ int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, const float* x,
                            const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
                            float* dx0, float* dx, float* dh, float* dtheta,
                            void* workspace, long long workspace_bytes, void* stream);
+int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g, const float* g_fx,
+                              const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
+                              float* dx0, float* dx, float* dh, float* dtheta, void* workspace, long long workspace_bytes, void* stream);
 long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E);
 
 /* Training forward / backward pair for nets of the three-stage backward family (first hidden layer of 5..8 sixteen-feature tiles

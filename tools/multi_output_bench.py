@@ -17,6 +17,17 @@ says whether multi is below the K fp32 launches (median against median) and give
 compares each column against its single-output fp32 launch (``rel_err`` = max |a - b| / max(|b|, 1), bound 1e-5) and the summed
 d_x / d_h of the K single backward launches against the multi backward.  Run the command twice to see the spread; kernel times are
 a separate run:  rocprofv3 --kernel-trace --stats -d DIR -- python tools/multi_output_bench.py --reps 2 --warmup 1 --only-k 4
+
+``--derivative`` times the differentiable pair (y, dy/dx) instead, forward + backward with d_x, d_h and d_theta, per K:
+
+    pair           the multi-output forward and the backward with both cotangents (g, g_fx): umnn_cc_backward_multi_fx
+    g_only         the same forward and the backward with g alone (the kernels without g_fx)
+    two_eval       what one writes without the pair: g_only plus a second evaluation of f(x; h) in ATen, differentiated by autograd
+
+and, through the C entries themselves with every buffer allocated once, ``abi_g_only`` twice in every round (``_a`` and ``_b``: their
+medians differ by the run-to-run spread of this session) and -- with ``--root DIR``, a built checkout of another commit --
+``abi_g_only_root`` on DIR/umnn_amd/libumnn_cc.so, alternating with them.  A ``derivative`` line per K gives pair / g_only against the
+node count (n + 2) / (n + 1) of the first backward pass, pair / two_eval, the spread and root / new.
 """
 import argparse
 import json
@@ -34,6 +45,8 @@ def main():
     ap.add_argument("--only-k", default="2,4,16")
     ap.add_argument("--out", default=None)
     ap.add_argument("--label", default="")
+    ap.add_argument("--derivative", action="store_true")
+    ap.add_argument("--root", default=None)
     args = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
@@ -66,7 +79,10 @@ def main():
 
     n, B = args.nb_steps, args.rows
     need = (False, True, True, True)
-    for K in [int(k) for k in args.only_k.split(",")]:
+    if args.derivative:
+        derivative(args, emit, timed)
+        args.only_k = ""
+    for K in [int(k) for k in args.only_k.split(",") if k]:
         torch.manual_seed(K)
         m = umnn_amd.MonotonicNN(3, [100, 100, 100], nb_steps=n, n_out=K).to(dev)
         spec = mlp_spec(m.integrand)
@@ -148,6 +164,96 @@ def main():
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
         with open(args.out, "a") as f:
             f.write("\n".join(lines) + "\n")
+
+
+def derivative(args, emit, timed):
+    import ctypes
+    import torch
+    import umnn_amd
+    from umnn_amd import _lib, integral as I
+    from umnn_amd._common import _ptr, _stream
+    from umnn_amd.nets import mlp_spec
+    from umnn_amd.quadrature import device_tables
+
+    dev = torch.device("cuda:0")
+    n, B = args.nb_steps, args.rows
+    need = (False, True, True, True)
+    root = ctypes.CDLL(os.path.join(os.path.abspath(args.root), "umnn_amd", "libumnn_cc.so")) if args.root else None
+
+    for K in [int(k) for k in args.only_k.split(",")]:
+        torch.manual_seed(K)
+        m = umnn_amd.MonotonicNN(3, [100, 100, 100], nb_steps=n, n_out=K).to(dev)
+        spec = mlp_spec(m.integrand)
+        gen = torch.Generator(device="cpu").manual_seed(1000 + K)
+        x = (torch.randn(B, 1, generator=gen) * 2).to(dev)
+        h = torch.randn(B, 2, generator=gen).to(dev)
+        g = torch.randn(B, K, generator=gen).to(dev)
+        gfx = torch.randn(B, K, generator=gen).to(dev)
+        params = list(m.integrand.parameters())
+
+        def g_only():
+            I.hip_forward_multi(spec, None, x, h, n)
+            return I.hip_backward_multi(spec, None, x, h, g, n, need)
+
+        def pair():
+            I.hip_forward_multi(spec, None, x, h, n)
+            return I.hip_backward_multi(spec, None, x, h, g, n, need, g_fx=gfx)
+
+        def two_eval():
+            out = g_only()
+            with torch.enable_grad():
+                xr, hr = x.detach().requires_grad_(), h.detach().requires_grad_()
+                return out, torch.autograd.grad((m.integrand(xr, hr) * gfx).sum(), [xr, hr] + params)
+
+        def abi(handle):
+            for nm in ("umnn_cc_forward_multi", "umnn_cc_backward_multi", "umnn_cc_backward_multi_workspace_bytes"):
+                fn = getattr(handle, nm)
+                fn.restype, fn.argtypes = _lib.SIGNATURES[nm]
+            desc, keep = I._desc(spec)
+            w, s = device_tables(n, dev)
+            E = h.shape[1]
+            F, fx, dx, dh = (torch.empty(B, c, device=dev) for c in (K, K, 1, E))
+            dth = torch.empty(sum(p.numel() for p in params), device=dev)
+            nbytes = handle.umnn_cc_backward_multi_workspace_bytes(ctypes.byref(desc), B, 1, E)
+            ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+            held = (keep, w, s, F, fx, dx, dh, dth, ws)
+
+            def run(held=held):
+                st = _stream(dev)
+                rc = handle.umnn_cc_forward_multi(ctypes.byref(desc), None, _ptr(x), _ptr(h), _ptr(w), _ptr(s), n, B, 1, E, 0, _ptr(F), _ptr(fx), None, st)
+                rc |= handle.umnn_cc_backward_multi(ctypes.byref(desc), None, _ptr(x), _ptr(h), _ptr(g), _ptr(w), _ptr(s), n, B, 1, E, 0,
+                                                    None, _ptr(dx), _ptr(dh), _ptr(dth), _ptr(ws), nbytes, st)
+                assert rc == 0
+                return dx, dh, dth
+            return run
+
+        new_abi = abi(ctypes.CDLL(_lib.LIB_PATH))
+        variants = {"pair": pair, "g_only": g_only, "two_eval": two_eval, "abi_g_only_a": new_abi}
+        if root is not None:
+            variants["abi_g_only_root"] = abi(root)
+        variants["abi_g_only_b"] = new_abi
+        with torch.no_grad():
+            if root is not None:
+                a, b = [t.clone() for t in new_abi()], variants["abi_g_only_root"]()
+                emit({"kind": "root_check", "K": K, "bit_equal_dx_dh_dtheta": [bool(torch.equal(u, v)) for u, v in zip(a, b)]})
+            for fn in variants.values():
+                for _ in range(args.warmup):
+                    fn()
+            torch.cuda.synchronize()
+            times = {name: [] for name in variants}
+            for _ in range(args.reps):
+                for name, fn in variants.items():
+                    times[name].append(timed(fn))
+        med = {}
+        for name, ts in times.items():
+            med[name] = statistics.median(ts)
+            emit({"kind": "time", "K": K, "direction": "fwd_bwd", "variant": name, "rows": B, "nb_steps": n, "reps": len(ts),
+                  "median_ms": med[name], "min_ms": min(ts), "max_ms": max(ts), "mean_ms": statistics.fmean(ts)})
+        new = 0.5 * (med["abi_g_only_a"] + med["abi_g_only_b"])
+        emit({"kind": "derivative", "K": K, "pair_over_g_only": med["pair"] / med["g_only"], "node_count_of_the_first_pass": (n + 2) / (n + 1),
+              "pair_over_two_eval": med["pair"] / med["two_eval"],
+              "spread": abs(med["abi_g_only_a"] - med["abi_g_only_b"]) / new,
+              "root_over_new": med["abi_g_only_root"] / new if root is not None else None})
 
 
 if __name__ == "__main__":

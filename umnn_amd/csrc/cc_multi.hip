@@ -19,7 +19,9 @@
 // wave-private LDS transpose, dc = sum_j delta_1 to the finishing kernels (d_h, dW_1[:, 1:], db_1), per-wave d_theta slices summed
 // by a last kernel in a fixed order: no float atomics, two runs are bit-identical.  New at the output layer: dout_k =
 // g_k (x - x0)/2 w_j out'(s_k) (times -1/f_k^2 under inv_f), delta_L = act'(z_L) * W_L^T dout (four K-steps against the
-// transposed output image), dW_L / db_L += dout (x) [a_L, 1] through the same LDS trip.
+// transposed output image), dW_L / db_L += dout (x) [a_L, 1] through the same LDS trip.  With a cotangent g_fx of f_x
+// (umnn_cc_backward_multi_fx, the FX builds of the passes) dout at node x gains g_fx,k out'(s_k) and dx the term
+// sum_k g_fx,k df_k/dx, taken from the delta_1 of one more walk of node x in the EDGE pass (see cc_bwd_multi_kernel).
 //
 // Shared with cc_bwd_kernel (cc_backward.hip), in cc_bwd_shared.h: the row-major image staging, perm16, sign_bits / act_grad_bits
 // (the kink convention), the theta offsets and the launch bracket of a pass; d_h is cc_backward.hip's cc_bwd_dh_kernel
@@ -42,6 +44,7 @@ struct MultiArgs {
     const float* x;
     const float* h;
     const float* g;                 // backward: [NI][K]
+    const float* gfx;               // backward: cotangent of f_x, [NI][K]; nullable (FX variants only)
     const float* ccw;
     const float* ccs;
     float* F;                       // forward outputs [NI][K]; fx, fx0 nullable
@@ -252,7 +255,12 @@ __device__ __forceinline__ void stage_multi_rowmajor(const MultiArgs& a, float* 
 // NACC: hidden images whose dW this pass accumulates (layers l_lo .. l_lo + NACC - 1).  EDGE: the pass that owns what exists
 // once per integral -- dc, dW_1[:, 0] and the Leibniz terms.  OUTW: the pass can hold the output layer's dW_L / db_L (it does when
 // a.outw is set): a separate switch, because the seven-tile EDGE pass with one dW layer has no registers left for it.
-template <int TMAX, int KSC, int NACC, bool EDGE, bool OUTW>
+// FX: the launch has a cotangent g_fx of f_x[q][k] = f_k(x_q; h_q) (a.gfx; f itself, also under inv_f).  Every pass adds
+// g_fx out'(s_k) to the output layer's cotangent at node x.  The EDGE pass does it by walking node x once more, last, with that
+// cotangent alone -- the ordinary node 0 keeps the quadrature's --, because the delta_1 of that walk is what dx needs:
+// sum_k g_fx,k df_k/dx = sum_feature delta_1[feature] W_1[feature, x-column].  No register is held across the node loop for it
+// (g_fx is loaded where it is used, dx is written from inside the walk), and the variants without FX are the kernels they were.
+template <int TMAX, int KSC, int NACC, bool EDGE, bool OUTW, bool FX>
 __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const MultiArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const MlpDev& m = a.m;
@@ -343,10 +351,13 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
         for (int t = 0; t < TMAX; ++t) dcs[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         f32x4 fxv = f32x4{0.f, 0.f, 0.f, 0.f}, fx0v = f32x4{0.f, 0.f, 0.f, 0.f};
 
-        for (int k = 0; k <= n; ++k) {
-            const float u = a.ccs[k] + 1.f;
-            const float wk = a.ccw[k];
-            const float tk = k == 0 ? xv : __fadd_rn(x0v, __fmul_rn(dxv, u) * 0.5f);
+        const int klast = (FX && EDGE) ? n + 1 : n;                       // EDGE with g_fx: node x once more
+        for (int k = 0; k <= klast; ++k) {
+            const bool xtra = FX && EDGE && k > n;
+            const int kn = xtra ? 0 : k;
+            const float u = a.ccs[kn] + 1.f;
+            const float wk = a.ccw[kn];
+            const float tk = kn == 0 ? xv : __fadd_rn(x0v, __fmul_rn(dxv, u) * 0.5f);
             unsigned bits[UMNN_MAX_LINEAR];          // bits[l]: sign bits of hidden layer l's activation
             f32x4 act[TMAX];
             // ---------------- forward recompute ----------------
@@ -392,6 +403,11 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                 if (k == n) fx0v[r] = f;
                 const float invs = a.inv_f ? -__frcp_rn(f * f) : 1.f;
                 dout[r] = cotbase[r] * invs * wk * fp;
+                if (FX && (xtra || (!EDGE && k == 0))) {
+                    const int ko = 4 * r + g;
+                    const float gf = (ok && ko < K) ? a.gfx[qq * K + ko] : 0.f;
+                    dout[r] = xtra ? gf * fp : fmaf(gf, fp, dout[r]);
+                }
             }
 
             // ---------------- backward sweep ----------------
@@ -472,6 +488,19 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                         dW1x[t][r] = fmaf(delta[t][r], tk, dW1x[t][r]);
                     }
             }
+            if (xtra) {
+                // dx = sum_k g_k f_k(x) + sum_feature delta_1[feature] W_1[feature, x-column]  (delta_1 of g_fx out' alone)
+                float sx = 0.f, sfx = 0.f;
+#pragma unroll
+                for (int r = 0; r < 4; ++r) sx = fmaf(gv[r], fxv[r], sx);
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) sfx = fmaf(delta[t][r], w1x[16 * t + 4 * r], sfx);
+                sx = group_allreduce(sx);
+                sfx = group_allreduce(sfx);
+                if (ok && g == 0 && a.dx) a.dx[q] = sx + sfx;
+            }
         }
 
         if (EDGE) {
@@ -491,7 +520,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
             sx = group_allreduce(sx);
             sx0 = group_allreduce(sx0);
             if (ok && g == 0) {
-                if (a.dx) a.dx[q] = sx;
+                if (!FX && a.dx) a.dx[q] = sx;
                 if (a.dx0) a.dx0[q] = -sx0;
             }
         }
@@ -612,8 +641,10 @@ static const MultiFwdVariant kMultiFwd[] = {
 };
 
 // the backward passes of a family: the EDGE pass holds `edge_nacc` dW layers, every further pass `rest_nacc`
-struct MultiBwdVariant { int T, KS, nacc, edge, outw; multi_kernel_t fn; const char* name; };
-#define MULTI_BWD(T, KS, N, E, O) { T, KS, N, E, O, cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0>, "cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ">" }
+// fn / name [1]: the FX build of the pass (a g_fx cotangent was given), [0]: the kernel without it
+struct MultiBwdVariant { int T, KS, nacc, edge, outw; multi_kernel_t fn[2]; const char* name[2]; };
+#define MULTI_BWD(T, KS, N, E, O) { T, KS, N, E, O, {cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, false>, cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, true>}, \
+                                    {"cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ">", "cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ",FX=1>"} }
 static const MultiBwdVariant kMultiBwd[] = {
     MULTI_BWD(2, 8, 3, 1, 1), MULTI_BWD(2, 8, 3, 0, 0),
     MULTI_BWD(4, 13, 3, 1, 1), MULTI_BWD(4, 13, 3, 0, 0),
@@ -757,10 +788,10 @@ extern "C" long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net,
     return total;
 }
 
-extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
-                                      const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
-                                      float* dx0, float* dx, float* dh, float* dtheta,
-                                      void* workspace, long long workspace_bytes, void* stream_) {
+extern "C" int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
+                                         const float* g_fx, const float* cc_w, const float* cc_s, int nb_steps, long long B, int d,
+                                         int E, int inv_f, float* dx0, float* dx, float* dh, float* dtheta,
+                                         void* workspace, long long workspace_bytes, void* stream_) {
     hipStream_t stream = (hipStream_t)stream_;
     MultiPlan pl;
     if (int rc = multi_plan(net, E, &pl)) return rc;
@@ -782,7 +813,8 @@ extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, cons
     if (tiles > 0x7fffffffLL) return umnn_fail(UMNN_EUNSUPPORTED, "backward_multi: batch too large");
     a.ngroups = (unsigned)tiles;
     char* ws = (char*)workspace;
-    a.x0 = x0; a.x = x; a.h = h; a.g = g; a.ccw = cc_w; a.ccs = cc_s; a.dx0 = dx0; a.dx = dx;
+    a.x0 = x0; a.x = x; a.h = h; a.g = g; a.gfx = g_fx; a.ccw = cc_w; a.ccs = cc_s; a.dx0 = dx0; a.dx = dx;
+    const int fx = g_fx != nullptr;     // the FX build of every pass; without a g_fx the kernels of umnn_cc_backward_multi
     a.partials = (float*)ws;
     a.dc = (float*)(ws + o_dc);
     float* p0 = (float*)(ws + o_p0);
@@ -803,9 +835,9 @@ extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, cons
         a.outw = passes[pass].outw;
         a.scratch_per_wave = multi_scratch_per_wave(pl.T, v->nacc);
         const size_t lds = multi_bwd_lds(pl, v->nacc, wpb);
-        if (int rc = umnn_allow_lds((const void*)v->fn, lds)) return rc;
-        if (int rc = umnn_bwd_launch(stream, pass == 0 ? umnn_bwd_flops(net, nb_steps, a.NI) : 0.0, v->name, "cc_bwd_multi launch",
-                                     [&] { hipLaunchKernelGGL(v->fn, dim3(nblocks), dim3(64 * wpb), lds, stream, a); })) return rc;
+        if (int rc = umnn_allow_lds((const void*)v->fn[fx], lds)) return rc;
+        if (int rc = umnn_bwd_launch(stream, pass == 0 ? umnn_bwd_flops(net, nb_steps, a.NI) : 0.0, v->name[fx], "cc_bwd_multi launch",
+                                     [&] { hipLaunchKernelGGL(v->fn[fx], dim3(nblocks), dim3(64 * wpb), lds, stream, a); })) return rc;
     }
 
     // ---- finishing kernels
@@ -819,4 +851,12 @@ extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, cons
                            a.partials, nslices, a.n_params, p0, nparts0, E, H1, a.poffW[0], a.poffb[0], dtheta);
     }
     return umnn_check(hipGetLastError(), "cc_bwd_multi finishing launch");
+}
+
+extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
+                                      const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
+                                      float* dx0, float* dx, float* dh, float* dtheta,
+                                      void* workspace, long long workspace_bytes, void* stream) {
+    return umnn_cc_backward_multi_fx(net, x0, x, h, g, nullptr, cc_w, cc_s, nb_steps, B, d, E, inv_f, dx0, dx, dh, dtheta,
+                                     workspace, workspace_bytes, stream);
 }

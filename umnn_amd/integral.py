@@ -285,18 +285,22 @@ def hip_forward_multi(spec, x0, x, h, nb_steps, inv_f=False):
     return F, fx, fx0
 
 
-def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True), inv_f=False):
-    """Multi-output backward (umnn_cc_backward_multi) for the cotangent g [B, n_out] -> (dx0, dx, dh, dtheta_flat), None where
+def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True), inv_f=False, g_fx=None):
+    """Multi-output backward (umnn_cc_backward_multi_fx) for the cotangent g [B, n_out] -> (dx0, dx, dh, dtheta_flat), None where
     ``need`` is False: dx = sum_k g_k f_k(x) and dx0 = -sum_k g_k f_k(x0) are [B,1]; dtheta is flat in parameters() order with
-    the last layer as [n_out, H_L] / [n_out]."""
+    the last layer as [n_out, H_L] / [n_out].  ``g_fx`` [B, n_out] (optional): the cotangent of the f_x output, f_k(x; h) -- it
+    reaches dh and dtheta through the same launches and adds sum_k g_fx,k df_k/dx (x) to dx."""
     lib = _lib.lib()
     K = n_out_of(spec)
     _check_multi_x(K, x)
     B, d, E = _shape(spec, x, h)
     if g.shape != (B, K):
         raise RuntimeError(f"umnn_amd: the cotangent of a multi-output integral has shape {tuple(g.shape)}; expected {(B, K)}")
+    if g_fx is not None and g_fx.shape != (B, K):
+        raise RuntimeError(f"umnn_amd: the cotangent of the f_x output of a multi-output integral has shape {tuple(g_fx.shape)}; expected {(B, K)}")
     x_dtype, h_dtype = x.dtype, h.dtype
     x, h, g, x0 = _f32c(x), _f32c(h), _f32c(g), (None if x0 is None else _f32c(x0))
+    g_fx = None if g_fx is None else _f32c(g_fx)
     w, s = device_tables(nb_steps, x.device)
     dx0 = torch.empty_like(x) if need[0] else None
     dx = torch.empty_like(x) if need[1] else None
@@ -309,10 +313,10 @@ def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True
         if nbytes < 0:
             _lib.check(_lib.EUNSUPPORTED, "umnn_cc_backward_multi_workspace_bytes")
         ws = torch.empty(max(int(nbytes), 4), device=x.device, dtype=torch.uint8)
-        rc = lib.umnn_cc_backward_multi(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(g), _ptr(w), _ptr(s), int(nb_steps),
-                                        B, d, E, int(bool(inv_f)), _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta),
-                                        _ptr(ws), int(nbytes), _stream(x.device))
-    _lib.check(rc, "umnn_cc_backward_multi")
+        rc = lib.umnn_cc_backward_multi_fx(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s),
+                                           int(nb_steps), B, d, E, int(bool(inv_f)), _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta),
+                                           _ptr(ws), int(nbytes), _stream(x.device))
+    _lib.check(rc, "umnn_cc_backward_multi_fx")
     _state.path = _last_backward["path"] = "hip"
     if x_dtype != torch.float32:
         dx0 = dx0.to(x_dtype) if dx0 is not None else None
@@ -722,8 +726,6 @@ def aten_vjp(integrand, x0, x, h, g, g_fx, nb_steps, inv_f=False, limits=True):
         multi = g.shape[1] != d          # g [B,K] of a multi-output integrand over x [B,1]: dx / dx0 are sums over k
         if multi:
             _check_multi_x(g.shape[1], x)
-            if g_fx is not None:
-                raise RuntimeError("umnn_amd: the f_x output belongs to the single-output operators (n_out = 1)")
         cot = g * (span.expand(B, g.shape[1]) if multi else span) / 2
         d_params = [torch.zeros_like(p) for p in params]
         dh = torch.zeros_like(h)
@@ -740,17 +742,16 @@ def aten_vjp(integrand, x0, x, h, g, g_fx, nb_steps, inv_f=False, limits=True):
                 acc += gr
             dh += gh.view(e - a, B, -1).sum(0)
         dx0 = dx = None
+        over_k = (lambda t: t.sum(1, keepdim=True)) if multi else (lambda t: t)      # the Leibniz terms of K outputs add up
         if g_fx is not None:
             fx, vjp = torch.func.vjp(f, params, x, h)
             gp, gx, gh = vjp(g_fx)
-            dx, dh = fx * g + gx, dh + gh
+            dx, dh = over_k(fx * g) + gx, dh + gh
             d_params = [acc + gr for acc, gr in zip(d_params, gp)]
         elif limits:
-            dx = f(params, x, h) * g
+            dx = over_k(f(params, x, h) * g)
         if limits:
-            dx0 = -f(params, x0, h) * g
-        if multi and limits:
-            dx, dx0 = dx.sum(1, keepdim=True), dx0.sum(1, keepdim=True)
+            dx0 = over_k(-f(params, x0, h) * g)
     _state.path = _last_backward["path"] = "aten"
     return dx0, dx, dh, (_flatten(d_params) if d_params else None)
 
@@ -766,10 +767,8 @@ def quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need=(True
     ``spec`` (None: the forward ran on ATen) has a backward kernel, else ``aten_vjp`` on ``integrand``.  x0 None: lower limit 0."""
     need = (bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3]))
     if spec is not None and n_out_of(spec) > 1:
-        if g_fx is not None:
-            raise RuntimeError(f"umnn_amd: the f_x output belongs to the single-output operators; this integrand has n_out = {n_out_of(spec)}")
         if _multi_kernels_ok(spec):
-            return hip_backward_multi(spec, x0, x, h, g, nb_steps, need, inv_f=inv_f)
+            return hip_backward_multi(spec, x0, x, h, g, nb_steps, need, inv_f=inv_f, g_fx=g_fx)
     elif spec is not None and _hip_backward_ok(spec, x, h):
         return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f=inv_f, z2_saved=z2_saved)
     out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
@@ -1056,7 +1055,9 @@ def _launch_backward(net, spec, integrand, x0, x, h, g, g_fx, nb_steps, need, in
     if not net:
         return quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need, inv_f)
     need = [bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3])]
-    if net[0][-1].shape[0] > 1:
+    if net[0][-1].shape[0] > 1 and g_fx is not None:
+        out = torch.ops.umnn.cc_backward_multi_fx(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
+    elif net[0][-1].shape[0] > 1:
         out = torch.ops.umnn.cc_backward_multi(x0, x, h, g, *net, int(nb_steps), need, bool(inv_f))
     else:
         out = torch.ops.umnn.cc_backward(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
@@ -1087,18 +1088,20 @@ def _saved(ctx, n):
 
 
 def _quad_forward(ctx, who, x0, x, integrand, h, nb_steps, inv_f, jac):
-    """forward of the four quadrature operators -> (F, f_x or None).  ``jac``: the operator owns its f_x output (HIP path only)."""
-    spec = _hip_spec(integrand, x, multi=not jac, who=who)
-    if jac and spec is None:
+    """forward of the quadrature operators -> (F, f_x or None).  ``jac``: the operator owns its f_x output -- True: single-output
+    integrands on the HIP path only; "any": every n_out and device (``IntegralWithDerivative``)."""
+    spec = _hip_spec(integrand, x, multi=jac is not True, who=who)
+    if jac is True and spec is None:
         raise RuntimeError(f"{who} needs an MLP integrand on a GPU")
-    ctx.nb_steps, ctx.inv_f, ctx.jac, ctx.x0_none = nb_steps, bool(inv_f), jac, x0 is None      # (x0 None: lower limit 0, nothing to save)
+    ctx.nb_steps, ctx.inv_f, ctx.jac, ctx.x0_none = nb_steps, bool(inv_f), bool(jac), x0 is None      # (x0 None: lower limit 0, nothing to save)
     lims = () if x0 is None else (x0,)
     if spec is not None and _graph_mode():
         _save(ctx, spec, integrand, *lims, x, h)
     else:       # clones: callers mutate their tensors in place after the call (UMNNMAF.compute_ll clamps z, :150)
         _save(ctx, spec, integrand, *(t.clone() for t in lims), x.clone(), h)
     if spec is None:
-        return aten_forward(integrand, x0, x, h, nb_steps, inv_f), None
+        F = aten_forward(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, nb_steps, inv_f)
+        return F, (integrand(x, h) if jac else None)
     return cc_forward(spec, x0, x, h, nb_steps, inv_f)
 
 
@@ -1149,6 +1152,32 @@ class IntegralWithJacobian(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x0, x, integrand, flat_params, h, nb_steps):
         return _quad_forward(ctx, "IntegralWithJacobian", x0, x, integrand, h, nb_steps, False, True)
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gF, gfx):
+        nig = ctx.needs_input_grad
+        dx0, dx, dh, dtheta = _quad_backward(ctx, gF, gfx, (nig[0], nig[1], nig[4], nig[3]))
+        return dx0, dx, None, dtheta, dh, None
+
+
+class IntegralWithDerivative(torch.autograd.Function):
+    """(F, f_x) = (int_{x0}^{x} f(t; h) dt, f(x; h)) for every integrand, n_out and device, differentiable in both outputs:
+
+        IntegralWithDerivative.apply(x0, x, integrand, flat_params, h, nb_steps) -> (F, f_x)
+
+    f_x is the derivative of F in its upper limit -- the density of a CDF, the hazard of a cumulative hazard -- and node 0 of the
+    quadrature, so it costs no second evaluation of the integrand.  This pair is the package's replacement for
+    ``torch.autograd.grad(F, x, create_graph=True)``, which raises here (every quadrature operator is ``once_differentiable``).
+    A single-output MLP integrand on the GPU takes the path of ``IntegralWithJacobian`` (same kernels, same bits); an MLP integrand of
+    2..16 outputs over x [B,1] on the GPU is one multi-output launch forward and the backward passes of umnn_cc_backward_multi_fx,
+    which take the cotangent of f_x next to that of F; everything else -- host tensors, n_out > 16, nets beyond the LDS, arbitrary
+    callables -- runs on ATen (``aten_forward`` / ``aten_vjp``).  A multi-output integrand returns [B, n_out] twice and
+    dx = sum_k g_k f_k(x) + sum_k g_fx,k df_k/dx (x)."""
+
+    @staticmethod
+    def forward(ctx, x0, x, integrand, flat_params, h, nb_steps):
+        return _quad_forward(ctx, "IntegralWithDerivative", x0, x, integrand, h, nb_steps, False, "any")
 
     @staticmethod
     @once_differentiable

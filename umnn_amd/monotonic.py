@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .integral import InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
+from .integral import IntegralWithDerivative, InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
 from .nets import IntegrandNN, MlpSpec, TensorLinear, _spec_from_sequential  # noqa: F401  (IntegrandNN is re-exported)
 
 
@@ -90,6 +90,25 @@ class MonotonicNN(nn.Module):
         integral = ParallelNeuralIntegral.apply(x0, x, self.integrand, _flatten(self.integrand.parameters()), h,
                                                 self.nb_steps)
         return scaling * integral + offset
+
+    def forward_with_derivative(self, x, h, log=False):
+        """(y [B, n_out], dy/dx [B, n_out]): ``forward(x, h)`` and its derivative in x, dy_k/dx = exp(s_k(h)) f_k(x; h) > 0 -- the
+        density of a CDF, the hazard of a cumulative hazard, the Jacobian of a change of variables.  ``log=True`` returns
+        log dy_k/dx = s_k(h) + log f_k(x; h) instead, what a likelihood consumes (no overflow through exp).  f_k(x; h) is node 0 of the
+        quadrature, so on GPU tensors the pair is ONE quadrature launch for every ``n_out`` (``IntegralWithDerivative``), and
+        gradients of both outputs reach x, h, the conditioner and the integrand through the backward kernels.
+
+        This is the package's replacement for ``torch.autograd.grad(y, x, create_graph=True)``: the quadrature operators are
+        once-differentiable by design, so that call keeps raising; a double backward through this pair is out of scope too."""
+        x0 = torch.zeros_like(x)
+        out = self.net(h)
+        if self.n_out == 1:
+            offset, log_scaling = out[:, [0]], out[:, [1]]
+        else:
+            offset, log_scaling = out[:, :self.n_out], out[:, self.n_out:]
+        scaling = torch.exp(log_scaling)
+        integral, f_x = IntegralWithDerivative.apply(x0, x, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps)
+        return scaling * integral + offset, (log_scaling + torch.log(f_x) if log else scaling * f_x)
 
     def inverse(self, y, h, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False, output=0):
         """x [B,1] in ``x_range`` with ``forward(x, h) = y`` (``forward(x, h)[:, output] = y`` when ``n_out > 1``): y is strictly

@@ -5,6 +5,7 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
     umnn::cc_backward(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_forward_multi(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)        x [B,1]; F, f_x [B, n_out]
     umnn::cc_backward_multi(x0?, x, h, g, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
+    umnn::cc_backward_multi_fx(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::cc_solve_block(t, h, x_init?, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::flow_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, log_jac_in?) -> (z, log_jac, f_x)
@@ -17,8 +18,9 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
 The integrand crosses the op boundary as tensors and plain values -- the fields of ``nets.MlpSpec`` -- never as a module.  Every
 implementation calls the eager path's own ``integral.hip_*`` function (same arithmetic mode, overflow fallback and
 ``path_taken()`` bookkeeping); every output is a fresh tensor and no op writes an input.  Outputs an op is told it need not
-compute (``need``) come back as empty tensors.  cc_forward, flow_block and flow_ll are differentiable (their backward is the
-matching op; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` -- is differentiable in its x output through cc_backward,
+compute (``need``) come back as empty tensors.  cc_forward, cc_forward_multi, flow_block and flow_ll are differentiable (their
+backward is the matching op -- cc_forward_multi's is cc_backward_multi_fx when a cotangent for its f_x output arrives, cc_backward_multi
+when none does; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` -- is differentiable in its x output through cc_backward,
 by the implicit-function theorem; cc_solve_block -- the same solve for every (row, dimension) in ONE launch, optionally warm-started,
 what the recorded ``invert(method="jacobi")`` sweeps call under no_grad -- has no autograd formula: a backward through it raises;
 flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
@@ -250,14 +252,14 @@ def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
             W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
 
 
-
 # ---------------------------------------------------------------------------------------------------------- multi-output quadrature
-def _check_cc_multi(op, x0, x, h, W, b, hidden_act, out_act, g=None):
+def _check_cc_multi(op, x0, x, h, W, b, hidden_act, out_act, g=None, g_fx=None):
     B, d = _check_net(op, x, h, W, b, hidden_act, out_act, multi=True)
     if x0 is not None:
         _check_tensor(op, "x0", x0, x, (B, 1), _FLOATS)
-    if g is not None:
-        _check_tensor(op, "g", g, x, (B, W[-1].shape[0]), _FLOATS)
+    for name, t in (("g", g), ("g_fx", g_fx)):
+        if t is not None:
+            _check_tensor(op, name, t, x, (B, W[-1].shape[0]), _FLOATS)
 
 
 def pure_mlp_multi(W, b, hidden_act, out_act):
@@ -301,19 +303,26 @@ def _(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
 
 def _cc_forward_multi_setup(ctx, inputs, output):
     x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f = inputs
-    ctx.mark_non_differentiable(output[1])         # (f_x is for inspection: the f_x operators are single-output)
+    ctx.set_materialize_grads(False)               # (an f_x nobody differentiates: no zero cotangent, the backward of before)
     ctx.meta = (hidden_act, out_act, nb_steps, inv_f, len(W), x0 is None)
     ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
 
 
-def _cc_forward_multi_backward(ctx, gF, _gfx):
+def _cc_forward_multi_backward(ctx, gF, gfx):
     hidden_act, out_act, nb_steps, inv_f, L, x0_none = ctx.meta
     saved = ctx.saved_tensors
     x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
     x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
     nig = ctx.needs_input_grad
     need = [bool(nig[0]) and not x0_none, bool(nig[1]), bool(nig[2]), any(nig[3]) or any(nig[4])]
-    dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward_multi(x0, x, h, gF.contiguous(), W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    if gF is None and gfx is None:
+        return (None,) * 9
+    gF = x.new_zeros((x.shape[0], W[-1].shape[0])) if gF is None else gF.contiguous()
+    if gfx is None:
+        dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward_multi(x0, x, h, gF, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    else:
+        dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward_multi_fx(x0, x, h, gF, gfx.contiguous(), W, b, hidden_act, out_act, nb_steps,
+                                                                  need, inv_f)
     gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[3], nig[4])
     return (dx0 if need[0] else None, dx if need[1] else None, dh if need[2] else None, gW, gb,
             None, None, None, None)
@@ -333,8 +342,12 @@ def cc_backward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, W: 
     """``integral.quadrature_backward`` of a multi-output integrand given as tensors: the multi-output HIP kernels, or -- decided
     here at run time -- the one ATen backward on ``pure_mlp_multi``."""
     _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return _backward_multi(x0, x, h, g, None, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+
+
+def _backward_multi(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
     need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
-    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp_multi(W, b, hidden_act, out_act), x0, x, h, g, None,
+    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp_multi(W, b, hidden_act, out_act), x0, x, h, g, g_fx,
                                  nb_steps, need, inv_f)
     like = (x, x, h, W[0])
     return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
@@ -344,10 +357,33 @@ def cc_backward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, W: 
 @cc_backward_multi.register_fake
 def _(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f):
     _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return _backward_fakes(x0, x, h, W, b, need)
+
+
+def _backward_fakes(x0, x, h, W, b, need):
     return (x.new_empty(x.shape) if (need[0] and x0 is not None) else _empty(x),
             x.new_empty(x.shape) if need[1] else _empty(x),
             h.new_empty(h.shape) if need[2] else _empty(h),
             W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
+
+
+def _check_cc_backward_multi_fx(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc_multi("cc_backward_multi_fx", x0, x, h, W, b, hidden_act, out_act, g, g_fx)
+    _check_need("cc_backward_multi_fx", need, 4)
+
+
+@torch.library.custom_op("umnn::cc_backward_multi_fx", mutates_args=(), device_types="cuda")
+def cc_backward_multi_fx(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, g_fx: Optional[Tensor], W: List[Tensor], b: List[Tensor],
+                         hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``cc_backward_multi`` with the cotangent ``g_fx`` [B, n_out] of the f_x output on top of ``g`` (None: exactly that op)."""
+    _check_cc_backward_multi_fx(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return _backward_multi(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+
+
+@cc_backward_multi_fx.register_fake
+def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc_backward_multi_fx(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return _backward_fakes(x0, x, h, W, b, need)
 
 
 # ---------------------------------------------------------------------------------------------------------- inverse (Newton solve)
@@ -562,7 +598,7 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
     return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
 
 
-OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_backward_multi", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_backward_multi", "cc_backward_multi_fx", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
 spec_args = _I.spec_args       # MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it
