@@ -285,6 +285,14 @@ int umnn_cc_backward_saved_io(const umnn_mlp* net, const umnn_io* io, const void
                               const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E,
                               void* dx, void* dh, float* dtheta, const float* z2_saved, long long z2_floats,
                               void* workspace, long long workspace_bytes, void* stream);
+/* The quadrature backward of one flow block: umnn_cc_backward_saved_io -- or, with z2_saved null, umnn_cc_backward_io with lower limit 0 --
+ * whose d_h also carries the block's h_0 term: z = exp(s) (F + h_0) sends the cotangent of F to embedding row 0 as well, and h0_cot
+ * ([B, d] fp32, nullable = none) is added to d_h[b, 0 * d + i] in fp32 by the kernel that stores d_h.  A bf16 d_h is thereby rounded
+ * once; added afterwards, row 0 would be rounded twice. */
+int umnn_cc_backward_block_io(const umnn_mlp* net, const umnn_io* io, const void* x, const void* h, const void* g, const void* g_fx,
+                              const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, const float* h0_cot,
+                              void* dx, void* dh, float* dtheta, const float* z2_saved, long long z2_floats,
+                              void* workspace, long long workspace_bytes, void* stream);
 
 /* Elementwise glue of a block's TRAINING path (umnn_amd/csrc/cc_flow_glue.hip), one launch each.
  * umnn_flow_block_cotangents: backward of the block epilogue (UMNNMAF.py:80-83,134,138-139)

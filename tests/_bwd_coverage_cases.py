@@ -1,4 +1,4 @@
-"""Case table, inputs and float64 truth of the quadrature-backward coverage tests: tests/test_backward_coverage_cpu.py (names,
+"""Case table, inputs, float64 truth, arithmetic classes and error yardsticks of the quadrature-backward coverage tests: tests/test_backward_coverage_cpu.py (names,
 completeness, the kink guard and the truth pin, no GPU) and tests/test_gpu_backward_coverage.py (every case on the device).
 
 Names.  Every expected name below was derived by hand from csrc/cc_bwd_plan.h for a device of 256 CUs, not read back from the
@@ -178,6 +178,13 @@ for _w1 in FRONT_W1:
         for _gfx in (True, False):
             Z2_CASES[_w1, _live, _gfx] = case(f"front-z2-{tag([_w1] + _rest)}-{'g_fx' if _gfx else 'no-g_fx'}", 4, "FRONT", [_w1] + _rest,
                                              f"cc_bwd_bf16<L=2,EDGE=1,LIVE={_live},FRONT>", x0=False, g_fx=_gfx)
+# the same pair with a bf16 embedding (the MNIST-shaped training path): T1 = 5 and 8, NL2 = 13 and 0, with g_fx, run through the C
+# entries umnn_flow_stack_block_forward_save_io / umnn_cc_backward_saved_io with an io descriptor.  (A four-part key: the tests that walk
+# the three-part keys above go through the Python wrappers.)
+for _w1 in (70, 120):
+    for _rest, _live in (([50, 50], 13), ([60, 60], 0)):
+        Z2_CASES[_w1, _live, True, "h-bf16"] = case(f"front-z2-{tag([_w1] + _rest)}-g_fx-h-bf16", 4, "FRONT", [_w1] + _rest,
+                                                    f"cc_bwd_bf16<L=2,EDGE=1,LIVE={_live},FRONT>", x0=False, g_fx=True, h_bf16=True)
 # Several chunks.  The scratch holds (2 x 257 + 1) slices per tile (sized for n = 256 with g_fx); a call needs 2 (n + 1) + 1 with g_fx, so
 # n = 257 (517 > 515) is the smallest n that does not fit: chunk = 8 x 515 // 517 = 7 of 8 tiles, evened out to two chunks of four.
 # d = 1, B = 123: 8 tiles of rows.  The launch counter counts one per main pass whatever the chunks (umnn_bwd_launch notes once), so
@@ -319,3 +326,160 @@ def truth(c, device="cpu", dtype=torch.float64):
         _TRUTH[key] = tuple(t.detach() for t in _truth64.backward_reference(i.net, to(i.x0), to(i.x), to(i.h), to(i.g), to(i.g_fx), c["n"],
                                                                             dtype=dtype, chunk=1024, inv_f=c["inv_f"]))
     return _TRUTH[key]
+
+
+# ---- arithmetic classes and yardsticks ----------------------------------------------------------------------------------------------
+# What the kernel headers declare, not what was measured:
+#   A (fp32 level): d_x0 and d_x of every family -- the Leibniz terms and the g_fx tangent come from the forward recompute, which is
+#     fp32 (cc_backward.hip) or three pieces / six cross terms "fp32-level accuracy" (cc_bwd_bf16_kernel.h) everywhere --; every output
+#     of cc_bwd<...> (fp32), cc_bwd_f16<...> (two fp16 pieces of 11 bits, cc_bwd_ws16_kernel.h) and cc_bwd_bf16x6<...> (UMNN_BWD_NPB = 3:
+#     six cross terms in the delta chain and the dW products too).
+#   B (two bf16 pieces, three cross terms, "errors stay ~1e-5": cc_bwd_bf16_kernel.h): d_h and d_theta of cc_bwd_bf16<...> in all its
+#     forms (loop, SWP, WS, FRONT, WS+FRONT; also where a flag made the fp16 pipeline ineligible, so that the expected name is the
+#     bf16 one), and of the fp16 middle stage with a bf16 stage C behind it.  cc_bwd_plan.h: stage C is BWD16 (fp16 pieces) only when
+#     front_bwd2 == 1; front_bwd2 = 2 (BWD2) and front_bwd2 = 0 (BWD, one wave per tile) both run the two-piece bf16 build of
+#     cc_backward_front.hip behind the fp16 middle stage.
+OUTPUTS = ("d_x0", "d_x", "d_h", "d_theta")
+M_GRAD = 8.0          # the project's constant: M_GRAD of tests/_multi_coverage_cases.py, M_FP32_LEVEL of tests/_fwd_coverage_cases.py
+# output -> M where the measured ratio asks for more than M_GRAD: twice the largest measured ratio (profiles/bwd_coverage/README.md).  Never
+# d_x / d_x0.
+#   "d_theta:b_out", the gradient of the output bias, a parameter tensor of ONE element: the single sum of dout = cot f'(s) over all
+#   B d (n + 1) points (+ the g_fx term), whose terms change sign -- sum |dout| / |sum dout| is 13 .. 16000 over the input sets here.  Its
+#   fp32 rounding error is a few units of 2^-24 times that cancellation, in the kernels (the fma chain `dwo`, the lane shuffles, the
+#   partial sums of the reduction kernel) as in ATen; but where a tensor of many elements takes the largest of many such errors, E32 of
+#   this one is ONE draw, anywhere between 0.00 and 0.96 of cancellation x 2^-24 over the input sets, often at the 2^-22 floor.  The five
+#   runs that measure above 8 x E32 (8.1 .. 17.0: rep-FRONT_WS16-no-x0, rep-FRONT_WS-inv_f, rep-FRONT_WS16-inv_f, front-chunks-ws16=2,
+#   front-z2-120x60x60-g_fx saved) all measure 0.35 .. 0.92 of cancellation x 2^-24: one fp32 rounding of that sum.  No product is involved.
+M_OF = {"d_theta:b_out": 2 * 17.02}
+FLOOR = 2.0 ** -22
+TOL = 1e-4            # tests/test_gpu_backward.py (restated: that module needs a GPU to import)
+
+
+def bf16_stage_c_behind_fp16(c):
+    return c["name"].startswith("cc_bwd_f16<") and "FRONT" in c["name"] and c["options"].get("front_bwd2", 1) != 1
+
+
+def arith_class(c):
+    """-> {output: "A" | "B"} from the case's expected name and options (the rule above)."""
+    two_piece = c["name"].startswith("cc_bwd_bf16<") or bf16_stage_c_behind_fp16(c)
+    assert two_piece or c["name"].startswith(("cc_bwd<", "cc_bwd_f16<", "cc_bwd_bf16x6<")), c["name"]
+    return {"d_x0": "A", "d_x": "A", "d_h": "B" if two_piece else "A", "d_theta": "B" if two_piece else "A"}
+
+
+def split_layers(c):
+    """Indices (into the net's Linear layers) of the layers whose backward products W_l^T delta and delta (x) a run on two bf16 pieces.
+    cc_bwd_bf16<...>: every hidden-to-hidden layer -- in the three-stage forms the first of them is stage C's, the rest the middle
+    stage's.  The fp16 middle stage with a bf16 stage C: that first one only.  The input layer is not among them (d_h and dW1 come from
+    dc = sum_k delta_1 in the fp32 finishing kernels, dW1[:, 0] from an fp32 fma), nor is the output layer: every bf16 kernel forms
+    delta_L = dout w_out act'(a_L) and dw_out += dout a_L in fp32 registers (`dwo`, `wout` in cc_bwd_bf16_kernel.h, cc_bwd_swp_kernel.h
+    and cc_bwd_ws_kernel.h -- which is why the SWP and loop kernels agree bit for bit in the output layer)."""
+    n_linear = len(c["hid"]) + 1
+    if c["name"].startswith("cc_bwd_bf16<"):
+        return tuple(range(1, n_linear - 1))
+    return (1,) if bf16_stage_c_behind_fp16(c) else ()
+
+
+def _pieces(t):
+    """hi = bf16(t), lo = bf16(t - hi), both round to nearest even (of the float32 value the kernel holds), as float64"""
+    hi = t.float().to(torch.bfloat16).to(t.dtype)
+    return hi, (t - hi).float().to(torch.bfloat16).to(t.dtype)
+
+
+class _TwoPieceLinear(torch.autograd.Function):
+    """y = a W^T + b exactly; backward with every product on two bf16 pieces and the cross terms hi hi + hi lo + lo hi (the constant-one
+    feature of the bias column is its own leading piece, so the bias gradient sums hi(delta) + lo(delta))."""
+
+    @staticmethod
+    def forward(ctx, a, W, b):
+        ctx.save_for_backward(a, W)
+        return torch.nn.functional.linear(a, W, b)
+
+    @staticmethod
+    def backward(ctx, g):
+        a, W = ctx.saved_tensors
+        (gh, gl), (ah, al), (Wh, Wl) = _pieces(g), _pieces(a), _pieces(W)
+        return gh @ Wh + gh @ Wl + gl @ Wh, gh.t() @ ah + gh.t() @ al + gl.t() @ ah, (gh + gl).sum(0)
+
+
+class _SplitLinear(torch.nn.Linear):
+    def forward(self, a):
+        return _TwoPieceLinear.apply(a, self.weight, self.bias)
+
+
+def three_term_net(c):
+    """A deep copy of the case's net whose split_layers(c) differentiate on two bf16 pieces; the forward stays exact."""
+    import copy
+    net = copy.deepcopy(inputs(c).net)
+    lins = [m for m in net.net if isinstance(m, torch.nn.Linear)]
+    for l in split_layers(c):
+        lins[l].__class__ = _SplitLinear
+    return net
+
+
+def param_sizes(c):
+    widths = [1 + c["E"]] + c["hid"] + [1]
+    return [k for i in range(len(widths) - 1) for k in (widths[i] * widths[i + 1], widths[i + 1])]
+
+
+def errors(c, outs, ref):
+    """-> {output: error} of (d_x0, d_x, d_h, d_theta) `outs` against `ref` (torch tensors, None where absent): U.rel_err for d_x0 and
+    d_x, U.scaled_err for d_h, the flat d_theta and -- under "tensors" -- each parameter tensor of d_theta separately."""
+    from tests import _util as U
+    np64 = lambda t: t.detach().double().cpu().numpy()
+    crit = (U.rel_err, U.rel_err, U.scaled_err, U.scaled_err)
+    e = {nm: None if o is None else crit[k](np64(o), np64(ref[k])) for k, (nm, o) in enumerate(zip(OUTPUTS, outs))}
+    if outs[3] is not None:
+        e["tensors"] = [U.scaled_err(a, b) for a, b in zip(np.split(np64(outs[3]), np.cumsum(param_sizes(c))[:-1]),
+                                                           np.split(np64(ref[3]), np.cumsum(param_sizes(c))[:-1]))]
+    return e
+
+
+_YARD = {}
+
+
+def yardsticks(c):
+    """-> {output: yardstick, "tensors": [per parameter tensor]}, on the CPU, once per input set and class: E32 = the error of the
+    reference's own float32 run against the float64 truth, floored at 2^-22; for class B outputs max(E32, E3), E3 the error of the
+    float64 truth with the products of split_layers(c) on two bf16 pieces."""
+    cls = arith_class(c)
+    key = _input_key(c) + (c["inv_f"], split_layers(c))
+    if key not in _YARD:
+        ref = truth(c)
+        floor = lambda e: {k: ([max(x, FLOOR) for x in v] if isinstance(v, list) else max(v, FLOOR)) for k, v in e.items()}
+        y = floor(errors(c, truth(c, dtype=torch.float32), ref))
+        if split_layers(c):
+            i = inputs(c)
+            e3 = floor(errors(c, [t.detach() for t in _truth64.backward_reference(three_term_net(c), i.x0, i.x, i.h, i.g, i.g_fx, c["n"],
+                                                                                   chunk=1024, inv_f=c["inv_f"])], ref))
+            y["E3"] = e3
+            for nm in ("d_h", "d_theta"):
+                y[nm] = max(y[nm], e3[nm])
+            y["tensors"] = [max(a, b) for a, b in zip(y["tensors"], e3["tensors"])]
+        _YARD[key] = y
+    assert all(cls[nm] == ("B" if split_layers(c) and nm in ("d_h", "d_theta") else "A") for nm in OUTPUTS)
+    return _YARD[key]
+
+
+def bound_of(name):
+    """M of one output: M_GRAD, or the entry of M_OF ("d_theta:b_out": the last parameter tensor)"""
+    return M_OF.get(name, M_GRAD)
+
+
+def check_bounds(c, outs, ref, tag=None):
+    """Every output present in `outs` within M x its yardstick of `ref`, d_theta flat and per parameter tensor; prints the largest
+    error / yardstick ratio per output, of the parameter tensors but the output bias, and of the output bias (BWDYARD lines), and
+    -> those ratios."""
+    y, e = yardsticks(c), errors(c, outs, ref)
+    ratio = {nm: None if e[nm] is None else e[nm] / y[nm] for nm in OUTPUTS}
+    per_tensor = [a / b for a, b in zip(e.get("tensors") or [], y["tensors"])]
+    if per_tensor:
+        ratio["tensors"], ratio["b_out"] = max(per_tensor[:-1]), per_tensor[-1]
+    cls = arith_class(c)
+    fmt = "|".join("-" if ratio.get(nm) is None else f"{ratio[nm]:.2f}" for nm in OUTPUTS + ("tensors", "b_out"))
+    print(f"BWDYARD|{c['part']}|{c['family']}|{tag or c['id']}|{''.join(cls[nm] for nm in OUTPUTS)}|{fmt}")
+    for nm in OUTPUTS:
+        assert ratio[nm] is None or ratio[nm] <= bound_of(nm), (c["id"], nm, cls[nm], e[nm], y[nm], ratio[nm])
+    for k, r in enumerate(per_tensor):
+        name = "d_theta:b_out" if k == len(per_tensor) - 1 else f"d_theta:{'bW'[k % 2 == 0]}_{k // 2}"
+        assert r <= bound_of(name), (c["id"], name, cls["d_theta"], e["tensors"][k], y["tensors"][k], r)
+    return ratio

@@ -1,7 +1,8 @@
 """The case table of tests/_bwd_coverage_cases.py, proved without a GPU: every case's hand-derived name is what
 umnn_cc_backward_plan_name gives under the case's options; the cases cover every kernel name the plan header can produce (or the name
 is in UNREACHED with the reason); every case's inputs keep the documented distance from the LeakyReLU kinks without rejecting more
-than half of the draws; and the float64 truth wrapper agrees with the oracle the reference fixtures pin."""
+than half of the draws; the float64 truth wrapper agrees with the oracle the reference fixtures pin; every case has an arithmetic class
+by the stated rule; and the bounds built on the yardsticks reject a wrong LeakyReLU slope that the flat tolerance lets through."""
 import ctypes
 
 import numpy as np
@@ -141,3 +142,114 @@ def test_truth_is_the_pinned_oracle(id, monkeypatch):
         rdx, rdh, rflat = rdx + jdx, rdh + jdh, rflat + jflat
     for got, ref in zip(C.truth(c), (rdx0, rdx, rdh, rflat)):
         assert np.abs(got.numpy() - ref).max() <= 1e-12 * np.abs(ref).max()
+
+
+# ---- arithmetic classes, yardsticks and the bounds built from them ------------------------------------------------------------------
+@pytest.mark.parametrize("c", C.CASES, ids=[c["id"] for c in C.CASES])
+def test_every_case_has_a_class_by_the_stated_rule(c):
+    """d_x0 and d_x are class A everywhere; d_h and d_theta are class B exactly for cc_bwd_bf16<...> and for the fp16 middle stage
+    whose stage C runs on bf16 pieces (cc_bwd_plan.h: every front_bwd2 but 1), class A for cc_bwd<...>, cc_bwd_f16<...> otherwise and
+    cc_bwd_bf16x6<...>; the emulated two-piece layers are the hidden-to-hidden ones of exactly the class B cases."""
+    cls = C.arith_class(c)
+    assert set(cls) == set(C.OUTPUTS) and set(cls.values()) <= {"A", "B"}
+    assert cls["d_x0"] == cls["d_x"] == "A" and cls["d_h"] == cls["d_theta"]
+    stem = c["name"].split("<")[0]
+    assert stem in ("cc_bwd", "cc_bwd_f16", "cc_bwd_bf16", "cc_bwd_bf16x6")
+    b = stem == "cc_bwd_bf16" or (stem == "cc_bwd_f16" and c["name"].endswith(",FRONT>") and c["options"].get("front_bwd2", 1) in (0, 2))
+    assert cls["d_h"] == ("B" if b else "A")
+    n_hidden = len(c["hid"])
+    assert C.split_layers(c) == (() if not b else tuple(range(1, n_hidden)) if stem == "cc_bwd_bf16" else (1,))
+    assert C.bound_of("d_x0") == C.bound_of("d_x") == C.bound_of("d_h") == C.bound_of("d_theta") == C.M_GRAD and set(C.M_OF) == {"d_theta:b_out"}
+
+
+def test_both_classes_and_every_two_piece_form_are_present():
+    stems = {(c["name"].split("<")[0], c["family"], C.arith_class(c)["d_h"]) for c in C.CASES}
+    for fam in ("LOOP", "SWP", "WS", "FRONT", "FRONT_WS"):
+        assert ("cc_bwd_bf16", fam, "B") in stems
+    assert ("cc_bwd_f16", "FRONT_WS16", "B") in stems and ("cc_bwd_f16", "FRONT_WS16", "A") in stems and ("cc_bwd_f16", "WS16", "A") in stems
+    assert ("cc_bwd_bf16", "WS16", "B") in stems and ("cc_bwd_bf16", "FRONT_WS16", "B") in stems        # (the fp16 pipeline not eligible)
+    assert ("cc_bwd_bf16x6", "FRONT_P3", "A") in stems and ("cc_bwd", "FP32", "A") in stems
+
+
+def test_two_piece_emulation_changes_only_the_backward_of_the_named_layers():
+    """The emulated net's forward is exact: d_x0 = -f(x0) g is the truth's to the bit.  (Its d_x is not looked at: autograd takes the
+    g_fx tangent back through the split W^T products, where the kernels take it forward through the recompute -- class A.)  d_h and
+    d_theta move by the three-term figure, 1e-6 .. 3e-5, every parameter tensor by less than the flat tolerance."""
+    c = C.BY_ID["rep-SWP"]
+    y, ref = C.yardsticks(c), C.truth(c)
+    assert C.split_layers(c) == (1, 2, 3)
+    i = C.inputs(c)
+    got = C._truth64.backward_reference(C.three_term_net(c), i.x0, i.x, i.h, i.g, i.g_fx, c["n"], chunk=1024)
+    assert torch.equal(got[0], ref[0])
+    for nm in ("d_h", "d_theta"):
+        assert 1e-6 < y["E3"][nm] < 3e-5, (nm, y["E3"][nm])
+    assert all(C.FLOOR <= e < 1e-4 for e in y["E3"]["tensors"])
+    assert len(y["tensors"]) == 2 * (len(c["hid"]) + 1) == len(C.param_sizes(c)) and sum(C.param_sizes(c)) == ref[3].numel()
+
+
+@pytest.mark.parametrize("key", [k for k in C.Z2_CASES if len(k) == 4], ids=lambda k: f"{k[0]}-NL2={k[1]}")
+def test_saved_z2_cases_with_a_bf16_embedding(key):
+    """T1 = 5 and 8, NL2 = 13 and 0, with g_fx: the three-stage name under PLAN_H_BF16, the library offers the pair, and the inputs (bf16
+    values of h) keep their kink margin within the rejection cap."""
+    c = C.Z2_CASES[key]
+    assert c["h_bf16"] and not c["x_bf16"] and c["g_fx"] and not c["x0"] and key[3] == "h-bf16"
+    assert (C.FRONT_W1[key[0]], 13 if (c["hid"][1] + 4) // 4 == 13 else 0) == ({70: 5, 120: 8}[key[0]], key[1])
+    assert _plan_name(c) == c["name"] == f"cc_bwd_bf16<L=2,EDGE=1,LIVE={key[1]},FRONT>"
+    assert _lib.lib().umnn_cc_forward_z2_floats(ctypes.byref(C.desc(c)), c["B"], c["d"], c["E"], c["n"]) > 0
+    i = C.inputs(c)
+    assert i.reject <= C.REJECT_CAP < 1 and i.margin >= C.GUARD
+    assert torch.equal(i.h.to(torch.bfloat16).double(), i.h)
+    assert C.arith_class(c)["d_h"] == "B"
+
+
+def test_the_bf16_embedding_pair_covers_both_ends_of_t1_and_both_nl2():
+    assert sorted(k[:2] for k in C.Z2_CASES if len(k) == 4) == [(70, 0), (70, 13), (120, 0), (120, 13)]
+
+
+def _wrong_slope_run(c, slope):
+    """the reference's own float32 arithmetic on a net whose LeakyReLU slope is `slope`"""
+    import copy
+    i = C.inputs(c)
+    net = copy.deepcopy(i.net)
+    for k, m in enumerate(net.net):
+        if isinstance(m, torch.nn.LeakyReLU):
+            net.net[k] = torch.nn.LeakyReLU(slope)
+    return C._truth64.backward_reference(net, i.x0, i.x, i.h, i.g, i.g_fx, c["n"], dtype=torch.float32, chunk=1024)
+
+
+@pytest.mark.parametrize("id", ["rep-FP32", "fp32-100x2", "ws16-60x60x60x60"])
+def test_the_bounds_bind_where_the_flat_tolerance_does_not(id):
+    """One class A case per family group.  A LeakyReLU slope of 0.01001 instead of 0.01 in the reference's float32 run -- an arithmetic
+    error of an fp32-level kernel -- passes the flat TOL = 1e-4 in all four outputs and fails M_GRAD x E32 in all four; the unchanged
+    float32 run passes both (it defines E32: ratio at most 1)."""
+    c = C.BY_ID[id]
+    assert set(C.arith_class(c).values()) == {"A"}
+    ref, y = C.truth(c), C.yardsticks(c)
+    wrong = C.errors(c, _wrong_slope_run(c, 0.01001), ref)
+    right = C.errors(c, _wrong_slope_run(c, 0.01), ref)
+    for nm in C.OUTPUTS:
+        print(f"{id} {nm}: slope 0.01001 error {wrong[nm]:.2e} = {wrong[nm] / y[nm]:.0f} x E32 {y[nm]:.2e}")
+        assert wrong[nm] < C.TOL
+        assert wrong[nm] > C.M_GRAD * y[nm]
+        assert right[nm] <= y[nm]
+    assert any(a > C.M_GRAD * b for a, b in zip(wrong["tensors"], y["tensors"]))
+    with pytest.raises(AssertionError):
+        C.check_bounds(c, _wrong_slope_run(c, 0.01001), ref)
+    C.check_bounds(c, _wrong_slope_run(c, 0.01), ref)
+
+
+def test_flat_yardsticks_stay_below_the_flat_tolerance():
+    """Over every input set: M_GRAD x the flat yardstick of every output is below TOL, so the new bounds are the tighter ones everywhere
+    (class A: at most 8 x 3.2e-6; class B: at most 8 x 1.2e-5).  Per parameter tensor nothing is capped: a one-element output bias that
+    is a cancelling sum carries its own float32 error."""
+    worst, n_b, over = {}, 0, 0
+    for c in C.CASES:
+        y, cls = C.yardsticks(c), C.arith_class(c)
+        for nm in C.OUTPUTS:
+            worst[cls[nm], nm] = max(worst.get((cls[nm], nm), 0.0), y[nm])
+            assert C.FLOOR <= y[nm] and C.M_GRAD * y[nm] < C.TOL, (c["id"], nm, y[nm])
+        if cls["d_h"] == "B":
+            n_b += 2
+            over += sum(C.M_GRAD * y["E3"][nm] > C.TOL for nm in ("d_h", "d_theta"))
+    print({k: f"{v:.2e}" for k, v in worst.items()}, f"class B outputs: {n_b}, with 8 x E3 above TOL: {over}")
+    assert n_b > 0 and over == 0

@@ -13,6 +13,11 @@ significand); d_theta is always fp32 and keeps TOL.  The inputs keep every hidde
 kink (see the case file), so the bound is an honest one.  Each case prints its four figures next to those of the reference's own
 float32 arithmetic (backward_reference(dtype=float32)) on the same inputs: profiles/bwd_coverage/README.md tabulates them.
 
+On top of TOL every output is held to the bound of its arithmetic class (the case file: arith_class, yardsticks, check_bounds): M = 8
+times E32 for fp32-level outputs, 8 times max(E32, E3) for the two-piece bf16 products, d_theta flat and per parameter tensor; the
+ratios are printed as BWDYARD lines.  bf16-storage cases run a second time on fp32 tensors holding the same values: that launch is held
+to these bounds and the stored one to it, rounded to nearest even, bit for bit.
+
 Kernel-against-kernel bounds are reused: the pipelined loop against the round-2 loop bit-equal in the Leibniz terms and the output
 layer and 2e-6 elsewhere (tests/test_gpu_round3.py::test_software_pipelined_backward_agrees_with_the_round2_loop), the workgroup
 pipeline against the pipelined loop 5e-6 (::test_weight_stationary_backward_agrees_with_the_pipelined_loop_and_fp32: the same terms, a
@@ -53,7 +58,8 @@ def _restore():
     umnn_amd.set_backward_precision(old)
 
 
-_DEVICE, _RUNS = {}, {}
+_DEVICE, _RUNS, _LAUNCHES = {}, {}, {}
+BF16 = torch.bfloat16
 
 
 def _on_device(c, dev):
@@ -73,18 +79,25 @@ def _bname():
     return _lib.lib().umnn_last_kernel_name_of(_lib.PROF_BACKWARD).decode()
 
 
-def _call(c, dev, need=ALL):
+def _widened(t):
+    """the same (bf16-valued) inputs held as fp32 tensors"""
+    return dict(t, **{k: None if t[k] is None else t[k].float() for k in ("x0", "x", "h", "g", "g_fx")})
+
+
+def _call(c, dev, need=ALL, widen=False):
     """One call of the C entry point under the case's options -> [d_x0, d_x, d_h, d_theta] (None where not asked for) and the
-    umnn_launch_count() delta."""
+    umnn_launch_count() delta.  widen: fp32 storage of the same inputs and a null io descriptor."""
     lib = _lib.lib()
     t = _on_device(c, dev)
+    if widen:
+        t = _widened(t)
     B, d, E, n = c["B"], c["d"], c["E"], c["n"]
     nan = lambda like: torch.full_like(like, float("nan"))
     n_params = sum(l.weight.numel() + l.bias.numel() for l in t["spec"].linears)
     outs = [nan(t["x"]) if need[0] else None, nan(t["x"]) if need[1] else None, nan(t["h"]) if need[2] else None,
             torch.full((n_params,), float("nan"), device=dev) if need[3] else None]
     io = None
-    if c["x_bf16"] or c["h_bf16"]:
+    if (c["x_bf16"] or c["h_bf16"]) and not widen:
         io = ctypes.byref(_lib.IoDesc(_lib.DTYPE_BF16 if c["x_bf16"] else _lib.DTYPE_F32, _lib.DTYPE_BF16 if c["h_bf16"] else _lib.DTYPE_F32))
     w, s = device_tables(n, dev)
     desc, keep = I._desc(t["spec"])
@@ -122,7 +135,7 @@ def _run(c, dev):
     if c["id"] not in _RUNS:
         outs, launches = _call(c, dev)
         assert launches == (c["launches"] or launches), (launches, c["launches"])
-        _RUNS[c["id"]] = outs
+        _RUNS[c["id"]], _LAUNCHES[c["id"]] = outs, launches
     return _RUNS[c["id"]]
 
 
@@ -145,7 +158,26 @@ def _against_truth(c, outs, dev, tag=None):
     print(f"BWDCOV|{c['part']}|{c['family']}|{tag or c['id']}|{fmt(err)}|{fmt(err32)}")
     for nm, e, b in zip(NAMES, err, _bounds(c)):
         assert e is None or e < b, (c["id"], nm, e, b)
+    # on top: M x the yardstick of the output's arithmetic class.  (Outputs stored as bf16 carry the storage rounding: their case's
+    # widened launch is held to these bounds, and the stored launch to that one bit for bit -- _widen_and_round.)
+    if not (c["x_bf16"] or c["h_bf16"]):
+        C.check_bounds(c, outs, ref, tag)
     return err
+
+
+def _widen_and_round(c, stored, wide, what):
+    """io_ld widens exactly and io_st rounds to nearest even once (cc_common.h): the launch on bf16 storage holds, bit for bit, the
+    fp32-storage launch on the same values rounded to bf16 -- d_x0 and d_x under x storage, d_h under h storage --, and the same d_theta."""
+    as_stored = (c["x_bf16"], c["x_bf16"], c["h_bf16"], False)
+    for nm, a, b, r in zip(NAMES, stored, wide, as_stored):
+        if a is None:
+            continue
+        want = b.to(BF16) if r else b
+        assert a.dtype == want.dtype
+        if not torch.equal(a, want):
+            bad = a != want
+            units = (a.view(torch.int16 if r else torch.int32).int() - want.view(torch.int16 if r else torch.int32).int()).abs().max()
+            raise AssertionError(f"{c['id']}: {what}: {nm} differs in {int(bad.sum())} of {a.numel()} elements, by up to {int(units)} units")
 
 
 def _scaled(a, b):
@@ -160,6 +192,12 @@ def test_case(c, dev):
     for nm, a, b in zip(NAMES, outs, again):
         assert torch.equal(a, b), f"{nm}: a second call is not bit-equal"
     _against_truth(c, outs, dev)
+    if c["x_bf16"] or c["h_bf16"]:
+        wide, launches = _call(c, dev, widen=True)            # (asserts the same noted name)
+        assert launches == _LAUNCHES[c["id"]], (launches, _LAUNCHES[c["id"]])
+        big = c["B"] * c["d"] >= 16384
+        C.check_bounds(c, wide, C.truth(c, device=dev if big else "cpu"), tag=c["id"] + "-widened")
+        _widen_and_round(c, outs, wide, "bf16 storage against the widened launch, rounded")
 
 
 # ---- part 2: the need masks ------------------------------------------------------------------------------------------------------
@@ -228,7 +266,7 @@ def test_stage_c_choices_agree(family, w1, live, b2, dev):
         assert _scaled(a, b) < WS_VS_SWP, (c["id"], nm, _scaled(a, b))
 
 
-@pytest.mark.parametrize("key", list(C.Z2_CASES), ids=lambda k: f"{k[0]}-NL2={k[1]}-{'g_fx' if k[2] else 'no-g_fx'}")
+@pytest.mark.parametrize("key", [k for k in C.Z2_CASES if len(k) == 3], ids=lambda k: f"{k[0]}-NL2={k[1]}-{'g_fx' if k[2] else 'no-g_fx'}")
 def test_saved_z2_against_the_recompute(key, dev):
     """hip_flow_block(save_z2=True) leaves hidden layer 2's pre-activations; hip_backward(z2_saved=...) skips stage A (all of it, or
     all but the tangent element of the g_fx term).  Every T1 x NL2: the name stays, both calls meet the truth, and they agree with
@@ -257,3 +295,168 @@ def test_d_h_kernel_by_name(key, dev):
     outs, _ = _call(c, dev, (0, 0, 1, 0))
     assert _lib.lib().umnn_last_kernel_name_of(_lib.PROF_FINISH).decode() == name
     assert torch.equal(outs[2], _run(c, dev)[2])
+
+
+# ---- part 4: the saved-z2 pair with a bf16 embedding, at the C entries -------------------------------------------------------------
+def _saved_pair(c, dev, widen, h0=None):
+    """umnn_flow_stack_block_forward_save_io into a z_2 buffer of exactly umnn_cc_forward_z2_floats floats, then
+    umnn_cc_backward_saved_io on it (h0 given: umnn_cc_backward_block_io, which adds h0 [B, d] into embedding row 0 of d_h before the
+    store), both with the case's io descriptor (widen: the same values as fp32 tensors, io = NULL).  Outputs
+    pre-filled with NaN, the workspace exactly sized and followed by the byte pattern, NaN behind z_2 -> ([None, d_x, d_h, d_theta],
+    z_2, the backward's launch count)."""
+    lib = _lib.lib()
+    t = _widened(_on_device(c, dev)) if widen else _on_device(c, dev)
+    B, d, E, n = c["B"], c["d"], c["E"], c["n"]
+    hb = c["h_bf16"] and not widen
+    io = ctypes.byref(_lib.IoDesc(_lib.DTYPE_F32, _lib.DTYPE_BF16)) if hb else None
+    assert t["x"].dtype == torch.float32 and t["h"].dtype == (BF16 if hb else torch.float32) and t["x0"] is None
+    nan = lambda like: torch.full_like(like, float("nan"))
+    n_params = sum(l.weight.numel() + l.bias.numel() for l in t["spec"].linears)
+    w, s = device_tables(n, dev)
+    desc, keep = I._desc(t["spec"])
+    scaling = torch.zeros(d, device=dev)
+    fwd = [nan(t["x"]) for _ in range(4)]
+    outs = [None, nan(t["x"]), nan(t["h"]), torch.full((n_params,), float("nan"), device=dev)]
+    pattern = (torch.arange(GUARD_BYTES, device=dev) * 37 + 11).to(torch.uint8)
+    with _lib.options(**c["options"]), torch.cuda.device(dev):
+        nfl = int(lib.umnn_cc_forward_z2_floats(ctypes.byref(desc), B, d, E, n))
+        assert nfl == -(-B * d // 16) * (n + 1) * ((c["hid"][1] + 4) // 4) * 64
+        z2 = torch.full((nfl + GUARD_BYTES,), float("nan"), device=dev)
+        rc = lib.umnn_flow_stack_block_forward_save_io(ctypes.byref(desc), io, _ptr(t["x"]), _ptr(t["h"]), _ptr(scaling), _ptr(w), _ptr(s), n, B, d,
+                                                       E, 0, None, *(_ptr(o) for o in fwd), _ptr(z2), nfl, _stream(dev))
+        _lib.check(rc, "umnn_flow_stack_block_forward_save_io")
+        torch.cuda.synchronize()
+        assert bool(torch.isfinite(z2[:nfl]).all()) and bool(torch.isnan(z2[nfl:]).all()), "z_2: not all written, or written behind its size"
+        assert all(bool(torch.isfinite(o).all()) for o in fwd)
+        nbytes = int(lib.umnn_cc_backward_workspace_bytes(ctypes.byref(desc), B, d, E))
+        assert nbytes > 0
+        ws = torch.empty(nbytes + GUARD_BYTES, device=dev, dtype=torch.uint8)
+        ws[nbytes:] = pattern
+        before = lib.umnn_launch_count()
+        head = (ctypes.byref(desc), io, _ptr(t["x"]), _ptr(t["h"]), _ptr(t["g"]), _ptr(t["g_fx"]), _ptr(w), _ptr(s), n, B, d, E)
+        tail = (*(_ptr(o) for o in outs[1:]), _ptr(z2), nfl, ctypes.c_void_p(ws.data_ptr()), nbytes, _stream(dev))
+        rc = lib.umnn_cc_backward_saved_io(*head, *tail) if h0 is None else lib.umnn_cc_backward_block_io(*head, _ptr(h0), *tail)
+        _lib.check(rc, "umnn_cc_backward_saved_io / _block_io")
+        torch.cuda.synchronize()
+        launches = lib.umnn_launch_count() - before
+    assert _bname() == c["name"], (_bname(), c["name"])
+    assert torch.equal(ws[nbytes:], pattern), "the call wrote behind umnn_cc_backward_workspace_bytes()"
+    assert bool(torch.isnan(z2[nfl:]).all())
+    for nm, o in zip(NAMES[1:], outs[1:]):
+        assert bool(torch.isfinite(o).all()), f"{nm}: an element was not written, or is not finite"
+    return outs, z2[:nfl], launches
+
+
+@pytest.mark.parametrize("key", [k for k in C.Z2_CASES if len(k) == 4], ids=lambda k: f"{k[0]}-NL2={k[1]}-g_fx-{k[3]}")
+def test_saved_z2_pair_with_a_bf16_embedding(key, dev):
+    """The MNIST-shaped training path at the C entries, T1 = 5 and 8, NL2 = 13 and 0: the three-stage name; the pair on fp32 storage of
+    the same values within the class B bounds of the truth; the pair on bf16 storage leaves the same z_2 and holds that pair's d_h
+    rounded to bf16, its d_x and d_theta, bit for bit; saved against recomputed (umnn_cc_backward_io, fp32 storage of the same values:
+    two stored d_h may differ by a whole bf16 unit) within 5e-6."""
+    c = C.Z2_CASES[key]
+    stored, z2_stored, launches = _saved_pair(c, dev, widen=False)
+    wide, z2_wide, launches_wide = _saved_pair(c, dev, widen=True)
+    assert launches == launches_wide and torch.equal(z2_stored, z2_wide)
+    assert stored[2].dtype == BF16 and wide[2].dtype == torch.float32
+    ref = C.truth(c)
+    err = _errors(wide, ref)
+    print(f"BWDCOV|{c['part']}|{c['family']}|{c['id']}-saved-widened|" + "|".join("-" if v is None else f"{v:.3e}" for v in err))
+    for nm, e in zip(NAMES, err):
+        assert e is None or e < TOL, (c["id"], nm, e)
+    C.check_bounds(c, wide, ref, tag=c["id"] + "-saved-widened")
+    _widen_and_round(c, stored, wide, "the saved pair on bf16 storage against the widened pair, rounded")
+    for nm, e, b in zip(NAMES, _errors(stored, ref), _bounds(c)):
+        assert e is None or e < b, (c["id"], nm, e, b)
+    recomputed, _ = _call(c, dev, widen=True)
+    for nm, a, b in zip(NAMES[1:], wide[1:], recomputed[1:]):
+        assert _scaled(a, b) < WS_VS_SWP, (nm, _scaled(a, b))
+    for nm, a, b in ((NAMES[1], stored[1], _run(c, dev)[1]), (NAMES[3], stored[3], _run(c, dev)[3])):
+        assert _scaled(a, b) < WS_VS_SWP, (nm, _scaled(a, b))
+    # the block entry: the h_0 cotangent goes into embedding row 0 of d_h in fp32, before the one store
+    h0 = _on_device(c, dev)["g"]
+    wide_h0, _, n_wide = _saved_pair(c, dev, widen=True, h0=h0)
+    stored_h0, _, n_stored = _saved_pair(c, dev, widen=False, h0=h0)
+    assert n_wide == n_stored == launches
+    _plus_h0(c, wide, wide_h0, h0)
+    _widen_and_round(c, stored_h0, wide_h0, "the block entry on bf16 storage against the widened one, rounded")
+
+
+def _plus_h0(c, plain, with_h0, h0):
+    """d_h with the h_0 term is d_h without it plus h0 in embedding row 0 (one fp32 addition: the same bits), every other output the same"""
+    want = plain[2].clone()
+    want.view(c["B"], c["E"], c["d"])[:, 0, :] += h0
+    assert torch.equal(with_h0[2], want), "d_h"
+    assert all(a is None and b is None or torch.equal(a, b) for k, (a, b) in enumerate(zip(plain, with_h0)) if k != 2)
+
+
+def _block_call(c, dev, h0, need=ALL):
+    """umnn_cc_backward_block_io without a saved z_2 (lower limit 0; the case's x0 is not used), exactly-sized workspace and guard."""
+    lib = _lib.lib()
+    t = _on_device(c, dev)
+    assert not (c["x_bf16"] or c["h_bf16"])
+    B, d, E, n = c["B"], c["d"], c["E"], c["n"]
+    nan = lambda like: torch.full_like(like, float("nan"))
+    n_params = sum(l.weight.numel() + l.bias.numel() for l in t["spec"].linears)
+    outs = [None, nan(t["x"]) if need[1] else None, nan(t["h"]) if need[2] else None, torch.full((n_params,), float("nan"), device=dev) if need[3] else None]
+    w, s = device_tables(n, dev)
+    desc, keep = I._desc(t["spec"])
+    pattern = (torch.arange(GUARD_BYTES, device=dev) * 37 + 11).to(torch.uint8)
+    with _lib.options(**c["options"]), torch.cuda.device(dev):
+        nbytes = int(lib.umnn_cc_backward_workspace_bytes(ctypes.byref(desc), B, d, E))
+        ws = torch.empty(nbytes + GUARD_BYTES, device=dev, dtype=torch.uint8)
+        ws[nbytes:] = pattern
+        rc = lib.umnn_cc_backward_block_io(ctypes.byref(desc), None, _ptr(t["x"]), _ptr(t["h"]), _ptr(t["g"]), _ptr(t["g_fx"]), _ptr(w), _ptr(s), n, B, d,
+                                           E, _ptr(h0), *(_ptr(o) for o in outs[1:]), None, 0, ctypes.c_void_p(ws.data_ptr()), nbytes, _stream(dev))
+        _lib.check(rc, "umnn_cc_backward_block_io")
+        torch.cuda.synchronize()
+    assert torch.equal(ws[nbytes:], pattern), "the call wrote behind umnn_cc_backward_workspace_bytes()"
+    assert all(o is None or bool(torch.isfinite(o).all()) for o in outs)
+    return outs
+
+
+# ---- the fused training block on a bf16 embedding: d_h is rounded once, row 0 included ----------------------------------------------
+@pytest.mark.parametrize("reverse_z", [False, True], ids=["forward-z", "reverse-z"])
+def test_flow_block_vjp_rounds_d_h_once(reverse_z, dev):
+    """FlowBlockTransform (B = 41, d = 3, E = 4, 50-50-50-50, n = 6; every g_z and g_log_jac non-zero) with the embedding h in bf16, and
+    with the same values in fp32: z carries h_0 = embedding row 0, so d_h row 0 is the quadrature's plus the cotangent of F.  The bf16
+    run's d_h is the fp32 run's rounded to bf16 once, bit for bit, in every row; d_x and the parameter gradients are the same bits."""
+    c = C.BY_ID["rep-SWP-h-bf16"]
+    assert (c["B"], c["d"], c["E"], c["hid"], c["n"]) == (41, 3, 4, [50] * 4, 6)
+    t = _on_device(c, dev)
+    B, d, E = c["B"], c["d"], c["E"]
+    scaling = torch.linspace(-0.3, 0.3, d, device=dev)
+    gz, glj = t["g"], t["g_fx"]
+    assert bool((gz != 0).all()) and bool((glj != 0).all())
+    params = list(t["net"].parameters())
+
+    def run(h):
+        x, h = t["x"].clone().requires_grad_(), h.clone().requires_grad_()
+        z, lj = I.FlowBlockTransform.apply(x, t["net"], h, scaling, c["n"], reverse_z, None, *params)
+        grads = torch.autograd.grad((z, lj), (x, h, *params), (gz, glj))
+        assert umnn_amd.path_taken() == "hip"
+        return grads, _bname()
+
+    (dx16, dh16, *dth16), name16 = run(t["h"])
+    (dx32, dh32, *dth32), name32 = run(t["h"].float())
+    assert name16 == name32 and dh16.dtype == BF16 and dh32.dtype == torch.float32
+    assert torch.equal(dx16, dx32), "d_x"
+    assert all(torch.equal(a, b) for a, b in zip(dth16, dth32)), "parameter gradients"
+    bad = (dh16 != dh32.to(BF16)).view(B, E, d)
+    rows = [int(bad[:, e, :].sum()) for e in range(E)]
+    print(f"d_h elements that are not the fp32 run's rounded once, per embedding row: {rows} of {B * d} each")
+    assert rows == [0] * E, rows
+
+
+@pytest.mark.parametrize("key", list(C.DH), ids=lambda k: f"{k[0]}-E{k[1]}")
+def test_d_h_kernels_add_the_h0_cotangent_before_the_store(key, dev):
+    """umnn_cc_backward_block_io on both d_h kernels (by name), every E of part 5 (one, a tile less one, a tile, a tile and one, five
+    tiles, above the matrix-core kernel's limit), integral counts that end a tile early, exactly and one in: with h0 the call returns the
+    d_h of the call without it plus h0 in embedding row 0 and nowhere else -- the same bits as the fp32 addition --, and the same d_x and
+    d_theta; d_h alone holds the bits of the all-outputs call."""
+    c, name = C.DH[key]
+    h0 = _on_device(c, dev)["g"]
+    plain, with_h0 = _block_call(c, dev, None), _block_call(c, dev, h0)
+    _plus_h0(c, plain, with_h0, h0)
+    alone = _block_call(c, dev, h0, (0, 0, 1, 0))
+    assert _lib.lib().umnn_last_kernel_name_of(_lib.PROF_FINISH).decode() == name
+    assert torch.equal(alone[2], with_h0[2])

@@ -128,6 +128,8 @@ SIGNATURES = {
                                                              _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_saved_io": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.POINTER(IoDesc), _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                                  _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _ll, _fp, _ll, _fp]),
+    "umnn_cc_backward_block_io": (ctypes.c_int, [ctypes.POINTER(MlpDesc), ctypes.POINTER(IoDesc), _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
+                                                 _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp, _ll, _fp]),
     "umnn_flow_block_cotangents": (ctypes.c_int, [_fp, _fp, _fp, _fp, _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp]),
     "umnn_flow_ll_forward": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp]),
     "umnn_flow_ll_backward": (ctypes.c_int, [_fp, _fp, _ll, ctypes.c_int, _fp, _fp, _fp]),

@@ -349,10 +349,11 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_kernel(const BwdArgs a) 
     }
 }
 
-// d_h[b, e*d+i] = sum_f W1[f][1+e] dc[q][f]
+// d_h[b, e*d+i] = sum_f W1[f][1+e] dc[q][f]  (+ h0_cot[b, i] in embedding row e = 0 when h0_cot is non-null: the cotangent a flow block's
+// z = exp(s) (F + h_0) sends to h_0, added in fp32 before the one store, so that a bf16 d_h is rounded once)
 __global__ __launch_bounds__(256) void cc_bwd_dh_kernel(const float* __restrict__ dc, const float* __restrict__ W0,
                                                         float* __restrict__ dh, long long NI, int d, int E, int H1, int qpb,
-                                                        int h_bf16) {
+                                                        int h_bf16, const float* __restrict__ h0_cot) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* sW = sm;                       // [H1][E]
     float* sdc = sm + H1 * E;             // [qpb][H1+1], qpb = integrals per block (64, or 16 for small batches)
@@ -370,6 +371,7 @@ __global__ __launch_bounds__(256) void cc_bwd_dh_kernel(const float* __restrict_
         float s = 0.f;
         for (int f = 0; f < H1; ++f) s = fmaf(sW[f * E + e], sdc[ql * (H1 + 1) + f], s);
         const long long q = q0 + ql, bi = q / d;
+        if (h0_cot && e == 0) s += h0_cot[q];
         io_st(dh, bi * ((long long)E * d) + (long long)e * d + (q - bi * d), s, h_bf16);
     }
 }
@@ -381,7 +383,8 @@ __global__ __launch_bounds__(256) void cc_bwd_dh_kernel(const float* __restrict_
 // 16 te + 4 g + r) is stored with 64-byte runs along the integrals.  The first version above reads two LDS words per FMA and sat
 // at 1.6 TB/s of dc + d_h traffic (101 us per C3 call against 165 MB); this one is bound by that stream.
 __global__ __launch_bounds__(256) void cc_bwd_dh_mfma_kernel(const float* __restrict__ dc, const float* __restrict__ W0,
-                                                             float* __restrict__ dh, long long NI, int d, int E, int H1, int h_bf16) {
+                                                             float* __restrict__ dh, long long NI, int d, int E, int H1, int h_bf16,
+                                                             const float* __restrict__ h0_cot) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     const int KS = (H1 + 3) / 4, TE = (E + 15) / 16;
     const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, p = lane & 15;
@@ -412,6 +415,7 @@ __global__ __launch_bounds__(256) void cc_bwd_dh_mfma_kernel(const float* __rest
         if (ok) {
             const long long bi = q / d;
             const long long base = bi * ((long long)E * d) + (q - bi * d);
+            if (h0_cot && g == 0) acc[0][0] += h0_cot[q];        // (embedding row e = 0: tile 0, lane group 0, register 0)
 #pragma unroll
             for (int te = 0; te < 5; ++te)
                 if (te < TE) {
@@ -576,13 +580,17 @@ static const bwd_kernel_t kBwdFp32Kernels[] = { UMNN_BWD_FP32_VARIANTS(BWD_FP32_
 static_assert(sizeof(kBwdFp32Kernels) / sizeof(kBwdFp32Kernels[0]) == kBwdFp32Count, "one kernel per variant");
 
 // d_h through cc_bwd_dh_kernel (cc_host.h: the multi-output backward finishes with it too).  Notes no launch: that is the caller's.
-int umnn_launch_bwd_dh(const float* dc, const float* W0, float* dh, long long NI, int d, int E, int H1, int h_bf16, hipStream_t stream) {
+static int launch_bwd_dh(const float* dc, const float* W0, float* dh, long long NI, int d, int E, int H1, int h_bf16, const float* h0_cot,
+                         hipStream_t stream) {
     const int qpb = NI / 64 < 2LL * umnn_num_cus() ? 16 : 64;      // integrals per workgroup
     const size_t sm = ((size_t)H1 * E + qpb * (H1 + 1)) * sizeof(float);
     const unsigned nb = (unsigned)((NI + qpb - 1) / qpb);
     if (int rc = umnn_allow_lds((const void*)cc_bwd_dh_kernel, sm)) return rc;
-    hipLaunchKernelGGL(cc_bwd_dh_kernel, dim3(nb), dim3(256), sm, stream, dc, W0, dh, NI, d, E, H1, qpb, h_bf16);
+    hipLaunchKernelGGL(cc_bwd_dh_kernel, dim3(nb), dim3(256), sm, stream, dc, W0, dh, NI, d, E, H1, qpb, h_bf16, h0_cot);
     return 0;
+}
+int umnn_launch_bwd_dh(const float* dc, const float* W0, float* dh, long long NI, int d, int E, int H1, int h_bf16, hipStream_t stream) {
+    return launch_bwd_dh(dc, W0, dh, NI, d, E, H1, h_bf16, nullptr, stream);
 }
 
 static BwdOptions bwd_options() {
@@ -649,7 +657,7 @@ static int backward_impl(const umnn_mlp* net, const umnn_io* io, const void* x0_
                          const void* g_, const void* g_fx_,
                          const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
                          void* dx0_, void* dx_, void* dh_, float* dtheta,
-                         void* workspace, long long workspace_bytes, void* stream_, const float* z2_saved);
+                         void* workspace, long long workspace_bytes, void* stream_, const float* z2_saved, const float* h0_cot = nullptr);
 extern "C" int umnn_cc_backward_io(const umnn_mlp* net, const umnn_io* io, const void* x0_, const void* x_, const void* h_,
                                    const void* g_, const void* g_fx_,
                                    const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
@@ -685,11 +693,22 @@ extern "C" int umnn_cc_backward_saved_io(const umnn_mlp* net, const umnn_io* io,
     return backward_impl(net, io, nullptr, x, h, g, g_fx, cc_w, cc_s, nb_steps, B, d, E, 0, nullptr, dx, dh, dtheta, workspace,
                          workspace_bytes, stream_, z2_saved);
 }
+// The backward of one flow block: umnn_cc_backward_saved_io (z2_saved null: umnn_cc_backward_io with lower limit 0) whose d_h finishing
+// kernel adds h0_cot [B, d] (fp32, nullable) into embedding row 0 before its store.
+extern "C" int umnn_cc_backward_block_io(const umnn_mlp* net, const umnn_io* io, const void* x, const void* h, const void* g, const void* g_fx,
+                                         const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, const float* h0_cot,
+                                         void* dx, void* dh, float* dtheta, const float* z2_saved, long long z2_floats,
+                                         void* workspace, long long workspace_bytes, void* stream_) {
+    if (z2_saved)
+        if (int rc = check_z2_saved(net, B, d, E, nb_steps, &z2_saved, z2_floats)) return rc;
+    return backward_impl(net, io, nullptr, x, h, g, g_fx, cc_w, cc_s, nb_steps, B, d, E, 0, nullptr, dx, dh, dtheta, workspace,
+                         workspace_bytes, stream_, z2_saved, h0_cot);
+}
 static int backward_impl(const umnn_mlp* net, const umnn_io* io, const void* x0_, const void* x_, const void* h_,
                          const void* g_, const void* g_fx_,
                          const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
                          void* dx0_, void* dx_, void* dh_, float* dtheta,
-                         void* workspace, long long workspace_bytes, void* stream_, const float* z2_saved) {
+                         void* workspace, long long workspace_bytes, void* stream_, const float* z2_saved, const float* h0_cot) {
     const float *x0 = (const float*)x0_, *x = (const float*)x_, *h = (const float*)h_, *g = (const float*)g_, *g_fx = (const float*)g_fx_;
     float *dx0 = (float*)dx0_, *dx = (float*)dx_, *dh = (float*)dh_;
     if (int rc = umnn_check_io(io)) return rc;
@@ -759,10 +778,11 @@ static int backward_impl(const umnn_mlp* net, const umnn_io* io, const void* x0_
             const long long want = (groups + 3) / 4, cap = 8LL * umnn_num_cus();
             const unsigned nb = (unsigned)(want < cap ? want : cap);
             if (int rc = umnn_allow_lds((const void*)cc_bwd_dh_mfma_kernel, sm)) return rc;
-            hipLaunchKernelGGL(cc_bwd_dh_mfma_kernel, dim3(nb), dim3(256), sm, stream, a.dc, net->W[0], dh, a.NI, d, E, H1, a.h_bf16);
+            hipLaunchKernelGGL(cc_bwd_dh_mfma_kernel, dim3(nb), dim3(256), sm, stream, a.dc, net->W[0], dh, a.NI, d, E, H1, a.h_bf16,
+                               h0_cot);
             umnn_note_launch("cc_bwd_dh<mfma>");
         } else {
-            if (int rc = umnn_launch_bwd_dh(a.dc, net->W[0], dh, a.NI, d, E, H1, a.h_bf16, stream)) return rc;
+            if (int rc = launch_bwd_dh(a.dc, net->W[0], dh, a.NI, d, E, H1, a.h_bf16, h0_cot, stream)) return rc;
             umnn_note_launch("cc_bwd_dh");
         }
     }

@@ -618,9 +618,18 @@ def hip_flow_ll_block(spec, x, h, scaling, nb_steps, reverse_z, first, last, ll,
     return z
 
 
-def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None):
+def _add_h0(dh, h0_cot, d):
+    """d_h + the h_0 term in embedding row 0 (z carries h_0 = embedding row 0, UMNNMAF.py:80), in fp32, in dh's dtype"""
+    out = dh.float() if dh.dtype != torch.float32 else dh
+    out.view(dh.shape[0], -1, d)[:, 0, :].add_(h0_cot)
+    return out.to(dh.dtype)
+
+
+def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None, h0_cot=None):
     """-> (dx0, dx, dh, dtheta_flat); entries are None where need[...] is False.  dx0/dx come back in x's dtype, dh in
-    h's, dtheta in fp32 (the weights' dtype).  inv_f: the operator integrated 1/f (ParallelNeuralIntegral.py:58-59,70-72)."""
+    h's, dtheta in fp32 (the weights' dtype).  inv_f: the operator integrated 1/f (ParallelNeuralIntegral.py:58-59,70-72).
+    h0_cot [B,d] (a flow block's backward: lower limit 0): added to embedding row 0 of dh by the kernel that stores dh
+    (umnn_cc_backward_block_io), so that a bf16 dh is rounded once."""
     lib = _lib.lib()
     B, d, E = _shape(spec, x, h)
     x_dtype, h_dtype = x.dtype, h.dtype
@@ -638,7 +647,12 @@ def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True
         ws = torch.empty(max(int(nbytes), 4), device=x.device, dtype=torch.uint8)
         head = (ctypes.byref(desc), io)
         mid = (_ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s), int(nb_steps), B, d, E)
-        if z2_saved is not None and not inv_f and x0 is None and not need[0]:      # (that entry point has no x0 and no d_x0 output)
+        h0 = _as(h0_cot, torch.float32) if dh is not None else None
+        if h0 is not None and not inv_f and x0 is None and not need[0]:
+            rc = lib.umnn_cc_backward_block_io(*head, *mid, _ptr(h0), _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved),
+                                               0 if z2_saved is None else int(z2_saved.numel()), _ptr(ws), int(nbytes), _stream(x.device))
+            h0 = None
+        elif z2_saved is not None and not inv_f and x0 is None and not need[0]:    # (that entry point has no x0 and no d_x0 output)
             rc = lib.umnn_cc_backward_saved_io(*head, *mid, _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved), int(z2_saved.numel()),
                                                _ptr(ws), int(nbytes), _stream(x.device))
         else:
@@ -649,6 +663,8 @@ def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True
     if x_dtype != xd:
         dx0 = dx0.to(x_dtype) if dx0 is not None else None
         dx = dx.to(x_dtype) if dx is not None else None
+    if h0 is not None:
+        dh = _add_h0(dh, h0, d)
     if h_dtype != hd and dh is not None:
         dh = dh.to(h_dtype)
     return dx0, dx, dh, dtheta
@@ -762,17 +778,23 @@ def aten_backward(integrand, x0, x, h, g, nb_steps, inv_f=False):
     return dtheta, dh
 
 
-def quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None):
+def quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None,
+                        h0_cot=None):
     """The quadrature backward of every operator -> (dx0, dx, dh, dtheta_flat), None where ``need`` says so: the HIP kernels when
-    ``spec`` (None: the forward ran on ATen) has a backward kernel, else ``aten_vjp`` on ``integrand``.  x0 None: lower limit 0."""
+    ``spec`` (None: the forward ran on ATen) has a backward kernel, else ``aten_vjp`` on ``integrand``.  x0 None: lower limit 0.
+    ``h0_cot`` [B,d] (single-output operators): a flow block's h_0 term, added to embedding row 0 of dh -- inside the HIP launch that
+    stores dh, in fp32 torch ops on the ATen path."""
     need = (bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3]))
-    if spec is not None and n_out_of(spec) > 1:
-        if _multi_kernels_ok(spec):
-            return hip_backward_multi(spec, x0, x, h, g, nb_steps, need, inv_f=inv_f, g_fx=g_fx)
-    elif spec is not None and _hip_backward_ok(spec, x, h):
-        return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f=inv_f, z2_saved=z2_saved)
-    out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
-    return tuple(t if n else None for t, n in zip(out, need))
+    if spec is not None and n_out_of(spec) == 1 and _hip_backward_ok(spec, x, h):
+        return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f=inv_f, z2_saved=z2_saved, h0_cot=h0_cot)
+    if spec is not None and n_out_of(spec) > 1 and _multi_kernels_ok(spec):
+        out = hip_backward_multi(spec, x0, x, h, g, nb_steps, need, inv_f=inv_f, g_fx=g_fx)
+    else:
+        out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
+        out = tuple(t if n else None for t, n in zip(out, need))
+    if h0_cot is not None and out[2] is not None:
+        out = (out[0], out[1], _add_h0(out[2], h0_cot, x.shape[1]), out[3])
+    return out
 
 
 def split_flat(flat, shapes, needed):
@@ -949,12 +971,10 @@ def hip_flow_ll_backward(z, g_ll, need_z, need_lj):
 
 def flow_block_vjp(spec, integrand, x, h, fx, scaling, gz, glj, nb_steps, reverse_z, need, z2_saved=None):
     """Backward of a fused block -> (dx, dh, dtheta_flat) for ``need``: one elementwise launch (cotangents of F and f_x from those of z
-    and log_jac), the quadrature backward, and the h_0 term added into d_h."""
-    B, d = x.shape
+    and log_jac), and the quadrature backward, whose d_h kernel also adds the h_0 term (z carries h_0 = embedding row 0,
+    UMNNMAF.py:80: the cotangent of F is that of h_0 too) before it stores d_h -- a bf16 d_h is rounded once, row 0 included."""
     gF, gfx = hip_flow_block_cotangents(gz, glj, fx, scaling, reverse_z)
-    _, dx, dh, dtheta = quadrature_backward(spec, integrand, None, x, h, gF, gfx, nb_steps, (False, *need), z2_saved=z2_saved)
-    if dh is not None:
-        dh.view(B, -1, d)[:, 0, :].add_(gF)            # z carries h_0 = embedding row 0 (UMNNMAF.py:80)
+    _, dx, dh, dtheta = quadrature_backward(spec, integrand, None, x, h, gF, gfx, nb_steps, (False, *need), z2_saved=z2_saved, h0_cot=gF)
     return dx, dh, dtheta
 
 
