@@ -286,6 +286,38 @@ def test_saved_z2_against_the_recompute(key, dev):
         assert _scaled(a, b) < WS_VS_SWP, (nm, _scaled(a, b))
 
 
+def test_hip_backward_with_a_saved_z2_is_the_saved_entry(dev):
+    """integral.hip_backward(z2_saved=z2) without an h_0 cotangent goes through umnn_cc_backward_block_io with h0_cot = NULL.  The
+    entry it called before, umnn_cc_backward_saved_io, called here directly on the same tensors and workspace size (T1 = 5, NL2 = 13:
+    the smallest saved-z_2 case): the same kernel name and d_x, d_h, d_theta bit for bit."""
+    c = C.Z2_CASES[70, 13, True]
+    t = _on_device(c, dev)
+    B, d, E, n = c["B"], c["d"], c["E"], c["n"]
+    lib = _lib.lib()
+    nan = lambda like: torch.full_like(like, float("nan"))
+    with _lib.options(**c["options"]), torch.cuda.device(dev):
+        z2 = I.hip_flow_block(t["spec"], t["x"], t["h"], torch.zeros(d, device=dev), n, save_z2=True)[4]
+        assert z2 is not None, "umnn_cc_forward_z2_floats says the pair does not apply"
+        wrapped = I.hip_backward(t["spec"], None, t["x"], t["h"], t["g"], t["g_fx"], n, need=(False, True, True, True), z2_saved=z2)
+        torch.cuda.synchronize()
+        name = _bname()
+        n_params = sum(l.weight.numel() + l.bias.numel() for l in t["spec"].linears)
+        outs = [nan(t["x"]), nan(t["h"]), torch.full((n_params,), float("nan"), device=dev)]
+        w, s = device_tables(n, dev)
+        desc, keep = I._desc(t["spec"])
+        nbytes = int(lib.umnn_cc_backward_workspace_bytes(ctypes.byref(desc), B, d, E))
+        assert nbytes > 0
+        ws = torch.empty(nbytes, device=dev, dtype=torch.uint8)
+        rc = lib.umnn_cc_backward_saved_io(ctypes.byref(desc), None, _ptr(t["x"]), _ptr(t["h"]), _ptr(t["g"]), _ptr(t["g_fx"]), _ptr(w), _ptr(s),
+                                           n, B, d, E, *(_ptr(o) for o in outs), _ptr(z2), int(z2.numel()), _ptr(ws), nbytes, _stream(dev))
+        _lib.check(rc, "umnn_cc_backward_saved_io")
+        torch.cuda.synchronize()
+    assert name == _bname() == c["name"], (name, _bname(), c["name"])
+    assert wrapped[0] is None
+    for nm, a, b in zip(NAMES[1:], wrapped[1:], outs):
+        assert a.dtype == b.dtype and torch.equal(a, b), nm
+
+
 # ---- part 5: the d_h kernels by name ---------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("key", list(C.DH), ids=lambda k: f"{k[0]}-E{k[1]}")
 def test_d_h_kernel_by_name(key, dev):

@@ -9,8 +9,8 @@ from torch._subclasses.fake_tensor import FakeTensorMode
 from torch.fx.experimental.symbolic_shapes import DimDynamic, ShapeEnv, StatelessSymbolicContext
 
 import umnn_amd
-from umnn_amd import integral, made, ops
-from umnn_amd.nets import IntegrandNetwork
+from umnn_amd import _lib, integral, made, ops
+from umnn_amd.nets import IntegrandNN, IntegrandNetwork
 from umnn_amd.quadrature import device_tables
 
 SCHEMA_ARGS = {
@@ -158,6 +158,56 @@ def test_fake_shapes_with_a_symbolic_batch():
         assert t.shape[1] == d
     assert isinstance(ll.shape[0], torch.SymInt) and ll.shape[0] == B and ll2.shape[0] == B
     assert dh.shape[0] == B and dh.shape[1] == E * d
+
+
+@pytest.mark.parametrize("with_x0", [False, True])
+def test_the_three_backward_fakes_agree(with_x0):
+    """cc_backward, cc_backward_multi and cc_backward_multi_fx share one fake: at B = 4, d = 1, E = 2 (a single-output and a K = 2 net on
+    the same hidden layers) every ``need`` mask gives the three the same shapes and dtypes, and empty tensors where need is False."""
+    B, E, K = 4, 2, 2
+    with FakeTensorMode():
+        x, h = torch.empty(B, 1, device="cuda"), torch.empty(B, E, device="cuda", dtype=torch.bfloat16)
+        x0 = torch.empty(B, 1, device="cuda") if with_x0 else None
+        W, b = _net(E, [20, 20])
+        WK, bK = W[:-1] + [torch.empty(K, 20, device="cuda")], b[:-1] + [torch.empty(K, device="cuda")]
+        g, gK = torch.empty(B, 1, device="cuda"), torch.empty(B, K, device="cuda")
+        n_params = [sum(t.numel() for t in ts) for ts in (W + b, WK + bK)]
+        u = torch.ops.umnn
+        for mask in range(16):
+            need = [bool(mask >> i & 1) for i in range(4)]
+            single = u.cc_backward(x0, x, h, g, g, W, b, 0, 0, 10, need, False)
+            multi = u.cc_backward_multi(x0, x, h, gK, WK, bK, 0, 0, 10, need, False)
+            multi_fx = u.cc_backward_multi_fx(x0, x, h, gK, gK, WK, bK, 0, 0, 10, need, False)
+            want = [(B, 1) if need[0] and with_x0 else (0,), (B, 1) if need[1] else (0,), (B, E) if need[2] else (0,)]
+            for outs, n in ((single, n_params[0]), (multi, n_params[1]), (multi_fx, n_params[1])):
+                assert [tuple(t.shape) for t in outs] == want + [(n,) if need[3] else (0,)], (need, outs)
+                assert [t.dtype for t in outs] == [torch.float32, torch.float32, torch.bfloat16, torch.float32]
+                assert all(t.device.type == "cuda" for t in outs)
+
+
+@pytest.mark.parametrize("n_out,d,E", [(3, 1, 3), (1, 3, 2)], ids=["K=3", "d=3"])
+def test_pure_mlp_is_the_module_for_every_n_out(n_out, d, E):
+    """The one ``ops.pure_mlp`` at B = 5, hidden 7-6: for K = 3 outputs over x [B,1] it is ``IntegrandNN(4, [7, 6], n_out=3)`` on the same
+    weights -> [B, 3]; for one output at d = 3, E = 2 it is ``IntegrandNetwork.forward`` -> [B, d].  The same ATen ops in the same
+    order (at d = 1 the row gather is the identity), so values are equal bit for bit, and ``torch.func.vjp`` gives the gradients of
+    the module's autograd."""
+    torch.manual_seed(0)
+    B = 5
+    net = IntegrandNN(1 + E, [7, 6], n_out=n_out) if n_out > 1 else IntegrandNetwork(d, 1 + E, [7, 6], 1)
+    hidden_act = _lib.ACT_RELU if n_out > 1 else _lib.ACT_LEAKY_RELU
+    lins = [m for m in net.net if isinstance(m, torch.nn.Linear)]
+    f, params = ops.pure_mlp([l.weight for l in lins], [l.bias for l in lins], hidden_act, _lib.OUT_ELU_PLUS_ONE)
+    x, h = torch.randn(B, d), torch.randn(B, E * d)
+    want = net(x, h)
+    assert want.shape == (B, n_out * d)
+    got, vjp = torch.func.vjp(f, params, x, h)
+    assert torch.equal(got, want) and torch.equal(f(params, x, h), want)
+    cot = torch.randn_like(want)
+    xr, hr = x.clone().requires_grad_(), h.clone().requires_grad_()
+    grads = torch.autograd.grad(net(xr, hr), [xr, hr] + list(net.parameters()), cot)
+    g_params, g_x, g_h = vjp(cot)
+    for name, a, w in zip(["x", "h"] + [f"parameter {i}" for i in range(len(params))], [g_x, g_h] + list(g_params), grads):
+        assert a.shape == w.shape and torch.equal(a, w), name
 
 
 def test_import_loads_no_library():

@@ -156,6 +156,19 @@ def _check_multi_x(n_out, x):
                            f"{tuple(x.shape)}.  Integrate the dimensions one by one, or use n_out = 1.")
 
 
+def _kernel_probe(cache, key, spec, ask, warn_key, message):
+    """Does the library have a kernel for this net: ``ask(desc)`` once per ``key`` (the widths, and whatever else decides) into
+    ``cache``; a negative answer is announced once (``message(widths)``), and the caller runs on ATen.  -> the cached answer."""
+    answer = cache.get(key)
+    if answer is None:
+        desc, keep = _desc(spec)
+        answer = cache[key] = ask(ctypes.byref(desc))
+    if answer < 0:
+        widths = [m.out_features for m in spec.linears]
+        _warn_once((warn_key, tuple((m.in_features, m.out_features) for m in spec.linears)), message(widths))
+    return answer
+
+
 _multi_ok = {}
 
 
@@ -163,16 +176,10 @@ def _multi_kernels_ok(spec):
     """False (after a one-time notice) for multi-output nets whose weight images, output image and scratch exceed the LDS: the
     library answers UMNN_EUNSUPPORTED and the quadrature runs on ATen, like the deep wide single-output nets' backward."""
     key = tuple((m.in_features, m.out_features) for m in spec.linears)
-    ok = _multi_ok.get(key)
-    if ok is None:
-        desc, keep = _desc(spec)
-        nbytes = _lib.lib().umnn_cc_backward_multi_workspace_bytes(ctypes.byref(desc), 1, 1, spec.linears[0].in_features - 1)
-        ok = _multi_ok[key] = nbytes >= 0
-    if not ok:
-        _warn_once(("multi-aten", key),
-                   f"umnn_amd: no multi-output HIP kernel for integrand widths {[w for _, w in key]} "
-                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): integrating with the generic ATen quadrature on the GPU.")
-    return ok
+    return _kernel_probe(
+        _multi_ok, key, spec, lambda desc: min(int(_lib.lib().umnn_cc_backward_multi_workspace_bytes(desc, 1, 1, key[0][0] - 1)), 0),
+        "multi-aten", lambda widths: f"umnn_amd: no multi-output HIP kernel for integrand widths {widths} "
+        f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): integrating with the generic ATen quadrature on the GPU.") >= 0
 
 
 _bwd_kind = {}
@@ -195,19 +202,18 @@ def _hip_backward_ok(spec, x, h):
         return True
     E = h.shape[1] // x.shape[1]
     key = (tuple((m.in_features, m.out_features) for m in spec.linears), E, _lib.get_option("bwd_precision"))
-    kind = _bwd_kind.get(key)
-    if kind is None:
-        desc, keep = _desc(spec)
-        kind = _lib.lib().umnn_cc_backward_kind(ctypes.byref(desc), E)
+
+    def ask(desc):
+        kind = _lib.lib().umnn_cc_backward_kind(desc, E)
         if kind < -1:       # an error code (invalid descriptor, umnn_prepare_mlp failure): surfaced, never rerouted as "a wide net"
             _lib.check(kind, "umnn_cc_backward_kind")
-        _bwd_kind[key] = kind
-    if kind < 0:
-        _warn_once(("bwd-aten", key[0]),
-                   f"umnn_amd: the HIP backward has no shape-exact kernel for integrand widths {[w for _, w in key[0]]} "
-                   "(deep net of unequal wide hidden layers: its zero-padded weight images exceed the LDS): differentiating with the materialised ATen chain on the "
-                   "GPU instead (forward stays on the HIP kernel; umnn_amd.set_backward_wide(True) forces the HIP kernels).")
-    return kind >= 0
+        return kind
+
+    return _kernel_probe(
+        _bwd_kind, key, spec, ask, "bwd-aten",
+        lambda widths: f"umnn_amd: the HIP backward has no shape-exact kernel for integrand widths {widths} "
+        "(deep net of unequal wide hidden layers: its zero-padded weight images exceed the LDS): differentiating with the materialised ATen chain on the "
+        "GPU instead (forward stays on the HIP kernel; umnn_amd.set_backward_wide(True) forces the HIP kernels).") >= 0
 
 
 def _shape(spec, x, h):
@@ -243,64 +249,73 @@ def _as(t, dtype):
     return None if t is None else t.detach().to(dtype).contiguous()
 
 
-def hip_forward(spec, x0, x, h, nb_steps, inv_f=False):
-    """-> (F, f_x, f_x0), each [B,d] in x's dtype.  x0 may be None (zeros)."""
+def _quad_plan(spec, x, h, multi):
+    """Shape check and storage plan of the four quadrature wrappers -> (B, d, E, x storage dtype, h storage dtype, umnn_io pointer).
+    ``multi``: the multi-output entries are exact fp32 whatever ``set_precision`` says and take no descriptor: bf16 / fp16 callers
+    are converted at the boundary."""
+    if multi:
+        _check_multi_x(n_out_of(spec), x)
+    return _shape(spec, x, h) + ((torch.float32, torch.float32, None) if multi else _io_prep(x, h))
+
+
+def _quad_done(rc, fn_name, x_outs, stored, x_dtype, backward=False):
+    """What the four end with: ``check``, the path bookkeeping, and the x-shaped outputs from their ``stored`` dtype back to the
+    caller's (fp16 callers, bf16 ones of the multi-output entries: fp32 inside, theirs outside)."""
+    _lib.check(rc, fn_name)
+    _state.path = "hip"
+    if backward:
+        _last_backward["path"] = "hip"
+    if x_dtype == stored:
+        return x_outs
+    return tuple(None if t is None else t.to(x_dtype) for t in x_outs)
+
+
+def hip_forward(spec, x0, x, h, nb_steps, inv_f=False, multi=False):
+    """-> (F, f_x, f_x0), each [B,d] in x's dtype.  x0 may be None (zeros).  ``multi``: the body of ``hip_forward_multi``."""
     lib = _lib.lib()
-    B, d, E = _shape(spec, x, h)
+    B, d, E, xd, hd, io = _quad_plan(spec, x, h, multi)
     out_dtype = x.dtype
-    xd, hd, io = _io_prep(x, h)
     x, h, x0 = _as(x, xd), _as(h, hd), _as(x0, xd)
     w, s = device_tables(nb_steps, x.device)
-    F, fx, fx0 = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    shape = (B, n_out_of(spec) if multi else d)
+    F, fx, fx0 = x.new_empty(shape), x.new_empty(shape), x.new_empty(shape)
     desc, keep = _desc(spec)
     with torch.cuda.device(x.device):
-        rc = lib.umnn_cc_forward_io(ctypes.byref(desc), io, _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps), B, d, E,
-                                    int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0), _stream(x.device))
-    _lib.check(rc, "umnn_cc_forward")
-    _state.path = "hip"
-    if out_dtype != xd:                   # fp16 callers: fp32 inside, their dtype outside
-        F, fx, fx0 = F.to(out_dtype), fx.to(out_dtype), fx0.to(out_dtype)
-    return F, fx, fx0
+        tail = (_ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps), B, d, E, int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0),
+                _stream(x.device))
+        rc = lib.umnn_cc_forward_multi(ctypes.byref(desc), *tail) if multi else lib.umnn_cc_forward_io(ctypes.byref(desc), io, *tail)
+    return _quad_done(rc, "umnn_cc_forward_multi" if multi else "umnn_cc_forward", (F, fx, fx0), xd, out_dtype)
 
 
 def hip_forward_multi(spec, x0, x, h, nb_steps, inv_f=False):
     """Multi-output forward (umnn_cc_forward_multi): x [B,1], h [B,E] -> (F, f_x, f_x0), each [B, n_out] in x's dtype.  Exact fp32
     kernels and fp32 storage whatever ``set_precision`` says; bf16 / fp16 callers are converted at the boundary."""
-    lib = _lib.lib()
-    K = n_out_of(spec)
-    _check_multi_x(K, x)
-    B, d, E = _shape(spec, x, h)
-    out_dtype = x.dtype
-    x, h, x0 = _f32c(x), _f32c(h), (None if x0 is None else _f32c(x0))
-    w, s = device_tables(nb_steps, x.device)
-    F, fx, fx0 = (torch.empty(B, K, device=x.device, dtype=torch.float32) for _ in range(3))
-    desc, keep = _desc(spec)
-    with torch.cuda.device(x.device):
-        rc = lib.umnn_cc_forward_multi(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps), B, d, E,
-                                       int(bool(inv_f)), _ptr(F), _ptr(fx), _ptr(fx0), _stream(x.device))
-    _lib.check(rc, "umnn_cc_forward_multi")
-    _state.path = "hip"
-    if out_dtype != torch.float32:
-        F, fx, fx0 = F.to(out_dtype), fx.to(out_dtype), fx0.to(out_dtype)
-    return F, fx, fx0
+    return hip_forward(spec, x0, x, h, nb_steps, inv_f, multi=True)
 
 
-def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True), inv_f=False, g_fx=None):
-    """Multi-output backward (umnn_cc_backward_multi_fx) for the cotangent g [B, n_out] -> (dx0, dx, dh, dtheta_flat), None where
-    ``need`` is False: dx = sum_k g_k f_k(x) and dx0 = -sum_k g_k f_k(x0) are [B,1]; dtheta is flat in parameters() order with
-    the last layer as [n_out, H_L] / [n_out].  ``g_fx`` [B, n_out] (optional): the cotangent of the f_x output, f_k(x; h) -- it
-    reaches dh and dtheta through the same launches and adds sum_k g_fx,k df_k/dx (x) to dx."""
+def _add_h0(dh, h0_cot, d):
+    """d_h + the h_0 term in embedding row 0 (z carries h_0 = embedding row 0, UMNNMAF.py:80), in fp32, in dh's dtype"""
+    out = dh.float() if dh.dtype != torch.float32 else dh
+    out.view(dh.shape[0], -1, d)[:, 0, :].add_(h0_cot)
+    return out.to(dh.dtype)
+
+
+def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None, h0_cot=None, multi=False):
+    """-> (dx0, dx, dh, dtheta_flat); entries are None where need[...] is False.  dx0/dx come back in x's dtype, dh in
+    h's, dtheta in fp32 (the weights' dtype).  inv_f: the operator integrated 1/f (ParallelNeuralIntegral.py:58-59,70-72).
+    h0_cot [B,d] (a flow block's backward: lower limit 0): added to embedding row 0 of dh by the kernel that stores dh
+    (umnn_cc_backward_block_io, the entry of every call without x0, inv_f and d_x0; ``z2_saved`` is that entry's too), so that a
+    bf16 dh is rounded once.  ``multi``: the body of ``hip_backward_multi``."""
     lib = _lib.lib()
-    K = n_out_of(spec)
-    _check_multi_x(K, x)
-    B, d, E = _shape(spec, x, h)
-    if g.shape != (B, K):
-        raise RuntimeError(f"umnn_amd: the cotangent of a multi-output integral has shape {tuple(g.shape)}; expected {(B, K)}")
-    if g_fx is not None and g_fx.shape != (B, K):
-        raise RuntimeError(f"umnn_amd: the cotangent of the f_x output of a multi-output integral has shape {tuple(g_fx.shape)}; expected {(B, K)}")
+    B, d, E, xd, hd, io = _quad_plan(spec, x, h, multi)
+    if multi:
+        K = n_out_of(spec)
+        if g.shape != (B, K):
+            raise RuntimeError(f"umnn_amd: the cotangent of a multi-output integral has shape {tuple(g.shape)}; expected {(B, K)}")
+        if g_fx is not None and g_fx.shape != (B, K):
+            raise RuntimeError(f"umnn_amd: the cotangent of the f_x output of a multi-output integral has shape {tuple(g_fx.shape)}; expected {(B, K)}")
     x_dtype, h_dtype = x.dtype, h.dtype
-    x, h, g, x0 = _f32c(x), _f32c(h), _f32c(g), (None if x0 is None else _f32c(x0))
-    g_fx = None if g_fx is None else _f32c(g_fx)
+    x, h, g, x0, g_fx = _as(x, xd), _as(h, hd), _as(g, xd), _as(x0, xd), _as(g_fx, xd)
     w, s = device_tables(nb_steps, x.device)
     dx0 = torch.empty_like(x) if need[0] else None
     dx = torch.empty_like(x) if need[1] else None
@@ -308,22 +323,38 @@ def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True
     n_params = sum(l.weight.numel() + l.bias.numel() for l in spec.linears)
     dtheta = torch.empty(n_params, device=x.device, dtype=torch.float32) if need[3] else None
     desc, keep = _desc(spec)
+    net = ctypes.byref(desc)
     with torch.cuda.device(x.device):
-        nbytes = lib.umnn_cc_backward_multi_workspace_bytes(ctypes.byref(desc), B, d, E)
-        if nbytes < 0:
+        nbytes = (lib.umnn_cc_backward_multi_workspace_bytes if multi else lib.umnn_cc_backward_workspace_bytes)(net, B, d, E)
+        if multi and nbytes < 0:
             _lib.check(_lib.EUNSUPPORTED, "umnn_cc_backward_multi_workspace_bytes")
         ws = torch.empty(max(int(nbytes), 4), device=x.device, dtype=torch.uint8)
-        rc = lib.umnn_cc_backward_multi_fx(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s),
-                                           int(nb_steps), B, d, E, int(bool(inv_f)), _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta),
-                                           _ptr(ws), int(nbytes), _stream(x.device))
-    _lib.check(rc, "umnn_cc_backward_multi_fx")
-    _state.path = _last_backward["path"] = "hip"
-    if x_dtype != torch.float32:
-        dx0 = dx0.to(x_dtype) if dx0 is not None else None
-        dx = dx.to(x_dtype) if dx is not None else None
-    if h_dtype != torch.float32 and dh is not None:
+        mid = (_ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s), int(nb_steps), B, d, E)
+        outs = (_ptr(dx), _ptr(dh), _ptr(dtheta))
+        end = (_ptr(ws), int(nbytes), _stream(x.device))
+        h0 = _as(h0_cot, torch.float32) if dh is not None else None
+        if multi:
+            rc = lib.umnn_cc_backward_multi_fx(net, _ptr(x0), *mid, int(bool(inv_f)), _ptr(dx0), *outs, *end)
+        elif x0 is None and not inv_f and not need[0]:      # (the flow block's entry has no x0 and no d_x0 output; h0 and z_2 nullable)
+            rc = lib.umnn_cc_backward_block_io(net, io, *mid, _ptr(h0), *outs, _ptr(z2_saved),
+                                               0 if z2_saved is None else int(z2_saved.numel()), *end)
+            h0 = None
+        else:
+            rc = lib.umnn_cc_backward_io(net, io, _ptr(x0), *mid, int(bool(inv_f)), _ptr(dx0), *outs, *end)
+    dx0, dx = _quad_done(rc, "umnn_cc_backward_multi_fx" if multi else "umnn_cc_backward", (dx0, dx), xd, x_dtype, backward=True)
+    if h0 is not None:
+        dh = _add_h0(dh, h0, d)
+    if h_dtype != hd and dh is not None:
         dh = dh.to(h_dtype)
     return dx0, dx, dh, dtheta
+
+
+def hip_backward_multi(spec, x0, x, h, g, nb_steps, need=(True, True, True, True), inv_f=False, g_fx=None):
+    """Multi-output backward (umnn_cc_backward_multi_fx) for the cotangent g [B, n_out] -> (dx0, dx, dh, dtheta_flat), None where
+    ``need`` is False: dx = sum_k g_k f_k(x) and dx0 = -sum_k g_k f_k(x0) are [B,1]; dtheta is flat in parameters() order with
+    the last layer as [n_out, H_L] / [n_out].  ``g_fx`` [B, n_out] (optional): the cotangent of the f_x output, f_k(x; h) -- it
+    reaches dh and dtheta through the same launches and adds sum_k g_fx,k df_k/dx (x) to dx."""
+    return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f, multi=True)
 
 
 # z_2 handed from the training forward to the backward (three-stage family): memory held from forward to backward.  Two caps: per
@@ -618,58 +649,6 @@ def hip_flow_ll_block(spec, x, h, scaling, nb_steps, reverse_z, first, last, ll,
     return z
 
 
-def _add_h0(dh, h0_cot, d):
-    """d_h + the h_0 term in embedding row 0 (z carries h_0 = embedding row 0, UMNNMAF.py:80), in fp32, in dh's dtype"""
-    out = dh.float() if dh.dtype != torch.float32 else dh
-    out.view(dh.shape[0], -1, d)[:, 0, :].add_(h0_cot)
-    return out.to(dh.dtype)
-
-
-def hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need=(True, True, True, True), inv_f=False, z2_saved=None, h0_cot=None):
-    """-> (dx0, dx, dh, dtheta_flat); entries are None where need[...] is False.  dx0/dx come back in x's dtype, dh in
-    h's, dtheta in fp32 (the weights' dtype).  inv_f: the operator integrated 1/f (ParallelNeuralIntegral.py:58-59,70-72).
-    h0_cot [B,d] (a flow block's backward: lower limit 0): added to embedding row 0 of dh by the kernel that stores dh
-    (umnn_cc_backward_block_io), so that a bf16 dh is rounded once."""
-    lib = _lib.lib()
-    B, d, E = _shape(spec, x, h)
-    x_dtype, h_dtype = x.dtype, h.dtype
-    xd, hd, io = _io_prep(x, h)
-    x, h, g, x0, g_fx = _as(x, xd), _as(h, hd), _as(g, xd), _as(x0, xd), _as(g_fx, xd)
-    w, s = device_tables(nb_steps, x.device)
-    dx0 = torch.empty_like(x) if need[0] else None
-    dx = torch.empty_like(x) if need[1] else None
-    dh = torch.empty_like(h) if need[2] else None
-    n_params = sum(l.weight.numel() + l.bias.numel() for l in spec.linears)
-    dtheta = torch.empty(n_params, device=x.device, dtype=torch.float32) if need[3] else None
-    desc, keep = _desc(spec)
-    with torch.cuda.device(x.device):
-        nbytes = lib.umnn_cc_backward_workspace_bytes(ctypes.byref(desc), B, d, E)
-        ws = torch.empty(max(int(nbytes), 4), device=x.device, dtype=torch.uint8)
-        head = (ctypes.byref(desc), io)
-        mid = (_ptr(x), _ptr(h), _ptr(g), _ptr(g_fx), _ptr(w), _ptr(s), int(nb_steps), B, d, E)
-        h0 = _as(h0_cot, torch.float32) if dh is not None else None
-        if h0 is not None and not inv_f and x0 is None and not need[0]:
-            rc = lib.umnn_cc_backward_block_io(*head, *mid, _ptr(h0), _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved),
-                                               0 if z2_saved is None else int(z2_saved.numel()), _ptr(ws), int(nbytes), _stream(x.device))
-            h0 = None
-        elif z2_saved is not None and not inv_f and x0 is None and not need[0]:    # (that entry point has no x0 and no d_x0 output)
-            rc = lib.umnn_cc_backward_saved_io(*head, *mid, _ptr(dx), _ptr(dh), _ptr(dtheta), _ptr(z2_saved), int(z2_saved.numel()),
-                                               _ptr(ws), int(nbytes), _stream(x.device))
-        else:
-            rc = lib.umnn_cc_backward_io(*head, _ptr(x0), *mid, int(bool(inv_f)), _ptr(dx0), _ptr(dx), _ptr(dh), _ptr(dtheta),
-                                         _ptr(ws), int(nbytes), _stream(x.device))
-    _lib.check(rc, "umnn_cc_backward")
-    _state.path = _last_backward["path"] = "hip"
-    if x_dtype != xd:
-        dx0 = dx0.to(x_dtype) if dx0 is not None else None
-        dx = dx.to(x_dtype) if dx is not None else None
-    if h0 is not None:
-        dh = _add_h0(dh, h0, d)
-    if h_dtype != hd and dh is not None:
-        dh = dh.to(h_dtype)
-    return dx0, dx, dh, dtheta
-
-
 # ----------------------------------------------------------------------------------------------
 # generic ATen path (arbitrary callables; any device)
 # ----------------------------------------------------------------------------------------------
@@ -785,13 +764,11 @@ def quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need=(True
     ``h0_cot`` [B,d] (single-output operators): a flow block's h_0 term, added to embedding row 0 of dh -- inside the HIP launch that
     stores dh, in fp32 torch ops on the ATen path."""
     need = (bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3]))
-    if spec is not None and n_out_of(spec) == 1 and _hip_backward_ok(spec, x, h):
-        return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f=inv_f, z2_saved=z2_saved, h0_cot=h0_cot)
-    if spec is not None and n_out_of(spec) > 1 and _multi_kernels_ok(spec):
-        out = hip_backward_multi(spec, x0, x, h, g, nb_steps, need, inv_f=inv_f, g_fx=g_fx)
-    else:
-        out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
-        out = tuple(t if n else None for t, n in zip(out, need))
+    multi = spec is not None and n_out_of(spec) > 1
+    if spec is not None and (_multi_kernels_ok(spec) if multi else _hip_backward_ok(spec, x, h)):
+        return hip_backward(spec, x0, x, h, g, g_fx, nb_steps, need, inv_f, z2_saved, h0_cot, multi)
+    out = aten_vjp(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, g, g_fx, nb_steps, inv_f, limits=need[0] or need[1])
+    out = tuple(t if n else None for t, n in zip(out, need))
     if h0_cot is not None and out[2] is not None:
         out = (out[0], out[1], _add_h0(out[2], h0_cot, x.shape[1]), out[3])
     return out
@@ -823,7 +800,7 @@ def cc_forward(spec, x0, x, h, nb_steps, inv_f=False):
     if _graph_mode():
         op = torch.ops.umnn.cc_forward_multi if multi else torch.ops.umnn.cc_forward
         return op(x0, x, h, *spec_args(spec), int(nb_steps), bool(inv_f))
-    return (hip_forward_multi if multi else hip_forward)(spec, x0, x, h, nb_steps, inv_f)[:2]
+    return hip_forward(spec, x0, x, h, nb_steps, inv_f, multi)[:2]
 
 
 def cc_forward_jac(spec, integrand, x0, x, h, nb_steps, no_graph):
@@ -1075,12 +1052,13 @@ def _launch_backward(net, spec, integrand, x0, x, h, g, g_fx, nb_steps, need, in
     if not net:
         return quadrature_backward(spec, integrand, x0, x, h, g, g_fx, nb_steps, need, inv_f)
     need = [bool(need[0]) and x0 is not None, bool(need[1]), bool(need[2]), bool(need[3])]
-    if net[0][-1].shape[0] > 1 and g_fx is not None:
-        out = torch.ops.umnn.cc_backward_multi_fx(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
-    elif net[0][-1].shape[0] > 1:
-        out = torch.ops.umnn.cc_backward_multi(x0, x, h, g, *net, int(nb_steps), need, bool(inv_f))
+    if net[0][-1].shape[0] == 1:
+        op, cotangents = torch.ops.umnn.cc_backward, (g, g_fx)
+    elif g_fx is None:
+        op, cotangents = torch.ops.umnn.cc_backward_multi, (g,)
     else:
-        out = torch.ops.umnn.cc_backward(x0, x, h, g, g_fx, *net, int(nb_steps), need, bool(inv_f))
+        op, cotangents = torch.ops.umnn.cc_backward_multi_fx, (g, g_fx)
+    out = op(x0, x, h, *cotangents, *net, int(nb_steps), need, bool(inv_f))
     return tuple(t if n else None for t, n in zip(out, need))
 
 

@@ -80,13 +80,20 @@ class MonotonicNN(nn.Module):
         self.device = dev
         self.nb_steps = nb_steps
 
+    def _offset_log_scaling(self, h, k=None):
+        """The conditioner's output, split -> (o(h), s(h)): every output ([B, n_out] each), or output ``k`` alone ([B, 1] each).
+        ``n_out == 1`` is its output 0 in the indexing form of the reference (MonotonicNN.py:47-48), which decides the autograd nodes."""
+        out = self.net(h)
+        if k is None and self.n_out == 1:
+            k = 0
+        if k is not None:
+            return out[:, [k]], out[:, [self.n_out + k]]
+        return out[:, :self.n_out], out[:, self.n_out:]
+
     def forward(self, x, h):
         x0 = torch.zeros_like(x)
-        out = self.net(h)
-        if self.n_out == 1:
-            offset, scaling = out[:, [0]], torch.exp(out[:, [1]])
-        else:
-            offset, scaling = out[:, :self.n_out], torch.exp(out[:, self.n_out:])
+        offset, log_scaling = self._offset_log_scaling(h)
+        scaling = torch.exp(log_scaling)
         integral = ParallelNeuralIntegral.apply(x0, x, self.integrand, _flatten(self.integrand.parameters()), h,
                                                 self.nb_steps)
         return scaling * integral + offset
@@ -101,11 +108,7 @@ class MonotonicNN(nn.Module):
         This is the package's replacement for ``torch.autograd.grad(y, x, create_graph=True)``: the quadrature operators are
         once-differentiable by design, so that call keeps raising; a double backward through this pair is out of scope too."""
         x0 = torch.zeros_like(x)
-        out = self.net(h)
-        if self.n_out == 1:
-            offset, log_scaling = out[:, [0]], out[:, [1]]
-        else:
-            offset, log_scaling = out[:, :self.n_out], out[:, self.n_out:]
+        offset, log_scaling = self._offset_log_scaling(h)
         scaling = torch.exp(log_scaling)
         integral, f_x = IntegralWithDerivative.apply(x0, x, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps)
         return scaling * integral + offset, (log_scaling + torch.log(f_x) if log else scaling * f_x)
@@ -119,16 +122,13 @@ class MonotonicNN(nn.Module):
         the integrand's last layer, whose other rows get zero gradient).  ``return_info=True`` -> (x, f(x; h), status): the integrand at the solution
         (dy/dx = exp(s(h)) f) and an int32 word per row, evaluations used in the low 16 bits, above them
         ``umnn_amd.SOLVE_CLAMPED`` (ended on an endpoint), ``SOLVE_CAPPED`` (still running after ``max_iter``) and ``SOLVE_NONFINITE``."""
-        out = self.net(h)
-        if self.n_out == 1:
-            if output != 0:
-                raise IndexError(f"MonotonicNN.inverse: output {output} of a model with n_out = 1")
-            t = (y - out[:, [0]]) * torch.exp(-out[:, [1]])
-            return InverseNeuralIntegral.apply(t, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
-                                               x_range, tol, max_iter, return_info)
         k = int(output)
         if not 0 <= k < self.n_out:
             raise IndexError(f"MonotonicNN.inverse: output {output} of a model with n_out = {self.n_out}")
-        t = (y - out[:, [k]]) * torch.exp(-out[:, [self.n_out + k]])
+        offset, log_scaling = self._offset_log_scaling(h, k)
+        t = (y - offset) * torch.exp(-log_scaling)
+        if self.n_out == 1:
+            return InverseNeuralIntegral.apply(t, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
+                                               x_range, tol, max_iter, return_info)
         row = OutputRow(self.integrand, k)
         return InverseNeuralIntegral.apply(t, row, _flatten(row.row_params()), h, self.nb_steps, x_range, tol, max_iter, return_info)

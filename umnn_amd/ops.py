@@ -97,11 +97,16 @@ def _check_need(op, need, n):
     _req(op, len(need) == n, f"need has {len(need)} entries; expected {n}")
 
 
-def _check_cc(op, x0, x, h, W, b, hidden_act, out_act, g=None, g_fx=None):
-    B, d = _check_net(op, x, h, W, b, hidden_act, out_act)
-    for name, t in (("x0", x0), ("g", g), ("g_fx", g_fx)):
+def _check_cc(op, x0, x, h, W, b, hidden_act, out_act, g=None, g_fx=None, need=None, multi=False):
+    """The quadrature ops: x0 shaped like x; the cotangents [B, d], or [B, n_out] over x [B, 1] (``multi``); ``need`` of four."""
+    B, d = _check_net(op, x, h, W, b, hidden_act, out_act, multi=multi)
+    if x0 is not None:
+        _check_tensor(op, "x0", x0, x, (B, 1) if multi else (B, d), _FLOATS)
+    for name, t in (("g", g), ("g_fx", g_fx)):
         if t is not None:
-            _check_tensor(op, name, t, x, (B, d), _FLOATS)
+            _check_tensor(op, name, t, x, (B, W[-1].shape[0]) if multi else (B, d), _FLOATS)
+    if need is not None:
+        _check_need(op, need, 4)
 
 
 def _check_block(op, x, h, scaling, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS, s_dtypes=_FLOATS):
@@ -110,13 +115,11 @@ def _check_block(op, x, h, scaling, W, b, hidden_act, out_act, x_dtypes=_FLOATS,
     return B, d
 
 
-def _check_cc_forward(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
-    _check_cc("cc_forward", x0, x, h, W, b, hidden_act, out_act)
-
-
-def _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
-    _check_cc("cc_backward", x0, x, h, W, b, hidden_act, out_act, g, g_fx)
-    _check_need("cc_backward", need, 4)
+def _check_solve(op, nb_steps, lo, hi, tol, max_iter):
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+    _req(op, lo < hi, f"empty bracket [{lo}, {hi}]")
+    _req(op, tol >= 0, f"tol is {tol}; expected >= 0")
+    _req(op, 1 <= max_iter <= _lib.SOLVE_EVALS_MASK, f"max_iter is {max_iter}; expected 1..{_lib.SOLVE_EVALS_MASK}")
 
 
 def _check_flow_block(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, log_jac_in):
@@ -178,116 +181,28 @@ def _param_grads(dtheta, W, b, need_W, need_b):
 @torch.library.custom_op("umnn::cc_forward", mutates_args=(), device_types="cuda")
 def cc_forward(x0: Optional[Tensor], x: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
                nb_steps: int, inv_f: bool) -> tuple[Tensor, Tensor]:
-    _check_cc_forward(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f)
+    _check_cc("cc_forward", x0, x, h, W, b, hidden_act, out_act)
     F_, fx, _ = _I.hip_forward(spec_from_tensors(W, b, hidden_act, out_act), x0, x, h, nb_steps, inv_f)
     return F_, fx
 
 
 @cc_forward.register_fake
 def _(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
-    _check_cc_forward(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f)
+    _check_cc("cc_forward", x0, x, h, W, b, hidden_act, out_act)
     return x.new_empty(x.shape), x.new_empty(x.shape)
-
-
-def _cc_forward_setup(ctx, inputs, output):
-    x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f = inputs
-    ctx.meta = (hidden_act, out_act, nb_steps, inv_f, len(W), x0 is None)
-    ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
-
-
-def _cc_forward_backward(ctx, gF, gfx):
-    hidden_act, out_act, nb_steps, inv_f, L, x0_none = ctx.meta
-    saved = ctx.saved_tensors
-    x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
-    x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
-    nig = ctx.needs_input_grad
-    need = [bool(nig[0]) and not x0_none, bool(nig[1]), bool(nig[2]), any(nig[3]) or any(nig[4])]
-    dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward(x0, x, h, gF, gfx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[3], nig[4])
-    return (dx0 if need[0] else None, dx if need[1] else None, dh if need[2] else None, gW, gb,
-            None, None, None, None)
-
-
-cc_forward.register_autograd(_cc_forward_backward, setup_context=_cc_forward_setup)
-
-
-def pure_mlp(W, b, hidden_act, out_act):
-    """The integrand the ops get -- W[], b[] and the activation codes, never a module -- as ``integral.aten_vjp`` takes it:
-    (f(params, x, h) -> [B,d], params in parameters() order), f the MLP on the rows [x_i, h_{0,i}, ..., h_{E-1,i}]
-    (nets.IntegrandNetwork.rows)."""
-    L = len(W)
-
-    def f(params, x, h):
-        B, d = x.shape
-        a = torch.cat((x, h), 1).view(B, -1, d).transpose(1, 2).reshape(B * d, -1)
-        for l in range(L):
-            a = F.linear(a, params[2 * l], params[2 * l + 1])
-            if l + 1 < L:
-                a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
-        return (F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)).view(B, d)
-
-    return f, [p.detach() for pair in zip(W, b) for p in pair]
-
-
-@torch.library.custom_op("umnn::cc_backward", mutates_args=(), device_types="cuda")
-def cc_backward(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, g_fx: Optional[Tensor], W: List[Tensor], b: List[Tensor],
-                hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """``integral.quadrature_backward`` for an integrand given as tensors: the HIP kernels, or -- for the nets
-    ``integral._hip_backward_ok`` turns away, decided here at run time -- the one ATen backward, on ``pure_mlp``."""
-    _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
-    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp(W, b, hidden_act, out_act), x0, x, h, g, g_fx,
-                                 nb_steps, need, inv_f)
-    like = (x, x, h, W[0])
-    return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
-                 for i, (t, n, l) in enumerate(zip(out, need, like)))
-
-
-@cc_backward.register_fake
-def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
-    _check_cc_backward(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    return (x.new_empty(x.shape) if (need[0] and x0 is not None) else _empty(x),
-            x.new_empty(x.shape) if need[1] else _empty(x),
-            h.new_empty(h.shape) if need[2] else _empty(h),
-            W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
-
-
-# ---------------------------------------------------------------------------------------------------------- multi-output quadrature
-def _check_cc_multi(op, x0, x, h, W, b, hidden_act, out_act, g=None, g_fx=None):
-    B, d = _check_net(op, x, h, W, b, hidden_act, out_act, multi=True)
-    if x0 is not None:
-        _check_tensor(op, "x0", x0, x, (B, 1), _FLOATS)
-    for name, t in (("g", g), ("g_fx", g_fx)):
-        if t is not None:
-            _check_tensor(op, name, t, x, (B, W[-1].shape[0]), _FLOATS)
-
-
-def pure_mlp_multi(W, b, hidden_act, out_act):
-    """``pure_mlp`` for a multi-output integrand over x [B,1]: f(params, x, h) -> [B, n_out]."""
-    L = len(W)
-
-    def f(params, x, h):
-        a = torch.cat((x, h), 1)
-        for l in range(L):
-            a = F.linear(a, params[2 * l], params[2 * l + 1])
-            if l + 1 < L:
-                a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
-        return F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)
-
-    return f, [p.detach() for pair in zip(W, b) for p in pair]
 
 
 @torch.library.custom_op("umnn::cc_forward_multi", mutates_args=(), device_types="cuda")
 def cc_forward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
                      nb_steps: int, inv_f: bool) -> tuple[Tensor, Tensor]:
     """``integral.hip_forward_multi`` for an integrand given as tensors -> (F, f_x), each [B, n_out]; for the nets whose images
-    exceed the LDS (``integral._multi_kernels_ok``, decided here at run time) the ATen quadrature on ``pure_mlp_multi``."""
-    _check_cc_multi("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act)
+    exceed the LDS (``integral._multi_kernels_ok``, decided here at run time) the ATen quadrature on ``pure_mlp``."""
+    _check_cc("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act, multi=True)
     spec = spec_from_tensors(W, b, hidden_act, out_act)
     if _I._multi_kernels_ok(spec):
         F_, fx, _ = _I.hip_forward_multi(spec, x0, x, h, nb_steps, inv_f)
         return F_, fx
-    f, params = pure_mlp_multi(W, b, hidden_act, out_act)
+    f, params = pure_mlp(W, b, hidden_act, out_act)
     with torch.no_grad():
         xd, hd = x.detach(), h.detach()
         x0d = torch.zeros_like(xd) if x0 is None else x0.detach()
@@ -296,104 +211,140 @@ def cc_forward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, W: List[Tensor]
 
 @cc_forward_multi.register_fake
 def _(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
-    _check_cc_multi("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act)
+    _check_cc("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act, multi=True)
     shape = (x.shape[0], W[-1].shape[0])
     return x.new_empty(shape), x.new_empty(shape)
 
 
-def _cc_forward_multi_setup(ctx, inputs, output):
+# The autograd glue of the two forward ops: one ctx layout, one ``need`` rule, one packer of the nine input gradients.
+def _cc_setup(ctx, inputs, output):
     x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f = inputs
-    ctx.set_materialize_grads(False)               # (an f_x nobody differentiates: no zero cotangent, the backward of before)
     ctx.meta = (hidden_act, out_act, nb_steps, inv_f, len(W), x0 is None)
     ctx.save_for_backward(*(() if x0 is None else (x0,)), x, h, *W, *b)
 
 
-def _cc_forward_multi_backward(ctx, gF, gfx):
+def _cc_saved(ctx):
+    """-> ((x0, x, h), the integrand and step arguments every backward op ends in before ``need``, need[4])."""
     hidden_act, out_act, nb_steps, inv_f, L, x0_none = ctx.meta
     saved = ctx.saved_tensors
     x0, rest = (None, saved) if x0_none else (saved[0], saved[1:])
-    x, h, W, b = rest[0], rest[1], list(rest[2:2 + L]), list(rest[2 + L:])
     nig = ctx.needs_input_grad
     need = [bool(nig[0]) and not x0_none, bool(nig[1]), bool(nig[2]), any(nig[3]) or any(nig[4])]
-    if gF is None and gfx is None:
-        return (None,) * 9
-    gF = x.new_zeros((x.shape[0], W[-1].shape[0])) if gF is None else gF.contiguous()
-    if gfx is None:
-        dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward_multi(x0, x, h, gF, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    else:
-        dx0, dx, dh, dtheta = torch.ops.umnn.cc_backward_multi_fx(x0, x, h, gF, gfx.contiguous(), W, b, hidden_act, out_act, nb_steps,
-                                                                  need, inv_f)
-    gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[3], nig[4])
+    return (x0, rest[0], rest[1]), (list(rest[2:2 + L]), list(rest[2 + L:]), hidden_act, out_act, nb_steps), need, inv_f
+
+
+def _cc_input_grads(ctx, out, W, b, need):
+    dx0, dx, dh, dtheta = out
+    gW, gb = _param_grads(dtheta if need[3] else None, W, b, ctx.needs_input_grad[3], ctx.needs_input_grad[4])
     return (dx0 if need[0] else None, dx if need[1] else None, dh if need[2] else None, gW, gb,
             None, None, None, None)
 
 
+def _cc_forward_backward(ctx, gF, gfx):
+    lims, net, need, inv_f = _cc_saved(ctx)
+    return _cc_input_grads(ctx, torch.ops.umnn.cc_backward(*lims, gF, gfx, *net, need, inv_f), net[0], net[1], need)
+
+
+def _cc_forward_multi_setup(ctx, inputs, output):
+    ctx.set_materialize_grads(False)               # (an f_x nobody differentiates: no zero cotangent, the backward of before)
+    _cc_setup(ctx, inputs, output)
+
+
+def _cc_forward_multi_backward(ctx, gF, gfx):
+    if gF is None and gfx is None:
+        return (None,) * 9
+    (x0, x, h), net, need, inv_f = _cc_saved(ctx)
+    gF = x.new_zeros((x.shape[0], net[0][-1].shape[0])) if gF is None else gF.contiguous()
+    if gfx is None:
+        out = torch.ops.umnn.cc_backward_multi(x0, x, h, gF, *net, need, inv_f)
+    else:
+        out = torch.ops.umnn.cc_backward_multi_fx(x0, x, h, gF, gfx.contiguous(), *net, need, inv_f)
+    return _cc_input_grads(ctx, out, net[0], net[1], need)
+
+
+cc_forward.register_autograd(_cc_forward_backward, setup_context=_cc_setup)
 cc_forward_multi.register_autograd(_cc_forward_multi_backward, setup_context=_cc_forward_multi_setup)
 
 
-def _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f):
-    _check_cc_multi("cc_backward_multi", x0, x, h, W, b, hidden_act, out_act, g)
-    _check_need("cc_backward_multi", need, 4)
+def pure_mlp(W, b, hidden_act, out_act):
+    """The integrand the ops get -- W[], b[] and the activation codes, never a module -- as ``integral.aten_vjp`` takes it:
+    (f(params, x, h), params in parameters() order), f the MLP on the rows [x_i, h_{0,i}, ..., h_{E-1,i}]
+    (nets.IntegrandNetwork.rows) -> [B, d] for one output, [B, n_out] for a multi-output last layer (x [B,1]: the rows are
+    ``cat((x, h), 1)`` itself)."""
+    L, n_in, n_out = len(W), W[0].shape[1], W[-1].shape[0]
+
+    def f(params, x, h):
+        B, d = x.shape
+        a = torch.cat((x, h), 1).view(B, n_in, d).transpose(1, 2).reshape(B * d, n_in)
+        for l in range(L):
+            a = F.linear(a, params[2 * l], params[2 * l + 1])
+            if l + 1 < L:
+                a = F.leaky_relu(a, 0.01) if hidden_act == _lib.ACT_LEAKY_RELU else F.relu(a)
+        return (F.elu(a) + 1. if out_act == _lib.OUT_ELU_PLUS_ONE else torch.sigmoid(a)).view(B, d * n_out)
+
+    return f, [p.detach() for pair in zip(W, b) for p in pair]
 
 
-@torch.library.custom_op("umnn::cc_backward_multi", mutates_args=(), device_types="cuda")
-def cc_backward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, W: List[Tensor], b: List[Tensor],
-                      hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
-    """``integral.quadrature_backward`` of a multi-output integrand given as tensors: the multi-output HIP kernels, or -- decided
-    here at run time -- the one ATen backward on ``pure_mlp_multi``."""
-    _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    return _backward_multi(x0, x, h, g, None, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-
-
-def _backward_multi(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+def _cc_backward(op, multi, x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    """The three backward ops: ``integral.quadrature_backward`` for an integrand given as tensors -- the HIP kernels, or, for the
+    nets ``integral._hip_backward_ok`` / ``_multi_kernels_ok`` turn away, decided here at run time, the one ATen backward on
+    ``pure_mlp``."""
+    _check_cc(op, x0, x, h, W, b, hidden_act, out_act, g, g_fx, need, multi)
     need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
-    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp_multi(W, b, hidden_act, out_act), x0, x, h, g, g_fx,
+    out = _I.quadrature_backward(spec_from_tensors(W, b, hidden_act, out_act), pure_mlp(W, b, hidden_act, out_act), x0, x, h, g, g_fx,
                                  nb_steps, need, inv_f)
     like = (x, x, h, W[0])
     return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
                  for i, (t, n, l) in enumerate(zip(out, need, like)))
 
 
-@cc_backward_multi.register_fake
-def _(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f):
-    _check_cc_backward_multi(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    return _backward_fakes(x0, x, h, W, b, need)
-
-
-def _backward_fakes(x0, x, h, W, b, need):
+def _cc_backward_fake(op, multi, x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    _check_cc(op, x0, x, h, W, b, hidden_act, out_act, g, g_fx, need, multi)
     return (x.new_empty(x.shape) if (need[0] and x0 is not None) else _empty(x),
             x.new_empty(x.shape) if need[1] else _empty(x),
             h.new_empty(h.shape) if need[2] else _empty(h),
             W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
 
 
-def _check_cc_backward_multi_fx(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
-    _check_cc_multi("cc_backward_multi_fx", x0, x, h, W, b, hidden_act, out_act, g, g_fx)
-    _check_need("cc_backward_multi_fx", need, 4)
+@torch.library.custom_op("umnn::cc_backward", mutates_args=(), device_types="cuda")
+def cc_backward(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, g_fx: Optional[Tensor], W: List[Tensor], b: List[Tensor],
+                hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    return _cc_backward("cc_backward", False, x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+
+
+@torch.library.custom_op("umnn::cc_backward_multi", mutates_args=(), device_types="cuda")
+def cc_backward_multi(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, W: List[Tensor], b: List[Tensor],
+                      hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """x [B,1], g [B, n_out] of a multi-output integrand: dx and dx0 [B,1] are sums over the outputs."""
+    return _cc_backward("cc_backward_multi", True, x0, x, h, g, None, W, b, hidden_act, out_act, nb_steps, need, inv_f)
 
 
 @torch.library.custom_op("umnn::cc_backward_multi_fx", mutates_args=(), device_types="cuda")
 def cc_backward_multi_fx(x0: Optional[Tensor], x: Tensor, h: Tensor, g: Tensor, g_fx: Optional[Tensor], W: List[Tensor], b: List[Tensor],
                          hidden_act: int, out_act: int, nb_steps: int, need: List[bool], inv_f: bool) -> tuple[Tensor, Tensor, Tensor, Tensor]:
     """``cc_backward_multi`` with the cotangent ``g_fx`` [B, n_out] of the f_x output on top of ``g`` (None: exactly that op)."""
-    _check_cc_backward_multi_fx(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    return _backward_multi(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+    return _cc_backward("cc_backward_multi_fx", True, x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+
+
+@cc_backward.register_fake
+def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    return _cc_backward_fake("cc_backward", False, x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
+
+
+@cc_backward_multi.register_fake
+def _(x0, x, h, g, W, b, hidden_act, out_act, nb_steps, need, inv_f):
+    return _cc_backward_fake("cc_backward_multi", True, x0, x, h, g, None, W, b, hidden_act, out_act, nb_steps, need, inv_f)
 
 
 @cc_backward_multi_fx.register_fake
 def _(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f):
-    _check_cc_backward_multi_fx(x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
-    return _backward_fakes(x0, x, h, W, b, need)
+    return _cc_backward_fake("cc_backward_multi_fx", True, x0, x, h, g, g_fx, W, b, hidden_act, out_act, nb_steps, need, inv_f)
 
 
 # ---------------------------------------------------------------------------------------------------------- inverse (Newton solve)
 def _check_cc_solve(t, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
-    op = "cc_solve"
-    _check_net(op, t, h, W, b, hidden_act, out_act)
-    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
-    _req(op, lo < hi, f"empty bracket [{lo}, {hi}]")
-    _req(op, tol >= 0, f"tol is {tol}; expected >= 0")
-    _req(op, 1 <= max_iter <= _lib.SOLVE_EVALS_MASK, f"max_iter is {max_iter}; expected 1..{_lib.SOLVE_EVALS_MASK}")
+    _check_net("cc_solve", t, h, W, b, hidden_act, out_act)
+    _check_solve("cc_solve", nb_steps, lo, hi, tol, max_iter)
 
 
 @torch.library.custom_op("umnn::cc_solve", mutates_args=(), device_types="cuda")
@@ -442,10 +393,7 @@ def _check_cc_solve_block(t, h, x_init, W, b, hidden_act, out_act, nb_steps, lo,
     B, d = _check_net(op, t, h, W, b, hidden_act, out_act, _F32)
     if x_init is not None:
         _check_tensor(op, "x_init", x_init, t, (B, d), _F32)
-    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
-    _req(op, lo < hi, f"empty bracket [{lo}, {hi}]")
-    _req(op, tol >= 0, f"tol is {tol}; expected >= 0")
-    _req(op, 1 <= max_iter <= _lib.SOLVE_EVALS_MASK, f"max_iter is {max_iter}; expected 1..{_lib.SOLVE_EVALS_MASK}")
+    _check_solve(op, nb_steps, lo, hi, tol, max_iter)
 
 
 @torch.library.custom_op("umnn::cc_solve_block", mutates_args=(), device_types="cuda")
