@@ -257,6 +257,27 @@ int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, const float*
                               float* dx0, float* dx, float* dh, float* dtheta, void* workspace, long long workspace_bytes, void* stream);
 long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E);
 
+/* Inverse of a weighted sum of the K monotone outputs, for all B rows in ONE launch (cc_multi.hip; MonotonicNN's shape, d = 1): solves
+ *     sum_k coef[b,k] * int_0^{x_b} f_k(t; h_b) dt = target[b]        for x_b in [lo, hi]
+ * with coef >= 0 and a positive entry per row (not checked) -- the event time of K competing risks, a quantile of a mixture of K
+ * CDFs.  The iteration is umnn_cc_solve's, word for word, on S = sum_k coef_k F_k(x) and D = sum_k coef_k f_k(x): start at 0 clamped
+ * into [lo, hi]; the residual r = S - target tightens the bracket by its sign; the next point is x - r / D, or the endpoint it
+ * overshot (each endpoint once, while not yet evaluated), or the bracket's midpoint; a row stops when |r| <= tol * max(1, |target|),
+ * when x sits on the endpoint the target lies beyond (UMNN_SOLVE_CLAMPED; a row of zero coefficients ends so), when its bracket has
+ * collapsed or x has stopped changing; rows still running after max_iter evaluations carry UMNN_SOLVE_CAPPED and their last
+ * evaluated x.  One iteration is one K-output quadrature (the node loop of umnn_cc_forward_multi with upper limit x): exact fp32
+ * MFMA whatever the precision options say, no atomics, two runs are bit-identical.
+ *   h [B,E]   target [B]   coef [B,K], k minor, K = net->widths[n_linear] in [2, UMNN_MAX_OUTPUTS] (anything else: UMNN_EINVAL)
+ *   x [B]     F, f_x [B,K] nullable: F_k and f_k at the returned x     status [B] nullable: the word of umnn_cc_solve
+ * A row whose target, embedding or coefficients hold a NaN returns NaN in x with UMNN_SOLVE_NONFINITE; every other row is
+ * unaffected.  A non-finite F_k marks its row UMNN_SOLVE_NONFINITE under a zero coefficient as well (0 * inf is a NaN).
+ * nb_steps >= 1, 1 <= max_iter <= 65535, lo < hi, tol >= 0, non-null h, target, coef, cc_w, cc_s, x; B == 0 returns 0 and launches
+ * nothing.  UMNN_EUNSUPPORTED when the weight images of the net exceed the LDS (callers iterate umnn_cc_forward_multi themselves). */
+int umnn_cc_solve_multi(const umnn_mlp* net, const float* h, const float* target, const float* coef,
+                        const float* cc_w, const float* cc_s, int nb_steps, long long B, int E,
+                        float lo, float hi, float tol, int max_iter,
+                        float* x, float* F, float* f_x, int* status, void* stream);
+
 /* Training forward / backward pair for nets of the three-stage backward family (first hidden layer of 5..8 sixteen-feature tiles
  * over 2..4 narrower ones: MNISTExperiment's 31-100-50-50-50-50-1, /root/reference MNISTExperiment.py:238).  That backward recomputes
  * the pre-activations z_2 of hidden layer 2 at every node in its stage A and hands them to stage B through HBM; the forward has just

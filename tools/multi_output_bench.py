@@ -28,6 +28,17 @@ and, through the C entries themselves with every buffer allocated once, ``abi_g_
 medians differ by the run-to-run spread of this session) and -- with ``--root DIR``, a built checkout of another commit --
 ``abi_g_only_root`` on DIR/umnn_amd/libumnn_cc.so, alternating with them.  A ``derivative`` line per K gives pair / g_only against the
 node count (n + 2) / (n + 1) of the first backward pass, pair / two_eval, the spread and root / new.
+
+``--inverse-sum`` times the inverse of a weighted sum of the K curves, sum_k coef_k int_0^x f_k = t, per K at ``--rows`` rows and at 100:
+
+    kernel         one launch of umnn_cc_solve_multi (``integral.hip_solve_multi``): the Newton iteration inside the kernel
+    host_loop      ``integral.newton_solve_sum`` over ``hip_forward_multi``: one forward launch and a handful of elementwise launches
+                   per iteration, with a sync for the stop test -- the only route without the solve kernel
+    api            ``MonotonicNN.inverse_sum`` under no_grad: the conditioner, the elementwise glue and the kernel
+
+Wall-clock milliseconds between two device synchronisations (the host loop's cost is largely host time), variants alternating
+within a round.  A ``solve`` line per (K, rows) gives the launch counts of one call, the evaluations per row (mean, max) of both
+routes, the largest |x_kernel - x_host| D in units of the stop bound tol max(1, |t|), and kernel / host_loop.
 """
 import argparse
 import json
@@ -47,6 +58,7 @@ def main():
     ap.add_argument("--label", default="")
     ap.add_argument("--derivative", action="store_true")
     ap.add_argument("--root", default=None)
+    ap.add_argument("--inverse-sum", action="store_true")
     args = ap.parse_args()
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
     import torch
@@ -81,6 +93,9 @@ def main():
     need = (False, True, True, True)
     if args.derivative:
         derivative(args, emit, timed)
+        args.only_k = ""
+    if args.inverse_sum:
+        inverse_sum(args, emit)
         args.only_k = ""
     for K in [int(k) for k in args.only_k.split(",") if k]:
         torch.manual_seed(K)
@@ -254,6 +269,78 @@ def derivative(args, emit, timed):
               "pair_over_two_eval": med["pair"] / med["two_eval"],
               "spread": abs(med["abi_g_only_a"] - med["abi_g_only_b"]) / new,
               "root_over_new": med["abi_g_only_root"] / new if root is not None else None})
+
+
+def inverse_sum(args, emit):
+    import time
+    import torch
+    import umnn_amd
+    from umnn_amd import _lib, integral as I
+    from umnn_amd.nets import mlp_spec
+
+    dev = torch.device("cuda:0")
+    n, tol, lo, hi, max_iter = args.nb_steps, 1e-6, -50., 50., 64
+    launches = _lib.lib().umnn_launch_count
+
+    def wall(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return (time.perf_counter() - t0) * 1e3
+
+    for K in [int(k) for k in args.only_k.split(",")]:
+        for B in (args.rows, 100):
+            torch.manual_seed(K)
+            m = umnn_amd.MonotonicNN(3, [100, 100, 100], nb_steps=n, n_out=K).to(dev)
+            spec = mlp_spec(m.integrand)
+            gen = torch.Generator(device="cpu").manual_seed(2000 + K)
+            x = (torch.randn(B, 1, generator=gen) * 2).to(dev)
+            h = torch.randn(B, 2, generator=gen).to(dev)
+            w = (0.5 + torch.rand(B, K, generator=gen)).to(dev)
+            with torch.no_grad():
+                out = m.net(h)
+                coef = (w * torch.exp(out[:, K:])).contiguous()
+                t = (coef * I.hip_forward_multi(spec, None, x, h, n)[0]).sum(1, keepdim=True)
+                y = t + (w * out[:, :K]).sum(1, keepdim=True)
+
+                def kernel():
+                    return I.hip_solve_multi(spec, h, t, coef, n, lo, hi, tol, max_iter)
+
+                def host_loop():
+                    return I.newton_solve_sum(I.quadrature_eval(spec, None, h, n, True), t, coef, lo, hi, tol, max_iter)
+
+                def api():
+                    return m.inverse_sum(y, h, w, (lo, hi), tol, max_iter)
+
+                variants = {"kernel": kernel, "host_loop": host_loop, "api": api}
+                counts, results = {}, {}
+                for name, fn in variants.items():
+                    before = launches()
+                    results[name] = fn()
+                    counts[name] = launches() - before
+                kernel()
+                kname = _lib.lib().umnn_last_kernel_name().decode()
+                for fn in variants.values():
+                    for _ in range(args.warmup):
+                        fn()
+                times = {name: [] for name in variants}
+                for _ in range(args.reps):
+                    for name, fn in variants.items():
+                        times[name].append(wall(fn))
+            med = {}
+            for name, ts in times.items():
+                med[name] = statistics.median(ts)
+                emit({"kind": "time", "K": K, "direction": "inverse_sum", "variant": name, "rows": B, "nb_steps": n, "reps": len(ts),
+                      "median_ms": med[name], "min_ms": min(ts), "max_ms": max(ts), "mean_ms": statistics.fmean(ts)})
+            (xk, _, fk, sk), (xh, _, _, sh) = results["kernel"], results["host_loop"]
+            ek, eh = (sk & _lib.SOLVE_EVALS_MASK).float(), (sh & _lib.SOLVE_EVALS_MASK).float()
+            D = (coef * fk).sum(1, keepdim=True)
+            emit({"kind": "solve", "K": K, "rows": B, "nb_steps": n, "kernel": kname, "quadrature_launches": counts,
+                  "evals_per_row_kernel": [float(ek.mean()), float(ek.max())], "evals_per_row_host_loop": [float(eh.mean()), float(eh.max())],
+                  "flagged_rows_kernel": int((sk & ~_lib.SOLVE_EVALS_MASK != 0).sum()),
+                  "max_x_gap_in_stop_bounds": float(((xk - xh).abs() * D / (tol * t.abs().clamp(min=1.))).max()),
+                  "kernel_over_host_loop": med["kernel"] / med["host_loop"], "kernel_not_slower": med["kernel"] <= med["host_loop"]})
 
 
 if __name__ == "__main__":

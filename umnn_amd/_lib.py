@@ -90,6 +90,8 @@ SIGNATURES = {
     "umnn_cc_backward_multi_fx": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                                  _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_multi_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),
+    "umnn_cc_solve_multi": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int, _ll, ctypes.c_int,
+                                           ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, _fp, _fp, _fp, _fp, _fp]),
     "umnn_cc_tables_host": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_float),
                                            ctypes.POINTER(ctypes.c_float)]),
     "umnn_cc_forward_flops_per_integral": (ctypes.c_double, [ctypes.POINTER(MlpDesc), ctypes.c_int]),

@@ -14,6 +14,9 @@
 // of kMultiFamilies, so the kernels carry no runtime tile counts.  A padded unit has zero weights and bias: z = 0, act(0) = 0, and
 // it contributes exact zeros to every sum.
 //
+// Inverse (umnn_cc_solve_multi, cc_solve_multi_kernel): the forward's node loop inside the Newton iteration of umnn_cc_solve, for
+// x with sum_k coef_k int_0^x f_k = target; see the kernel.
+//
 // Backward (the reference's gradient convention, ParallelNeuralIntegral.py:66-94,110-123, summed over the K outputs): persistent
 // waves, the forward chain recomputed per node keeping sign bits, delta through W^T on MFMA, dW_l += delta_{l+1} (x) a_l through a
 // wave-private LDS transpose, dc = sum_j delta_1 to the finishing kernels (d_h, dW_1[:, 1:], db_1), per-wave d_theta slices summed
@@ -237,6 +240,227 @@ __global__ __launch_bounds__(UMNN_BLOCK) void cc_fwd_multi_kernel(const MultiArg
             if (a.fx) a.fx[o] = fxv[pt][r];
             if (a.fx0) a.fx0[o] = fx0v[pt][r];
         }
+    }
+}
+
+// ------------------------------------------------------------------------------------------ Newton solve of a weighted sum
+// sum_k coef[b][k] int_0^{x_b} f_k(t; h_b) dt = target[b] for x_b in [lo, hi] (umnn_cc_solve_multi; d = 1): cc_fwd_multi_kernel's
+// node loop with x0 = 0, dxv = x and P = 1 -- one 16-row tile per wave -- inside the iteration of umnn_cc_solve (the INV = 2 block
+// of cc_fwd_bf16_kernel.h, word for word).  The staging and the hoisted first-layer term depend on the weights and h only and run
+// once per launch.  After the node loop a lane holds F_k and f_k(x) of the outputs k = 4r + g it owns; S = sum_k coef_k F_k and
+// D = sum_k coef_k f_k are a four-term fmaf chain per lane (coefficient 0 for k >= K: the padded outputs are finite and add exact
+// zeros) and a butterfly over the four lane groups (xor 16, 32).  fp32 addition is commutative, so all four copies of a row end
+// with the same bits, take the same step and cast the same vote.  A non-finite F_k makes S non-finite under a zero coefficient as
+// well (0 * inf is a NaN): such a row ends UMNN_SOLVE_NONFINITE.
+
+// the output tile as cc_fwd_multi_kernel stages it (a copy of its text: as a helper shared with the forward it moved that kernel's
+// scalar register counts)
+template <int KSC>
+__device__ __forceinline__ void stage_output_tile(const MlpDev& m, float* img, int K, int tid) {
+    const int L = m.n_linear - 1, HL = m.width[L];
+    const float* __restrict__ WL = m.W[L];
+    const float* __restrict__ bL = m.b[L];
+    for (int idx = tid; idx < KSC * 64; idx += UMNN_BLOCK) {
+        const int ln = idx & 63, s = idx >> 6;
+        const int k = fout_of(0, ln & 15), fi = 4 * s + (ln >> 4);
+        float v = 0.f;
+        if (k < K) {
+            if (fi < HL) v = WL[k * HL + fi];
+            else if (fi == HL) v = bL[k];
+        }
+        img[idx] = v;
+    }
+}
+
+struct SolveMultiArgs {
+    MultiArgs a;                    // m, h, ccw, ccs, F (nullable here), fx (nullable), NI, E, n, K, ngroups, out_off
+    const float* target;            // [NI]
+    const float* coef;              // [NI][K]
+    float* x;                       // [NI]
+    int* status;                    // [NI], nullable
+    float lo, hi, tol;
+    int max_iter;
+};
+
+template <int TMAX, int KSC>
+__global__ __launch_bounds__(UMNN_BLOCK) void cc_solve_multi_kernel(const SolveMultiArgs sa) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const MultiArgs& a = sa.a;
+    const MlpDev& m = a.m;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, p = lane & 15;
+    const int L = m.n_linear - 1;
+    const int H1 = m.width[1], K = a.K;
+    const int E = a.E, n = a.n;
+    const float slope = m.hidden_act == UMNN_ACT_RELU ? 0.f : 0.01f;
+
+    stage_hidden_images(m, lds, tid, UMNN_BLOCK);
+    stage_output_tile<KSC>(m, lds + a.out_off, K, tid);
+    __syncthreads();
+
+    const unsigned grp = xcd_remap(blockIdx.x, gridDim.x) * UMNN_WAVES_PER_BLOCK + wid;
+    if (grp >= a.ngroups) return;
+
+    // lane p's row; lanes beyond the batch mirror the last row, never run and store nothing
+    const long long q = (long long)grp * 16 + p;
+    const bool ok = q < a.NI;
+    const long long qq = ok ? q : a.NI - 1;
+    const IoView hb = IoView{a.h, 0} + qq * (long long)E;
+    const float target = sa.target[qq];
+    f32x4 cf;
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int k = 4 * r + g;
+        cf[r] = k < K ? sa.coef[qq * K + k] : 0.f;
+    }
+
+    // ---- per-lane constants: first-layer x-column
+    float w1x[TMAX][4];
+    {
+        const float* __restrict__ W0 = m.W[0];
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = feat_of(t, r, g);
+                w1x[t][r] = f < H1 ? W0[f * (1 + E)] : 0.f;
+            }
+    }
+
+    // ---- hoisted first-layer term c = W1[:,1:] h + b1 (and the constant-one feature), on MFMA: once for all iterations
+    f32x4 c[TMAX];
+    {
+        const float* __restrict__ W0 = m.W[0];
+        const float* __restrict__ b0 = m.b[0];
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = feat_of(t, r, g);
+                c[t][r] = f < H1 ? b0[f] : (f == H1 ? 1.f : 0.f);
+            }
+        for (int se = 0; se < (E + 3) / 4; ++se) {
+            const int e = 4 * se + g;
+            const float hv = e < E ? hb[(long long)e] : 0.f;
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t) {
+                const int fo = fout_of(t, p);
+                const float A = (fo < H1 && e < E) ? W0[fo * (1 + E) + 1 + e] : 0.f;
+                c[t] = mfma16(A, hv, c[t]);
+            }
+        }
+    }
+
+    // ---- Newton state: lane p's row; every lane group g holds the same values
+    float sv_a = sa.lo, sv_b = sa.hi;
+    float sv_x = fminf(fmaxf(0.f, sa.lo), sa.hi);
+    bool sv_done = !ok, sv_aopen = true, sv_bopen = true, sv_bad = false;
+    int sv_stat = 0;
+    f32x4 Fout = f32x4{0.f, 0.f, 0.f, 0.f}, fout = f32x4{0.f, 0.f, 0.f, 0.f};      // F_k, f_k at the row's last evaluated x
+
+    const float* oimg = lds + a.out_off + lane;
+    const int rounds = sa.max_iter;
+    for (int round = 0; round < rounds; ++round) {
+        const float xv = sv_x;
+        f32x4 Facc = f32x4{0.f, 0.f, 0.f, 0.f}, fxv = f32x4{0.f, 0.f, 0.f, 0.f};
+        // ---- walk the quadrature nodes (cc_fwd_multi_kernel: x0 = 0, dxv = x)
+        for (int k = 0; k <= n; ++k) {
+            const float u = a.ccs[k] + 1.f;
+            const float wk = a.ccw[k];
+            const float tk = k == 0 ? xv : __fadd_rn(0.f, __fmul_rn(xv, u) * 0.5f);
+            f32x4 act[TMAX];
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) act[t][r] = hidden_act_f(fmaf(w1x[t][r], tk, c[t][r]), slope);
+            for (int l = 1; l < L; ++l) {
+                const float* img = lds + m.lds_off[l] + lane;
+                f32x4 acc[TMAX];
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t) acc[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int s = 0; s < KSC; ++s)
+#pragma unroll
+                    for (int t = 0; t < TMAX; ++t) acc[t] = mfma16(img[(t * KSC + s) * 64], act[s >> 2][s & 3], acc[t]);
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) act[t][r] = hidden_act_f(acc[t][r], slope);
+            }
+            // the output tile: component r of lane (g, p) = s_k of output k = 4r + g
+            f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < KSC; ++s) o = mfma16(oimg[s * 64], act[s >> 2][s & 3], o);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float f = out_act_f(o[r], m.out_act);
+                Facc[r] = fmaf(wk, f, Facc[r]);
+                if (k == 0) fxv[r] = f;
+            }
+        }
+        // ---- S = sum_k coef_k F_k, D = sum_k coef_k f_k: the same bits in all four lane groups
+        f32x4 Fk;
+        float S = 0.f, D = 0.f;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            Fk[r] = Facc[r] * xv * 0.5f;
+            S = fmaf(cf[r], Fk[r], S);
+            D = fmaf(cf[r], fxv[r], D);
+        }
+        S += __shfl_xor(S, 16); D += __shfl_xor(D, 16);
+        S += __shfl_xor(S, 32); D += __shfl_xor(D, 32);
+
+        if (!sv_done) {
+            ++sv_stat;
+            Fout = Fk; fout = fxv;
+            const float r = S - target;
+            if (!(__builtin_fabsf(S) < __builtin_inff()) || r != r) {
+                sv_bad = true; sv_done = true;                   // a NaN in the target, the embedding or the coefficients; a non-finite F_k
+            } else if (fabsf(r) <= sa.tol * fmaxf(1.f, fabsf(target)) && fabsf(r) < __builtin_inff()) {   // (no x meets an infinite target: the bound is infinite too)
+                sv_done = true;
+            } else {
+                if (r > 0.f) {
+                    if (sv_x <= sa.lo) { sv_stat |= UMNN_SOLVE_CLAMPED; sv_done = true; }      // target below G(lo)
+                    sv_b = sv_x; sv_bopen = false;
+                } else {
+                    if (sv_x >= sa.hi) { sv_stat |= UMNN_SOLVE_CLAMPED; sv_done = true; }      // target above G(hi)
+                    sv_a = sv_x; sv_aopen = false;
+                }
+                if (!sv_done) {
+                    float xn = sv_x - r / D;
+                    if (!(xn > sv_a && xn < sv_b)) {
+                        if (xn >= sv_b && sv_bopen) { xn = sv_b; sv_bopen = false; }       // overshot an endpoint not yet evaluated: try it
+                        else if (xn <= sv_a && sv_aopen) { xn = sv_a; sv_aopen = false; }
+                        else {
+                            xn = 0.5f * (sv_a + sv_b);
+                            if (!(xn > sv_a && xn < sv_b)) sv_done = true;                 // bracket collapsed to adjacent floats
+                        }
+                    }
+                    if (!sv_done) {
+                        if (xn == sv_x) sv_done = true;                                    // x has stopped changing
+                        else if (round + 1 < rounds) sv_x = xn;                            // (the last evaluated point is what leaves)
+                    }
+                }
+            }
+        }
+        if (__all(sv_done)) break;
+    }
+
+    // ---- lane group 0 writes x and status; every lane the (up to four) outputs of F and f_x it owns, as the forward does
+    if (!ok) return;
+    if (g == 0) {
+        if (!sv_done) sv_stat |= UMNN_SOLVE_CAPPED;
+        if (sv_bad) sv_stat |= UMNN_SOLVE_NONFINITE;
+        sa.x[qq] = sv_bad ? __builtin_nanf("") : sv_x;
+        if (sa.status) sa.status[qq] = sv_stat;
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int k = 4 * r + g;
+        if (k >= K) continue;
+        if (a.F) a.F[qq * K + k] = Fout[r];
+        if (a.fx) a.fx[qq * K + k] = fout[r];
     }
 }
 
@@ -766,6 +990,53 @@ extern "C" int umnn_cc_forward_multi(const umnn_mlp* net, const float* x0, const
     umnn_prof_end(stream, umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI, UMNN_PROF_FORWARD);
     umnn_note_launch(v->name);
     return umnn_check(hipGetLastError(), "cc_fwd_multi launch");
+}
+
+typedef void (*solve_multi_kernel_t)(const SolveMultiArgs);
+struct MultiSolveVariant { int T, KS; solve_multi_kernel_t fn; const char* name; };
+#define MULTI_SOLVE(T, KS) { T, KS, cc_solve_multi_kernel<T, KS>, "cc_solve_multi<T=" #T ",KS=" #KS ">" }
+static const MultiSolveVariant kMultiSolve[] = {
+    MULTI_SOLVE(2, 8), MULTI_SOLVE(4, 13), MULTI_SOLVE(4, 16), MULTI_SOLVE(7, 26), MULTI_SOLVE(8, 32),
+};
+
+// The forward's plan, images and grid (one 16-row tile per wave); the argument checks of solve_entry (cc_solve.hip).
+extern "C" int umnn_cc_solve_multi(const umnn_mlp* net, const float* h, const float* target, const float* coef,
+                                   const float* cc_w, const float* cc_s, int nb_steps, long long B, int E,
+                                   float lo, float hi, float tol, int max_iter,
+                                   float* x, float* F, float* f_x, int* status, void* stream_) {
+    hipStream_t stream = (hipStream_t)stream_;
+    if (!net) return umnn_fail(UMNN_EINVAL, "net is null");
+    if (nb_steps < 1 || max_iter < 1 || max_iter > UMNN_SOLVE_EVALS_MASK)
+        return umnn_fail(UMNN_EINVAL, "solve_multi: nb_steps >= 1 and 1 <= max_iter <= 65535");
+    if (B < 0) return umnn_fail(UMNN_EINVAL, "solve_multi: B must be >= 0");
+    if (!(lo < hi) || !(tol >= 0.f)) return umnn_fail(UMNN_EINVAL, "solve_multi: lo < hi and tol >= 0");
+    SolveMultiArgs sa;
+    MultiPlan pl;
+    if (int rc = multi_plan(net, E, &pl)) return rc;
+    if (B == 0) return 0;
+    if (!h || !target || !coef || !cc_w || !cc_s || !x)
+        return umnn_fail(UMNN_EINVAL, "solve_multi: h, target, coef, cc_w, cc_s, x must be non-null");
+    sa.a = pl.a;
+    MultiArgs& a = sa.a;
+    a.h = h; a.ccw = cc_w; a.ccs = cc_s; a.F = F; a.fx = f_x;
+    a.NI = B; a.d = 1; a.E = E; a.n = nb_steps;
+    sa.target = target; sa.coef = coef; sa.x = x; sa.status = status;
+    sa.lo = lo; sa.hi = hi; sa.tol = tol; sa.max_iter = max_iter;
+    const long long tiles = (B + 15) / 16;
+    if (tiles > 0x7fffffffLL) return umnn_fail(UMNN_EUNSUPPORTED, "solve_multi: batch too large");
+    a.ngroups = (unsigned)tiles;
+    const MultiSolveVariant* v = nullptr;
+    for (const MultiSolveVariant& c : kMultiSolve)
+        if (c.T == pl.T && c.KS == pl.KS) v = &c;
+    if (!v) return umnn_fail(UMNN_EUNSUPPORTED, "solve_multi: no kernel variant");
+    if (int rc = umnn_allow_lds((const void*)v->fn, pl.fwd_lds)) return rc;
+    const unsigned blocks = (a.ngroups + UMNN_WAVES_PER_BLOCK - 1) / UMNN_WAVES_PER_BLOCK;
+    umnn_prof_begin(stream);
+    hipLaunchKernelGGL(v->fn, dim3(blocks), dim3(UMNN_BLOCK), pl.fwd_lds, stream, sa);
+    // algorithmic work: the iteration count is decided inside the launch -- booked at four quadratures per row, like umnn_cc_solve
+    umnn_prof_end(stream, umnn_cc_forward_flops_per_integral(net, nb_steps) * 4.0 * (double)B, UMNN_PROF_FORWARD);
+    umnn_note_launch(v->name);
+    return umnn_check(hipGetLastError(), "cc_solve_multi launch");
 }
 
 // workspace: [d_theta slices: 4 waves x CUs][dc: NI x H1][first-layer partials: nparts0 x H1 (E + 1)]

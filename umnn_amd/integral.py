@@ -446,13 +446,14 @@ def hip_invert_dim(spec, h, z, scaling, nb_steps, j, iters, x_inv):
         "host-driven bracket search (d x iter forward launches per block).")
 
 
-def _solve_call(fn_name, spec, h, target, nb_steps, x_out, want_info, info_shape, call):
-    """hip_solve / hip_solve_block: allocates x_out (when None) and the ``info_shape`` f_x / status (when ``want_info``), runs
+def _solve_call(fn_name, spec, h, target, nb_steps, x_out, want_info, info_shape, call, fx_shape=None):
+    """hip_solve / hip_solve_block / hip_solve_multi: allocates x_out (when None) and the ``info_shape`` f_x / status (when
+    ``want_info``; ``fx_shape``: an f_x of another shape than status, the [B,K] of the multi-output solve), runs
     ``call(lib, desc, w, s, B, d, E, stream, x_out, fx, status)`` -> rc.  -> (x_out, f_x, status), or None without a kernel."""
     dev = target.device
     if x_out is None:
         x_out = torch.empty(target.shape, device=dev, dtype=torch.float32)
-    fx = torch.empty(info_shape, device=dev, dtype=torch.float32) if want_info else None
+    fx = torch.empty(info_shape if fx_shape is None else fx_shape, device=dev, dtype=torch.float32) if want_info else None
     status = torch.empty(info_shape, device=dev, dtype=torch.int32) if want_info else None
     ok = _inverse_call(
         fn_name, spec, h, target, nb_steps, lambda *a: call(*a, _ptr(x_out), _ptr(fx), _ptr(status)),
@@ -499,6 +500,25 @@ def hip_solve_block(spec, h, target, nb_steps, scaling=None, off_h0=False, x_ini
         lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve_block(
             desc, _ptr(h), _ptr(target), _ptr(scaling), 1 if off_h0 else 0, _ptr(x_init), w, s, int(nb_steps), B, d, E,
             float(lo), float(hi), float(tol), int(max_iter), x, fx, status, stream))
+
+
+def hip_solve_multi(spec, h, target, coef, nb_steps, lo=-50., hi=50., tol=1e-6, max_iter=64):
+    """Newton solve of a weighted sum of the K outputs of a multi-output integrand for every row in ONE launch
+    (umnn_cc_solve_multi): sum_k coef[b,k] int_0^x f_k(t; h_b) dt = target[b].  ``target`` [B,1], ``coef`` [B,K] and ``h`` [B,E] fp32
+    contiguous.  -> (x [B,1], F [B,K], f_x [B,K], status [B,1] int32), F_k and f_k at the returned x.  Exact fp32 kernels whatever
+    ``set_precision`` says.  Returns None when the library has no kernel for this net (its images exceed the LDS): the caller runs
+    ``newton_solve_sum`` over ``hip_forward_multi``."""
+    B, K = target.shape[0], n_out_of(spec)
+    if target.shape != (B, 1) or coef.shape != (B, K):
+        raise RuntimeError(f"umnn_amd: the weighted-sum solve takes a target [B, 1] and coefficients [B, {K}]; got "
+                           f"{tuple(target.shape)} and {tuple(coef.shape)}")
+    F = torch.empty((B, K), device=target.device, dtype=torch.float32)
+    out = _solve_call(
+        "umnn_cc_solve_multi", spec, h, target, nb_steps, None, True, (B, 1),
+        lambda lib, desc, w, s, B, d, E, stream, x, fx, status: lib.umnn_cc_solve_multi(
+            desc, _ptr(h), _ptr(target), _ptr(coef), w, s, int(nb_steps), B, E, float(lo), float(hi), float(tol), int(max_iter),
+            x, _ptr(F), fx, status, stream), fx_shape=(B, K))
+    return None if out is None else (out[0], F, out[1], out[2])
 
 
 def newton_solve(eval_fn, target, scale, off, lo, hi, tol, max_iter, x_init=None):
@@ -563,8 +583,8 @@ def quadrature_eval(spec, integrand, h, nb_steps, use_hip, column=False):
     ``use_hip`` one ``hip_forward`` launch per call (F and f_x together), else the ATen quadrature and one pass of the integrand.
     ``h`` is used as given (the caller brings it to x's dtype for the ATen form).  ``column``: x is the [B,1] column of one flow
     dimension and ``h`` its [B,E] embedding rows, which the ATen form evaluates through ``integrand.independant_forward``."""
-    if use_hip:
-        return lambda x: hip_forward(spec, None, x, h, nb_steps)[:2]
+    if use_hip:       # (a multi-output spec: F and f_x [B,K] of ``hip_forward_multi`` for x [B,1])
+        return lambda x: hip_forward(spec, None, x, h, nb_steps, multi=n_out_of(spec) > 1)[:2]
     f = (lambda x, hh: integrand.independant_forward(torch.cat((x, hh), 1))) if column else integrand
     return lambda x: (aten_forward(f, torch.zeros_like(x), x, h, nb_steps), f(x, h))
 
@@ -602,6 +622,41 @@ def solve_integral(spec, t, h, nb_steps, lo, hi, tol, max_iter):
             if B > 0:
                 fx[:, j], status[:, j] = out[1], out[2]
     return x.to(t.dtype), fx.to(t.dtype), status
+
+
+def newton_solve_sum(eval_fn, target, coef, lo, hi, tol, max_iter):
+    """``newton_solve`` on a weighted sum of K monotone curves: sum_k coef[b,k] F_k(x_b) = target[b], where ``eval_fn(x [B,1]) ->
+    (F [B,K], f [B,K])``.  -> (x [B,1], F [B,K], f [B,K], status [B,1]), F and f at the returned x (one more evaluation).  A
+    non-finite F_k marks its row SOLVE_NONFINITE under a zero coefficient too (0 * inf is a NaN), like the kernel."""
+    def sums(x):
+        F, f = eval_fn(x)
+        return (coef * F).sum(1, keepdim=True), (coef * f).sum(1, keepdim=True)
+
+    with torch.no_grad():
+        x, _, status = newton_solve(sums, target, 1., 0., lo, hi, tol, max_iter)
+        F, f = eval_fn(x)
+    return x, F, f, status
+
+
+def solve_sum(spec, integrand, t, coef, h, nb_steps, lo, hi, tol, max_iter):
+    """x [B,1] with sum_k coef[b,k] int_0^x f_k(s; h_b) ds = t[b] -> (x, F, f_x, status): F, f_x [B,K] at x in t's dtype, status
+    [B,1] int32.  ``spec`` (the HIP path): the in-kernel solve of umnn_cc_solve_multi, or -- for nets whose images exceed the LDS,
+    after a one-time notice -- ``newton_solve_sum`` over ``hip_forward_multi``, one launch per iteration.  ``spec`` None: the same
+    iteration on the ATen quadrature of ``integrand`` (CPU tensors, float64, integrands ``mlp_spec`` does not recognise)."""
+    if t.shape[0] == 0:
+        return t.new_empty(t.shape), t.new_empty(coef.shape), t.new_empty(coef.shape), t.new_empty(t.shape, dtype=torch.int32)
+    if spec is None:
+        out = newton_solve_sum(quadrature_eval(None, integrand, h.detach(), nb_steps, False), t.detach(), coef.detach(), lo, hi, tol,
+                               max_iter)
+        _state.path = "aten"
+        return out
+    t32, c32, h32 = _f32c(t), _f32c(coef), _f32c(h)
+    with torch.no_grad():
+        out = hip_solve_multi(spec, h32, t32, c32, nb_steps, lo, hi, tol, max_iter)
+        if out is None:
+            out = newton_solve_sum(quadrature_eval(spec, None, h32, nb_steps, True), t32, c32, lo, hi, tol, max_iter)
+    x, F, fx, status = out
+    return x.to(t.dtype), F.to(t.dtype), fx.to(t.dtype), status
 
 
 _row_counters = {}     # (device index, stream handle) -> zeroed uint32 [>= B] arrival counters (kernel leaves them zero)
@@ -1242,3 +1297,50 @@ class InverseNeuralIntegral(torch.autograd.Function):
             _, _, dh, dtheta = _launch_backward(net, ctx.spec, ctx.integrand, None, x, h, -g_t, None, ctx.nb_steps,
                                                 (False, False, nig[3], nig[2]))
         return (g_t if nig[0] else None, None, dtheta, dh, None, None, None, None, None)
+
+
+class InverseIntegralSum(torch.autograd.Function):
+    """x [B,1] with sum_k coef[b,k] int_0^x f_k(s; h_b) ds = t[b]: the inverse, in x, of a non-negative combination of the K curves
+    of a multi-output integrand -- the event time of K competing risks (sum_k H_k(T) = -log U), a quantile of a mixture of K CDFs.
+
+        InverseIntegralSum.apply(t, coef, integrand, flat_params, h, nb_steps=20, x_range=(-50., 50.), tol=1e-6, max_iter=64,
+                                 return_info=False)  ->  x [B,1]   or   (x, f [B,K], status [B,1])
+
+    t [B,1], coef [B,K] with coef >= 0 and a positive entry per row (not checked: a check would synchronise; a row of zeros follows
+    the clamping rule).  On GPU tensors an MLP integrand of 2..16 outputs is ONE launch of umnn_cc_solve_multi (the safeguarded
+    Newton iteration of umnn_cc_solve on the K-output quadrature, exact fp32); everything else runs ``newton_solve_sum``.  f is
+    f_k(x; h) at the returned x (cause probabilities are proportional to coef_k f_k), status the word of ``InverseNeuralIntegral``.
+
+    Once-differentiable by the implicit-function theorem, from what the forward saved and one existing backward: with
+    D = sum_k coef_k f_k(x),  g_t = g_x / D,  g_coef = -g_t F_k(x),  and (d_theta, d_h) those of the K integrals up to x for the
+    cotangent -g_t coef [B,K] (the multi-output backward).  No special case for clamped rows, as in ``InverseNeuralIntegral``."""
+
+    @staticmethod
+    def forward(ctx, t, coef, integrand, flat_params, h, nb_steps=20, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False):
+        lo, hi = float(x_range[0]), float(x_range[1])
+        if coef.dim() != 2 or coef.shape[0] != t.shape[0] or coef.shape[1] < 2:
+            raise RuntimeError(f"umnn_amd: InverseIntegralSum takes coef [B, K] with K >= 2 next to t [B, 1]; got {tuple(coef.shape)} "
+                               f"and {tuple(t.shape)} (one curve: InverseNeuralIntegral on t / coef)")
+        spec = _hip_spec(integrand, t, multi=True, who="InverseIntegralSum")
+        if spec is not None and _graph_mode():
+            x, F, fx, status = torch.ops.umnn.cc_solve_multi(t, coef, h, *spec_args(spec), int(nb_steps), lo, hi, float(tol), int(max_iter))
+        else:
+            x, F, fx, status = solve_sum(spec, integrand, t, coef, h, nb_steps, lo, hi, tol, max_iter)
+        ctx.nb_steps = nb_steps
+        _save(ctx, spec, integrand, x, h, coef, F, fx)
+        if not return_info:
+            return x
+        ctx.mark_non_differentiable(fx, status)
+        return x, fx, status
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_x, *_unused):
+        nig = ctx.needs_input_grad
+        (x, h, coef, F, fx), net = _saved(ctx, 5)
+        g_t = g_x / (coef * fx).sum(1, keepdim=True)
+        dh = dtheta = None
+        if nig[3] or nig[4]:
+            _, _, dh, dtheta = _launch_backward(net, ctx.spec, ctx.integrand, None, x, h, -g_t * coef, None, ctx.nb_steps,
+                                                (False, False, nig[4], nig[3]))
+        return (g_t if nig[0] else None, -g_t * F if nig[1] else None, None, dtheta, dh, None, None, None, None, None)

@@ -12,13 +12,14 @@ integrals are ONE launch of the multi-output kernels (csrc/cc_multi.hip: exact f
 
 ``inverse(y, h)`` (an extension of this package: the reference has no such method) returns the x with forward(x, h) = y --
 quantile functions, inverse-CDF sampling, calibration maps -- by the in-kernel Newton solve, differentiable in y, h and every parameter;
-``output=k`` picks the function to invert when ``n_out > 1``.
+``output=k`` picks the function to invert when ``n_out > 1``.  ``inverse_sum(y, h, weights)`` inverts a non-negative combination
+sum_k w_k y_k of the K curves -- the event time of competing risks, a quantile of a mixture of CDFs -- in one solve launch.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .integral import IntegralWithDerivative, InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
+from .integral import IntegralWithDerivative, InverseIntegralSum, InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
 from .nets import IntegrandNN, MlpSpec, TensorLinear, _spec_from_sequential  # noqa: F401  (IntegrandNN is re-exported)
 
 
@@ -132,3 +133,23 @@ class MonotonicNN(nn.Module):
                                                x_range, tol, max_iter, return_info)
         row = OutputRow(self.integrand, k)
         return InverseNeuralIntegral.apply(t, row, _flatten(row.row_params()), h, self.nb_steps, x_range, tol, max_iter, return_info)
+
+    def inverse_sum(self, y, h, weights=None, x_range=(-50., 50.), tol=1e-6, max_iter=64, return_info=False):
+        """x [B,1] in ``x_range`` with ``sum_k w_k forward(x, h)[:, k] = y``: the inverse of a non-negative combination of the
+        ``n_out`` curves, which is increasing in x like each of them -- the event time T of competing risks, sum_k H_k(T) = -log U
+        (median survival at y = log 2), a quantile of the mixture sum_k pi_k F_k.  ``weights``: None (all ones), [n_out], or
+        [B, n_out] (which may come from a network and receives gradients); they must be non-negative with a positive one per row
+        -- documented, not checked: a check would synchronise -- and a row of zeros follows the clamping rule.  On GPU tensors the
+        solve is ONE launch (``InverseIntegralSum``: the Newton iteration runs inside the K-output quadrature kernel) on
+        coef = w exp(s(h)) and t = y - sum_k w_k o_k(h), to ``tol * max(1, |t|)``.  Gradients reach y, the weights, h, the
+        conditioner and the integrand.  ``return_info=True`` -> (x, f_k(x; h) [B, n_out], status): cause k then has probability
+        proportional to coef_k f_k; status as in ``inverse``.  ``n_out == 1`` is ``inverse`` of y / w."""
+        offset, log_scaling = self._offset_log_scaling(h)
+        w = torch.ones_like(offset) if weights is None else weights.to(offset.dtype).expand_as(offset)
+        coef = w * torch.exp(log_scaling)
+        t = y - (w * offset).sum(1, keepdim=True)
+        if self.n_out == 1:
+            return InverseNeuralIntegral.apply(t / coef, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
+                                               x_range, tol, max_iter, return_info)
+        return InverseIntegralSum.apply(t, coef, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
+                                        x_range, tol, max_iter, return_info)

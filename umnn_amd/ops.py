@@ -8,6 +8,8 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
     umnn::cc_backward_multi_fx(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
     umnn::cc_solve_block(t, h, x_init?, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
+    umnn::cc_solve_multi(t, coef, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, F, f_x, status)
+        t, x, status [B,1]; coef, F, f_x [B, n_out]: x with sum_k coef_k int_0^x f_k = t
     umnn::flow_block(x, h, scaling, W[], b[], hidden_act, out_act, nb_steps, reverse_z, log_jac_in?) -> (z, log_jac, f_x)
     umnn::flow_block_backward(x, h, scaling, f_x, gz, glj, W[], b[], hidden_act, out_act, nb_steps, reverse_z, need[3])
         -> (dx, dh, dtheta)
@@ -21,7 +23,8 @@ implementation calls the eager path's own ``integral.hip_*`` function (same arit
 compute (``need``) come back as empty tensors.  cc_forward, cc_forward_multi, flow_block and flow_ll are differentiable (their
 backward is the matching op -- cc_forward_multi's is cc_backward_multi_fx when a cotangent for its f_x output arrives, cc_backward_multi
 when none does; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` -- is differentiable in its x output through cc_backward,
-by the implicit-function theorem; cc_solve_block -- the same solve for every (row, dimension) in ONE launch, optionally warm-started,
+by the implicit-function theorem; cc_solve_multi -- ``integral.solve_sum`` -- likewise, in t, coef, h and the weights, through
+cc_backward_multi; cc_solve_block -- the same solve for every (row, dimension) in ONE launch, optionally warm-started,
 what the recorded ``invert(method="jacobi")`` sweeps call under no_grad -- has no autograd formula: a backward through it raises;
 flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
 flow_ll_block are not.  Registration loads no library and touches no GPU.
@@ -385,6 +388,61 @@ def _cc_solve_backward(ctx, g_x, _gfx, _gstatus):
 
 
 cc_solve.register_autograd(_cc_solve_backward, setup_context=_cc_solve_setup)
+
+
+def _check_cc_solve_multi(t, coef, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
+    B, _ = _check_net("cc_solve_multi", t, h, W, b, hidden_act, out_act, multi=True)
+    _check_tensor("cc_solve_multi", "coef", coef, t, (B, W[-1].shape[0]), _FLOATS)
+    _check_solve("cc_solve_multi", nb_steps, lo, hi, tol, max_iter)
+
+
+@torch.library.custom_op("umnn::cc_solve_multi", mutates_args=(), device_types="cuda")
+def cc_solve_multi(t: Tensor, coef: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int, nb_steps: int,
+                   lo: float, hi: float, tol: float, max_iter: int) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """x [B,1] in [lo, hi] with sum_k coef[:, k] int_0^x f_k(s; h) ds = t (``integral.solve_sum``: ONE launch of the in-kernel
+    Newton solve on the K-output quadrature), F_k and f_k [B, n_out] at that x and the int32 status word per row.  For the nets
+    whose images exceed the LDS (``integral._multi_kernels_ok``, decided here at run time) the same iteration on the ATen
+    quadrature of ``pure_mlp``."""
+    _check_cc_solve_multi(t, coef, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter)
+    spec = spec_from_tensors(W, b, hidden_act, out_act)
+    if _I._multi_kernels_ok(spec):
+        return _I.solve_sum(spec, None, t, coef, h, nb_steps, lo, hi, tol, max_iter)
+    f, params = pure_mlp(W, b, hidden_act, out_act)
+    return _I.solve_sum(None, lambda x, hh: f(params, x, hh), t, coef, h, nb_steps, lo, hi, tol, max_iter)
+
+
+@cc_solve_multi.register_fake
+def _(t, coef, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
+    _check_cc_solve_multi(t, coef, h, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter)
+    shape = (t.shape[0], W[-1].shape[0])
+    return t.new_empty(t.shape), t.new_empty(shape), t.new_empty(shape), t.new_empty(t.shape, dtype=torch.int32)
+
+
+def _cc_solve_multi_setup(ctx, inputs, output):
+    t, coef, h, W, b, hidden_act, out_act, nb_steps = inputs[:8]
+    ctx.mark_non_differentiable(output[1], output[2], output[3])
+    ctx.meta = (hidden_act, out_act, nb_steps, len(W))
+    ctx.save_for_backward(output[0], h, coef, output[1], output[2], *W, *b)
+
+
+def _cc_solve_multi_backward(ctx, g_x, _gF, _gfx, _gstatus):
+    """Implicit backward: with D = sum_k coef_k f_k(x), g_t = g_x / D, g_coef = -g_t F_k(x); (d_theta, d_h) of the K integrals up to
+    x for the cotangent -g_t coef, through cc_backward_multi."""
+    hidden_act, out_act, nb_steps, L = ctx.meta
+    x, h, coef, F_, fx, *Wb = ctx.saved_tensors
+    W, b = Wb[:L], Wb[L:]
+    nig = ctx.needs_input_grad
+    need = [False, False, bool(nig[2]), any(nig[3]) or any(nig[4])]
+    g_t = g_x / (coef * fx).sum(1, keepdim=True)
+    dh = dtheta = None
+    if need[2] or need[3]:
+        _, _, dh, dtheta = torch.ops.umnn.cc_backward_multi(None, x, h, -g_t * coef, W, b, hidden_act, out_act, nb_steps, need, False)
+    gW, gb = _param_grads(dtheta if need[3] else None, W, b, nig[3], nig[4])
+    return (g_t if nig[0] else None, -g_t * F_ if nig[1] else None, dh if need[2] else None, gW, gb,
+            None, None, None, None, None, None, None)
+
+
+cc_solve_multi.register_autograd(_cc_solve_multi_backward, setup_context=_cc_solve_multi_setup)
 
 
 def _check_cc_solve_block(t, h, x_init, W, b, hidden_act, out_act, nb_steps, lo, hi, tol, max_iter):
