@@ -257,6 +257,23 @@ int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, const float*
                               float* dx0, float* dx, float* dh, float* dtheta, void* workspace, long long workspace_bytes, void* stream);
 long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E);
 
+/* Whole curves from one quadrature (cc_multi.hip, cc_cumulate.hip; d = 1, fp32 storage, exact fp32 MFMA).
+ * umnn_cc_forward_multi_nodes: umnn_cc_forward_multi (same plan, grid and arithmetic; no inv_f, f_x, f_x0) that also stores the
+ * integrand at every node, f_nodes[b][j][k] = f_k(t_j; h_b), [B, nb_steps + 1, K], k minor; node j = 0 is x, j = nb_steps is x0.
+ * K = net->widths[n_linear] in [1, UMNN_MAX_OUTPUTS] here (a single output too); d must be 1; F [B,K] and f_nodes non-null.
+ * umnn_cc_cumulate: out[q][n - i][k] = (x_q - x0_q)/2 * sum_j Q[i][j] values[q][j][k] for n = nb_steps, i, j = 0..n: with Q the
+ * fp32 [n+1, n+1] table of umnn_amd.quadrature.cc_cumulative_matrix (row i: the integral of the quadrature's interpolant from x0
+ * to node i) and values the f_nodes above, out[q][i'][k] is the integral from x0 to the i'-th abscissa counted FROM THE LOWER
+ * LIMIT: out[q][0] = 0 exactly, out[q][n] the F of the forward up to rounding.  values, out [NI, n+1, K], k minor, 1 <= K <=
+ * UMNN_MAX_OUTPUTS; x0 may be NULL (zeros).  The kernel applies whatever table it is given (the same table with its columns
+ * reversed takes values stored in ascending order).  No atomics: two runs are bit-identical.  UMNN_EUNSUPPORTED for nb_steps >
+ * 127 (the table's LDS image is budgeted at 64 KiB); NI == 0 returns 0.  Both note their kernel through the launch notes. */
+int umnn_cc_forward_multi_nodes(const umnn_mlp* net, const float* x0, const float* x, const float* h,
+                                const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E,
+                                float* F, float* f_nodes, void* stream);
+int umnn_cc_cumulate(const float* Q, const float* values, const float* x0, const float* x, int nb_steps, long long NI, int K,
+                     float* out, void* stream);
+
 /* Inverse of a weighted sum of the K monotone outputs, for all B rows in ONE launch (cc_multi.hip; MonotonicNN's shape, d = 1): solves
  *     sum_k coef[b,k] * int_0^{x_b} f_k(t; h_b) dt = target[b]        for x_b in [lo, hi]
  * with coef >= 0 and a positive entry per row (not checked) -- the event time of K competing risks, a quantile of a mixture of K

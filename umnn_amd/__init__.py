@@ -23,7 +23,7 @@ if "HSA_ENABLE_IPC_MODE_LEGACY" not in _os.environ:
 from .flow import UMNNMAFFlow, UMNNMAF, EmbeddingNetwork, IntegrandNetwork, ListModule
 from .monotonic import MonotonicNN, IntegrandNN
 from .made import MADE, ConditionnalMADE, MaskedLinear, invalidate_caches, set_made_fast_path, get_made_fast_path, set_made_fused
-from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, IntegralWithDerivative, InverseNeuralIntegral, InverseIntegralSum, integrate, path_taken, backward_path_taken, set_backward_wide
+from .integral import NeuralIntegral, ParallelNeuralIntegral, IntegralWithJacobian, IntegralWithDerivative, InverseNeuralIntegral, InverseIntegralSum, IntegralCurve, integrate, path_taken, backward_path_taken, set_backward_wide
 from .inverse import FlowBlockInverse
 from .nets import compute_lipschitz_linear
 from .quadrature import compute_cc_weights
@@ -67,4 +67,4 @@ __all__ = ["UMNNMAFFlow", "UMNNMAF", "EmbeddingNetwork", "IntegrandNetwork", "Li
            "IntegralWithJacobian", "IntegralWithDerivative", "integrate", "compute_cc_weights", "path_taken", "GraphedLL", "GraphedSampler", "GraphedTrainStep",
            "set_precision", "invalidate_caches", "set_made_fast_path", "get_made_fast_path", "set_forward_precision", "get_forward_precision", "set_backward_precision", "get_backward_precision",
            "set_backward_wide", "compute_lipschitz_linear", "backward_path_taken", "set_made_fused",
-           "InverseNeuralIntegral", "InverseIntegralSum", "FlowBlockInverse", "SOLVE_EVALS_MASK", "SOLVE_CLAMPED", "SOLVE_CAPPED", "SOLVE_NONFINITE"]
+           "InverseNeuralIntegral", "InverseIntegralSum", "IntegralCurve", "FlowBlockInverse", "SOLVE_EVALS_MASK", "SOLVE_CLAMPED", "SOLVE_CAPPED", "SOLVE_NONFINITE"]

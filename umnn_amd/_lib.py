@@ -85,6 +85,9 @@ SIGNATURES = {
     "umnn_cc_backward_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),
     "umnn_cc_forward_multi": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                              _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp]),
+    "umnn_cc_forward_multi_nodes": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
+                                                   _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp]),
+    "umnn_cc_cumulate": (ctypes.c_int, [_fp, _fp, _fp, _fp, ctypes.c_int, _ll, ctypes.c_int, _fp, _fp]),
     "umnn_cc_backward_multi": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                               _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_multi_fx": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,

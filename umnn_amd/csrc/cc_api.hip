@@ -219,7 +219,7 @@ long long umnn_param_count(const umnn_mlp* net) {
     return n;
 }
 
-int umnn_prepare_mlp(const umnn_mlp* net, int E, MlpDev* out, int* tmax, int* ksu, int max_out) {
+int umnn_prepare_mlp(const umnn_mlp* net, int E, MlpDev* out, int* tmax, int* ksu, int max_out, int min_out) {
     if (!net) return umnn_fail(UMNN_EINVAL, "net is null");
     const int nl = net->n_linear;
     if (nl < 2 || nl > UMNN_MAX_LINEAR)
@@ -228,8 +228,9 @@ int umnn_prepare_mlp(const umnn_mlp* net, int E, MlpDev* out, int* tmax, int* ks
         return umnn_fail(UMNN_EINVAL, "widths[0] must equal 1 + E (integration variable + embedding)");
     if (max_out <= 1) {
         if (net->widths[nl] != 1) return umnn_fail(UMNN_EINVAL, "integrand output width must be 1");
-    } else if (net->widths[nl] < 2 || net->widths[nl] > max_out) {
-        return umnn_fail(UMNN_EINVAL, "multi-output integrand: output width must be between 2 and UMNN_MAX_OUTPUTS");
+    } else if (net->widths[nl] < min_out || net->widths[nl] > max_out) {
+        return umnn_fail(UMNN_EINVAL, min_out > 1 ? "multi-output integrand: output width must be between 2 and UMNN_MAX_OUTPUTS"
+                                                  : "curve integrand: output width must be between 1 and UMNN_MAX_OUTPUTS");
     }
     if (net->hidden_act != UMNN_ACT_LEAKY_RELU && net->hidden_act != UMNN_ACT_RELU)
         return umnn_fail(UMNN_EINVAL, "unknown hidden_act");

@@ -11,8 +11,9 @@ int umnn_check(hipError_t e, const char* what);           // 0 or records + retu
 // Validates `net`, fills the device-side descriptor (tile / K-step counts, LDS offsets) and reports
 // tmax = max tiles over hidden layers and ksu = the common K-step count if all hidden layers agree (else 0).
 // max_out: the output width the caller's kernels accept -- 1 (every single-output entry point: widths[n_linear] must be 1), or
-// an upper bound above 1 (the multi-output entry points of cc_multi.hip: 2 <= widths[n_linear] <= max_out).
-int umnn_prepare_mlp(const umnn_mlp* net, int E, MlpDev* out, int* tmax, int* ksu, int max_out = 1);
+// an upper bound above 1 (the multi-output entry points of cc_multi.hip: min_out <= widths[n_linear] <= max_out; min_out = 1: the
+// node-value entry, whose K-output kernel serves a single output too).
+int umnn_prepare_mlp(const umnn_mlp* net, int E, MlpDev* out, int* tmax, int* ksu, int max_out = 1, int min_out = 2);
 int umnn_check_io(const umnn_io* io);                     // 0, or UMNN_EINVAL for an unknown dtype code
 int umnn_num_cus();                                      // CU count of the CURRENT device (cached per device)
 constexpr size_t UMNN_LDS_LIMIT = 160 * 1024;            // bytes of LDS one workgroup may take (gfx950: 160 KiB per CU)

@@ -243,6 +243,187 @@ __global__ __launch_bounds__(UMNN_BLOCK) void cc_fwd_multi_kernel(const MultiArg
     }
 }
 
+// cc_fwd_multi_kernel that also stores every node's f_k(t_j; h) to f_nodes[NI][n + 1][K] (node j = 0 is x, j = n is x0; k minor,
+// masked k < K, tail rows masked): what cc_cumulate_kernel (cc_cumulate.hip) turns into the whole curve.  A sibling, and a copy of
+// that kernel's text to be changed together with it, for the reason the header gives: as one body inlined into both kernels the
+// forward's register counts moved (profiles/curve/README.md).  f_nodes is an argument of its own, so that MultiArgs -- the kernel
+// argument of every other kernel of this file -- stays as it is.  (umnn_cc_forward_multi_nodes passes no inv_f, f_x or f_x0; the two texts differ in the store alone.)
+template <int TMAX, int KSC, int P>
+__global__ __launch_bounds__(UMNN_BLOCK) void cc_fwd_multi_nodes_kernel(const MultiArgs a, float* __restrict__ f_nodes) {
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    const MlpDev& m = a.m;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wid = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int g = lane >> 4, p = lane & 15;
+    const int L = m.n_linear - 1;
+    const int H1 = m.width[1], HL = m.width[L], K = a.K;
+    const int E = a.E, d = a.d, n = a.n;
+    const float slope = m.hidden_act == UMNN_ACT_RELU ? 0.f : 0.01f;
+
+    stage_hidden_images(m, lds, tid, UMNN_BLOCK);
+    {   // the output tile: one output tile of KSC K-steps, lane layout of every other image
+        float* img = lds + a.out_off;
+        const float* __restrict__ WL = m.W[L];
+        const float* __restrict__ bL = m.b[L];
+        for (int idx = tid; idx < KSC * 64; idx += UMNN_BLOCK) {
+            const int ln = idx & 63, s = idx >> 6;
+            const int k = fout_of(0, ln & 15), fi = 4 * s + (ln >> 4);
+            float v = 0.f;
+            if (k < K) {
+                if (fi < HL) v = WL[k * HL + fi];
+                else if (fi == HL) v = bL[k];
+            }
+            img[idx] = v;
+        }
+    }
+    __syncthreads();
+
+    const unsigned grp = xcd_remap(blockIdx.x, gridDim.x) * UMNN_WAVES_PER_BLOCK + wid;
+    if (grp >= a.ngroups) return;
+
+    float xv[P], x0v[P], dxv[P];
+    bool ok[P];
+    long long qv[P];
+    IoView hb[P];
+#pragma unroll
+    for (int pt = 0; pt < P; ++pt) {
+        const long long q = ((long long)grp * P + pt) * 16 + p;
+        ok[pt] = q < a.NI;
+        const long long qq = ok[pt] ? q : a.NI - 1;
+        qv[pt] = qq;
+        xv[pt] = a.x[qq];
+        x0v[pt] = a.x0 ? a.x0[qq] : 0.f;
+        dxv[pt] = xv[pt] - x0v[pt];
+        const long long bi = qq / d;
+        hb[pt] = IoView{a.h, 0} + (bi * ((long long)E * d) + (qq - bi * d));
+    }
+
+    // ---- per-lane constants: first-layer x-column
+    float w1x[TMAX][4];
+    {
+        const float* __restrict__ W0 = m.W[0];
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = feat_of(t, r, g);
+                w1x[t][r] = f < H1 ? W0[f * (1 + E)] : 0.f;
+            }
+    }
+
+    // ---- hoisted first-layer term c = W1[:,1:] h + b1 (and the constant-one feature), on MFMA
+    f32x4 c[P][TMAX];
+    {
+        const float* __restrict__ W0 = m.W[0];
+        const float* __restrict__ b0 = m.b[0];
+#pragma unroll
+        for (int t = 0; t < TMAX; ++t) {
+            f32x4 init;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int f = feat_of(t, r, g);
+                init[r] = f < H1 ? b0[f] : (f == H1 ? 1.f : 0.f);
+            }
+#pragma unroll
+            for (int pt = 0; pt < P; ++pt) c[pt][t] = init;
+        }
+        for (int se = 0; se < (E + 3) / 4; ++se) {
+            const int e = 4 * se + g;
+            float hv[P];
+#pragma unroll
+            for (int pt = 0; pt < P; ++pt) hv[pt] = e < E ? hb[pt][(long long)e * d] : 0.f;
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t) {
+                const int fo = fout_of(t, p);
+                const float A = (fo < H1 && e < E) ? W0[fo * (1 + E) + 1 + e] : 0.f;
+#pragma unroll
+                for (int pt = 0; pt < P; ++pt) c[pt][t] = mfma16(A, hv[pt], c[pt][t]);
+            }
+        }
+    }
+
+    f32x4 Facc[P], fxv[P], fx0v[P];
+#pragma unroll
+    for (int pt = 0; pt < P; ++pt) Facc[pt] = fxv[pt] = fx0v[pt] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // ---- walk the quadrature nodes
+    const float* oimg = lds + a.out_off + lane;
+    for (int k = 0; k <= n; ++k) {
+        const float u = a.ccs[k] + 1.f;
+        const float wk = a.ccw[k];
+        f32x4 act[P][TMAX];
+#pragma unroll
+        for (int pt = 0; pt < P; ++pt) {
+            // t_k = x0 + (x-x0)*(s_k+1)/2 in the reference's rounding order; node 0 is x itself
+            const float tk = k == 0 ? xv[pt] : __fadd_rn(x0v[pt], __fmul_rn(dxv[pt], u) * 0.5f);
+#pragma unroll
+            for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) act[pt][t][r] = hidden_act_f(fmaf(w1x[t][r], tk, c[pt][t][r]), slope);
+        }
+        for (int l = 1; l < L; ++l) {
+            const float* img = lds + m.lds_off[l] + lane;
+            f32x4 acc[P][TMAX];
+#pragma unroll
+            for (int pt = 0; pt < P; ++pt)
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t) acc[pt][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int s = 0; s < KSC; ++s)
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t) {
+                    const float A = img[(t * KSC + s) * 64];
+#pragma unroll
+                    for (int pt = 0; pt < P; ++pt) acc[pt][t] = mfma16(A, act[pt][s >> 2][s & 3], acc[pt][t]);
+                }
+#pragma unroll
+            for (int pt = 0; pt < P; ++pt)
+#pragma unroll
+                for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) act[pt][t][r] = hidden_act_f(acc[pt][t][r], slope);
+        }
+        // the output tile: component r of lane (g, p) = s_k of output k = 4r + g
+        f32x4 o[P];
+#pragma unroll
+        for (int pt = 0; pt < P; ++pt) o[pt] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int s = 0; s < KSC; ++s) {
+            const float A = oimg[s * 64];
+#pragma unroll
+            for (int pt = 0; pt < P; ++pt) o[pt] = mfma16(A, act[pt][s >> 2][s & 3], o[pt]);
+        }
+#pragma unroll
+        for (int pt = 0; pt < P; ++pt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float f = out_act_f(o[pt][r], m.out_act);
+                Facc[pt][r] = fmaf(wk, maybe_inverse(f, a.inv_f), Facc[pt][r]);
+                if (k == 0) fxv[pt][r] = f;
+                if (k == n) fx0v[pt][r] = f;
+                {
+                    const int ko = 4 * r + g;
+                    if (ok[pt] && ko < K) f_nodes[(qv[pt] * (n + 1) + k) * K + ko] = f;
+                }
+            }
+    }
+
+    // ---- [NI][K], k minor: a lane stores the (up to four) outputs it owns
+#pragma unroll
+    for (int pt = 0; pt < P; ++pt) {
+        if (!ok[pt]) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int k = 4 * r + g;
+            if (k >= K) continue;
+            const long long o = qv[pt] * K + k;
+            a.F[o] = Facc[pt][r] * dxv[pt] * 0.5f;
+            if (a.fx) a.fx[o] = fxv[pt][r];
+            if (a.fx0) a.fx0[o] = fx0v[pt][r];
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------ Newton solve of a weighted sum
 // sum_k coef[b][k] int_0^{x_b} f_k(t; h_b) dt = target[b] for x_b in [lo, hi] (umnn_cc_solve_multi; d = 1): cc_fwd_multi_kernel's
 // node loop with x0 = 0, dxv = x and P = 1 -- one 16-row tile per wave -- inside the iteration of umnn_cc_solve (the INV = 2 block
@@ -864,6 +1045,14 @@ static const MultiFwdVariant kMultiFwd[] = {
     MULTI_FWD(7, 26, 1), MULTI_FWD(7, 26, 2), MULTI_FWD(8, 32, 1), MULTI_FWD(8, 32, 2),
 };
 
+typedef void (*multi_nodes_kernel_t)(const MultiArgs, float*);
+struct MultiNodesVariant { int T, KS, P; multi_nodes_kernel_t fn; const char* name; };
+#define MULTI_NODES(T, KS, P) { T, KS, P, cc_fwd_multi_nodes_kernel<T, KS, P>, "cc_fwd_multi_nodes<T=" #T ",KS=" #KS ",P=" #P ">" }
+static const MultiNodesVariant kMultiNodes[] = {
+    MULTI_NODES(2, 8, 1), MULTI_NODES(2, 8, 2), MULTI_NODES(4, 13, 1), MULTI_NODES(4, 13, 2), MULTI_NODES(4, 16, 1), MULTI_NODES(4, 16, 2),
+    MULTI_NODES(7, 26, 1), MULTI_NODES(7, 26, 2), MULTI_NODES(8, 32, 1), MULTI_NODES(8, 32, 2),
+};
+
 // the backward passes of a family: the EDGE pass holds `edge_nacc` dW layers, every further pass `rest_nacc`
 // fn / name [1]: the FX build of the pass (a g_fx cotangent was given), [0]: the kernel without it
 struct MultiBwdVariant { int T, KS, nacc, edge, outw; multi_kernel_t fn[2]; const char* name[2]; };
@@ -922,12 +1111,13 @@ static size_t multi_bwd_lds(const MultiPlan& pl, int nacc, int waves) {
 }
 static const char* const kMultiBwdLdsError = "multi-output backward: weight images exceed 160 KiB of LDS";
 
-// Validates the net, pads it to its family and fills what both directions share.  K = widths[n_linear] in [2, 16].
-static int multi_plan(const umnn_mlp* net, int E, MultiPlan* pl) {
+// Validates the net, pads it to its family and fills what both directions share.  K = widths[n_linear] in [min_out, 16]
+// (min_out = 1: the node-value entry; the output tile is padded to 16 rows whatever K is).
+static int multi_plan(const umnn_mlp* net, int E, MultiPlan* pl, int min_out = 2) {
     MultiArgs& a = pl->a;
     memset(&a, 0, sizeof(a));
     int tmax = 0, ksu = 0;
-    if (int rc = umnn_prepare_mlp(net, E, &a.m, &tmax, &ksu, UMNN_MAX_OUTPUTS)) return rc;
+    if (int rc = umnn_prepare_mlp(net, E, &a.m, &tmax, &ksu, UMNN_MAX_OUTPUTS, min_out)) return rc;
     MlpDev& m = a.m;
     const int L = m.n_linear - 1;
     a.K = m.width[L + 1];
@@ -960,12 +1150,12 @@ static int multi_plan(const umnn_mlp* net, int E, MultiPlan* pl) {
     return 0;
 }
 
-extern "C" int umnn_cc_forward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h,
-                                     const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
-                                     float* F, float* f_x, float* f_x0, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+// The forward launch, with (f_nodes non-null: the NODES build, K >= 1, d = 1) or without the node values.
+static int multi_forward(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* cc_w, const float* cc_s,
+                         int nb_steps, long long B, int d, int E, int inv_f, float* F, float* f_x, float* f_x0, float* f_nodes,
+                         hipStream_t stream) {
     MultiPlan pl;
-    if (int rc = multi_plan(net, E, &pl)) return rc;
+    if (int rc = multi_plan(net, E, &pl, f_nodes ? 1 : 2)) return rc;
     if (nb_steps < 1) return umnn_fail(UMNN_EINVAL, "forward_multi: nb_steps must be >= 1");
     if (B < 0 || d < 1) return umnn_fail(UMNN_EINVAL, "forward_multi: B must be >= 0 and d >= 1");
     if (B == 0) return 0;
@@ -979,17 +1169,45 @@ extern "C" int umnn_cc_forward_multi(const umnn_mlp* net, const float* x0, const
     const long long groups = (tiles + P - 1) / P;
     if (groups > 0x7fffffffLL) return umnn_fail(UMNN_EUNSUPPORTED, "forward_multi: batch too large");
     a.ngroups = (unsigned)groups;
-    const MultiFwdVariant* v = nullptr;
-    for (const MultiFwdVariant& c : kMultiFwd)
-        if (c.T == pl.T && c.KS == pl.KS && c.P == P) v = &c;
-    if (!v) return umnn_fail(UMNN_EUNSUPPORTED, "forward_multi: no kernel variant");
-    if (int rc = umnn_allow_lds((const void*)v->fn, pl.fwd_lds)) return rc;
     const unsigned blocks = (a.ngroups + UMNN_WAVES_PER_BLOCK - 1) / UMNN_WAVES_PER_BLOCK;
-    umnn_prof_begin(stream);
-    hipLaunchKernelGGL(v->fn, dim3(blocks), dim3(UMNN_BLOCK), pl.fwd_lds, stream, a);
+    const char* name = nullptr;
+    if (f_nodes) {
+        const MultiNodesVariant* v = nullptr;
+        for (const MultiNodesVariant& c : kMultiNodes)
+            if (c.T == pl.T && c.KS == pl.KS && c.P == P) v = &c;
+        if (!v) return umnn_fail(UMNN_EUNSUPPORTED, "forward_multi_nodes: no kernel variant");
+        if (int rc = umnn_allow_lds((const void*)v->fn, pl.fwd_lds)) return rc;
+        umnn_prof_begin(stream);
+        hipLaunchKernelGGL(v->fn, dim3(blocks), dim3(UMNN_BLOCK), pl.fwd_lds, stream, a, f_nodes);
+        name = v->name;
+    } else {
+        const MultiFwdVariant* v = nullptr;
+        for (const MultiFwdVariant& c : kMultiFwd)
+            if (c.T == pl.T && c.KS == pl.KS && c.P == P) v = &c;
+        if (!v) return umnn_fail(UMNN_EUNSUPPORTED, "forward_multi: no kernel variant");
+        if (int rc = umnn_allow_lds((const void*)v->fn, pl.fwd_lds)) return rc;
+        umnn_prof_begin(stream);
+        hipLaunchKernelGGL(v->fn, dim3(blocks), dim3(UMNN_BLOCK), pl.fwd_lds, stream, a);
+        name = v->name;
+    }
     umnn_prof_end(stream, umnn_cc_forward_flops_per_integral(net, nb_steps) * (double)a.NI, UMNN_PROF_FORWARD);
-    umnn_note_launch(v->name);
+    umnn_note_launch(name);
     return umnn_check(hipGetLastError(), "cc_fwd_multi launch");
+}
+
+extern "C" int umnn_cc_forward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h,
+                                     const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E, int inv_f,
+                                     float* F, float* f_x, float* f_x0, void* stream) {
+    return multi_forward(net, x0, x, h, cc_w, cc_s, nb_steps, B, d, E, inv_f, F, f_x, f_x0, nullptr, (hipStream_t)stream);
+}
+
+extern "C" int umnn_cc_forward_multi_nodes(const umnn_mlp* net, const float* x0, const float* x, const float* h,
+                                           const float* cc_w, const float* cc_s, int nb_steps, long long B, int d, int E,
+                                           float* F, float* f_nodes, void* stream) {
+    if (d != 1) return umnn_fail(UMNN_EINVAL, "forward_multi_nodes: d must be 1");
+    if (B == 0) { MultiPlan pl; return multi_plan(net, E, &pl, 1); }           // (the checks of the net; nothing to launch)
+    if (!f_nodes) return umnn_fail(UMNN_EINVAL, "forward_multi_nodes: f_nodes must be non-null");
+    return multi_forward(net, x0, x, h, cc_w, cc_s, nb_steps, B, d, E, 0, F, nullptr, nullptr, f_nodes, (hipStream_t)stream);
 }
 
 typedef void (*solve_multi_kernel_t)(const SolveMultiArgs);

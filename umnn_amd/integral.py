@@ -33,7 +33,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from ._common import _graph_mode, _ptr, _stream, traced_native_call  # noqa: F401  (the names are part of this module)
 from .nets import graph_spec, mlp_spec, n_out_of, require_single
-from .quadrature import compute_cc_weights, device_tables
+from .quadrature import compute_cc_weights, device_cumulative_matrix, device_tables
 
 _state = threading.local()           # per-thread: last path taken, force_generic nesting
 _warned = set()                       # fallbacks announced once per process (see _warn_once)
@@ -291,6 +291,62 @@ def hip_forward_multi(spec, x0, x, h, nb_steps, inv_f=False):
     """Multi-output forward (umnn_cc_forward_multi): x [B,1], h [B,E] -> (F, f_x, f_x0), each [B, n_out] in x's dtype.  Exact fp32
     kernels and fp32 storage whatever ``set_precision`` says; bf16 / fp16 callers are converted at the boundary."""
     return hip_forward(spec, x0, x, h, nb_steps, inv_f, multi=True)
+
+
+def hip_forward_multi_nodes(spec, x0, x, h, nb_steps):
+    """The forward that keeps its nodes (umnn_cc_forward_multi_nodes): x [B,1], h [B,E], n_out = 1..16 -> (F [B, n_out],
+    f_nodes [B, nb_steps + 1, n_out]) in x's dtype, f_nodes[:, j] = f(t_j; h) in NODE order (node 0 is x, node n is x0).  Exact fp32
+    like every multi-output entry."""
+    B, d, E, xd, hd, io = _quad_plan(spec, x, h, True)
+    out_dtype, K = x.dtype, n_out_of(spec)
+    x, h, x0 = _as(x, xd), _as(h, hd), _as(x0, xd)
+    w, s = device_tables(nb_steps, x.device)
+    F, f_nodes = x.new_empty((B, K)), x.new_empty((B, int(nb_steps) + 1, K))
+    desc, keep = _desc(spec)
+    with torch.cuda.device(x.device):
+        rc = _lib.lib().umnn_cc_forward_multi_nodes(ctypes.byref(desc), _ptr(x0), _ptr(x), _ptr(h), _ptr(w), _ptr(s), int(nb_steps),
+                                                    B, d, E, _ptr(F), _ptr(f_nodes), _stream(x.device))
+    return _quad_done(rc, "umnn_cc_forward_multi_nodes", (F, f_nodes), xd, out_dtype)
+
+
+def hip_cumulate(values, x0, x, nb_steps, ascending=False):
+    """umnn_cc_cumulate: values [B, nb_steps + 1, K] at the nodes of [x0, x] (x, x0 [B,1]; x0 None: zeros), K <= 16 -> the integral from
+    x0 up to every node, [B, nb_steps + 1, K] in values' dtype, ASCENDING from the lower limit (index 0, exactly 0) to x.  ``values``
+    in node order (what ``hip_forward_multi_nodes`` leaves), or -- ``ascending`` -- from the lower limit up, like the result.  It has
+    no integrand, hence no ``_quad_plan``; it ends like the other wrappers, in ``_quad_done``."""
+    n = int(nb_steps)
+    _check_cumulate(values, x0, x, n)
+    B, K = values.shape[0], values.shape[2]
+    out_dtype = values.dtype
+    values, x, x0 = _as(values, torch.float32), _as(x, torch.float32), _as(x0, torch.float32)
+    Q = device_cumulative_matrix(n, values.device, ascending)
+    out = torch.empty_like(values)
+    with torch.cuda.device(values.device):
+        rc = _lib.lib().umnn_cc_cumulate(_ptr(Q), _ptr(values), _ptr(x0), _ptr(x), n, B, K, _ptr(out), _stream(values.device))
+    return _quad_done(rc, "umnn_cc_cumulate", (out,), torch.float32, out_dtype)[0]
+
+
+_curve_ok = {}
+
+
+def _curve_kernels_ok(spec, nb_steps):
+    """False (after a one-time notice) when the library answers UMNN_EUNSUPPORTED for a curve of this net and nb_steps -- weight images
+    beyond the LDS, or a cumulative table beyond its LDS budget (nb_steps > 127): asked with zero rows, which launches nothing."""
+    key = (tuple((m.in_features, m.out_features) for m in spec.linears), int(nb_steps))
+
+    def ask(desc):
+        lib = _lib.lib()
+        for name, rc in (("umnn_cc_forward_multi_nodes", lib.umnn_cc_forward_multi_nodes(desc, None, None, None, None, None, key[1], 0, 1,
+                                                                                        key[0][0][0] - 1, None, None, None)),
+                         ("umnn_cc_cumulate", lib.umnn_cc_cumulate(None, None, None, None, key[1], 0, key[0][-1][1], None, None))):
+            if rc == _lib.EUNSUPPORTED:
+                return rc
+            _lib.check(rc, name)
+        return 0
+
+    return _kernel_probe(
+        _curve_ok, key, spec, ask, "curve-aten", lambda widths: f"umnn_amd: no HIP curve kernels for integrand widths {widths} at "
+        f"nb_steps = {key[1]} ({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): the curve runs on the generic ATen path.") >= 0
 
 
 def _add_h0(dh, h0_cot, d):
@@ -744,6 +800,125 @@ def aten_forward(integrand, x0, x, h, nb_steps, inv_f=False):
         total = total + (f * w[a:b].view(-1, 1, 1)).sum(0)
     _state.path = "aten"
     return total * (span if total.shape[1] == d else span.expand(B, total.shape[1])) / 2
+
+
+def _check_cumulate(values, x0, x, n):
+    B = values.shape[0]
+    if values.dim() != 3 or values.shape[1] != n + 1 or x.shape != (B, 1) or (x0 is not None and x0.shape != (B, 1)):
+        raise RuntimeError(f"umnn_amd: cumulate takes values [B, nb_steps + 1, K] and limits [B, 1]; got {tuple(values.shape)} and "
+                           f"{tuple(x.shape)} at nb_steps = {n}")
+
+
+def _curve_abscissae(x0, x, nb_steps):
+    """[B, nb_steps + 1]: the quadrature nodes of [x0, x] ASCENDING from x0 to x, in the kernels' rounding order
+    x0 + ((x - x0) (s_j + 1)) / 2, the last one x itself (node 0 of the kernels)."""
+    _, s = device_tables(nb_steps, x.device)
+    u = (s.to(x.dtype) + 1).flip(0)
+    t = x0 + (x - x0) * u.view(1, -1) / 2
+    return torch.cat((t[:, :-1], x), 1)
+
+
+def aten_cumulate(values, x0, x, nb_steps, ascending=True):
+    """``hip_cumulate`` as one einsum with the cumulative matrix in values' dtype (float64 stays float64): any device, differentiable
+    by plain autograd.  -> [B, nb_steps + 1, K], ascending."""
+    _check_cumulate(values, x0, x, int(nb_steps))
+    Q = device_cumulative_matrix(nb_steps, values.device, ascending, values.dtype).flip(0)
+    span = x if x0 is None else x - x0
+    return torch.einsum("ij,bjk->bik", Q, values) * (span.to(values.dtype) / 2).unsqueeze(2)
+
+
+def aten_curve(integrand, x0, x, h, nb_steps):
+    """The curve on ATen -> (t [B, n+1], C [B, n+1, K], f [B, n+1, K]), all ascending from x0 to x: the integrand at the nodes as
+    ``aten_forward`` evaluates them (in node chunks), kept, and the cumulative matrix applied with one einsum.  Any device and dtype;
+    differentiable through x0, x, h and every parameter by plain autograd."""
+    B, n = x.shape[0], int(nb_steps)
+    t = _curve_abscissae(x0, x, n)
+    parts = []
+    for a, b in _node_chunks(n, B, h.shape[1] + 1):
+        hh = h.unsqueeze(1).expand(B, b - a, h.shape[1]).reshape(B * (b - a), -1)
+        parts.append(integrand(t[:, a:b].reshape(B * (b - a), 1), hh).view(B, b - a, -1))
+    f = torch.cat(parts, 1)
+    C = aten_cumulate(f, x0, x, n)
+    _state.path = "aten"
+    return t, C, f
+
+
+def cumulate(values, x0, x, nb_steps):
+    """Cumulative quadrature of values given at the ascending nodes of [x0, x] (``curve``'s t): [B, n+1, K] -> the integral from x0
+    to every node, [B, n+1, K], index 0 exactly 0.  One ``umnn_cc_cumulate`` launch for GPU tensors of K <= 16 outputs when nothing
+    asks for a gradient (recorded: ``umnn::cc_cumulate``); ``aten_cumulate`` otherwise -- host tensors, float64, K > 16, nb_steps
+    beyond the kernel's table budget, and whenever an input requires grad."""
+    wants_graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (values, x0, x))
+    hip = (values.is_cuda and values.dtype in (torch.float32, torch.bfloat16, torch.float16) and values.dim() == 3
+           and 1 <= values.shape[2] <= _lib.MAX_OUTPUTS and not wants_graph)
+    if hip and _graph_mode():
+        return torch.ops.umnn.cc_cumulate(values, x0, x, int(nb_steps), True)
+    if hip and not getattr(_state, "force_generic", False) and _cumulate_kernel_ok(values.shape[2], nb_steps):
+        return hip_cumulate(values, x0, x, nb_steps, ascending=True)
+    out = aten_cumulate(values, x0, x, nb_steps)
+    _state.path = "aten"
+    return out
+
+
+def _cumulate_kernel_ok(K, nb_steps):
+    rc = _lib.lib().umnn_cc_cumulate(None, None, None, None, int(nb_steps), 0, int(K), None, None)      # (zero rows: launches nothing)
+    if rc == _lib.EUNSUPPORTED:
+        _warn_once(("cumulate-aten", int(nb_steps)), f"umnn_amd: no HIP cumulate kernel at nb_steps = {int(nb_steps)} "
+                   f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): one einsum on the GPU instead.")
+        return False
+    _lib.check(rc, "umnn_cc_cumulate")
+    return True
+
+
+def curve(spec, integrand, x0, x, h, nb_steps):
+    """The whole monotone curve from ONE quadrature's worth of integrand evaluations -> (t [B, n+1], C [B, n+1, K], f [B, n+1, K]),
+    all ascending: t the n + 1 Clenshaw-Curtis nodes of [x0, x] (t[:, 0] = x0, t[:, n] = x), C[:, i, k] = int_{x0}^{t_i} f_k(s; h) ds
+    (C[:, 0] = 0 exactly, C[:, n] the integral ``aten_forward`` / the forward kernels return, up to rounding) and f the integrand there.
+    ``spec`` (``_hip_spec``: an MLP of 1..16 outputs on GPU tensors): two launches, the forward that keeps its node values and
+    ``umnn_cc_cumulate`` (recorded: ``umnn::cc_forward_multi_nodes`` and ``umnn::cc_cumulate``) -- unless the library answers
+    UMNN_EUNSUPPORTED (announced once), which runs ``aten_curve`` like ``spec`` None does: CPU tensors, float64, n_out > 16,
+    integrands ``mlp_spec`` does not recognise.  The kernels record no autograd graph: callers that need gradients pass ``spec``
+    None (``IntegralCurve`` decides)."""
+    x0z = torch.zeros_like(x) if x0 is None else x0
+    if spec is None or not (_graph_mode() or _curve_kernels_ok(spec, nb_steps)):
+        return aten_curve(integrand, x0z, x, h, nb_steps)
+    with torch.no_grad():
+        out_dtype = x.dtype       # (bf16 / fp16 callers: fp32 from end to end, theirs outside -- the node values are rounded once)
+        x0, x0z, x, h = (None if x0 is None else x0.float()), x0z.float(), x.float(), h.float()
+        if _graph_mode():
+            _, f_nodes = torch.ops.umnn.cc_forward_multi_nodes(x0, x, h, *spec_args(spec), int(nb_steps))
+            C = torch.ops.umnn.cc_cumulate(f_nodes, x0, x, int(nb_steps), False)
+        else:
+            _, f_nodes = hip_forward_multi_nodes(spec, x0, x, h, nb_steps)
+            C = hip_cumulate(f_nodes, x0, x, nb_steps)
+        return tuple(t.to(out_dtype) for t in (_curve_abscissae(x0z, x, nb_steps), C, f_nodes.flip(1)))
+
+
+class IntegralCurve:
+    """(t, C, f) = the curve of int_{x0}^{t} f(s; h) ds at the n + 1 quadrature nodes of [x0, x] (``curve``):
+
+        IntegralCurve.apply(x0, x, integrand, flat_params, h, nb_steps=20) -> (t [B, n+1], C [B, n+1, K], f [B, n+1, K])
+
+    x [B,1]; x0 [B,1] or None (zeros); the calling convention of the quadrature operators (``flat_params`` is accepted for parity
+    and not read).  The HIP kernels are the evaluation path: they run when grad mode is off or nothing -- x0, x, h, a parameter of the
+    integrand -- requires grad.  Otherwise the curve runs on ``aten_curve`` under plain autograd on the tensors' device, announced
+    once: a backward kernel with per-node cotangents does not exist yet."""
+
+    @staticmethod
+    def apply(x0, x, integrand, flat_params, h, nb_steps=20):
+        if x.dim() != 2 or x.shape[1] != 1:
+            raise RuntimeError(f"umnn_amd: a curve is integrated over x of shape [B, 1]; got {tuple(x.shape)}")
+        wants_graph = torch.is_grad_enabled() and (
+            any(t is not None and t.requires_grad for t in (x0, x, h))
+            or (isinstance(integrand, torch.nn.Module) and any(p.requires_grad for p in integrand.parameters())))
+        spec = _hip_spec(integrand, x, multi=True, who="IntegralCurve")
+        if spec is not None and wants_graph:
+            if not _graph_mode():
+                _warn_once("curve-grad", "umnn_amd: a curve whose inputs require grad runs on the generic ATen path under autograd "
+                                         "(the HIP curve kernels are the evaluation path; use torch.no_grad() for them).")
+            spec = None
+        with torch.set_grad_enabled(wants_graph):
+            return curve(spec, integrand, x0, x, h, nb_steps)
 
 
 def _pure(integrand):

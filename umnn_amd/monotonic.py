@@ -14,12 +14,16 @@ integrals are ONE launch of the multi-output kernels (csrc/cc_multi.hip: exact f
 quantile functions, inverse-CDF sampling, calibration maps -- by the in-kernel Newton solve, differentiable in y, h and every parameter;
 ``output=k`` picks the function to invert when ``n_out > 1``.  ``inverse_sum(y, h, weights)`` inverts a non-negative combination
 sum_k w_k y_k of the K curves -- the event time of competing risks, a quantile of a mixture of CDFs -- in one solve launch.
+
+``forward_curve(x, h)`` returns the whole curve t -> forward(t, h) at the nb_steps + 1 quadrature nodes of [0, x] for the work of ONE
+``forward`` (the kernel keeps the node values it used to sum away; csrc/cc_cumulate.hip integrates them up to every node), and
+``cumulative_incidence(x, h)`` the nested integral CIF_k(t) = int_0^t y_k'(s) exp(-sum_j y_j(s)) ds from the same nodes.
 """
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
-from .integral import IntegralWithDerivative, InverseIntegralSum, InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
+from .integral import IntegralCurve, IntegralWithDerivative, InverseIntegralSum, cumulate, InverseNeuralIntegral, ParallelNeuralIntegral, _flatten
 from .nets import IntegrandNN, MlpSpec, TensorLinear, _spec_from_sequential  # noqa: F401  (IntegrandNN is re-exported)
 
 
@@ -153,3 +157,28 @@ class MonotonicNN(nn.Module):
                                                x_range, tol, max_iter, return_info)
         return InverseIntegralSum.apply(t, coef, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
                                         x_range, tol, max_iter, return_info)
+
+    def forward_curve(self, x, h, with_derivative=False):
+        """(t [B, n+1], y [B, n+1, n_out]) with n = nb_steps: ``forward(t, h)`` on the whole grid t[b] of the n + 1 quadrature nodes
+        of [0, x_b], ascending -- t[:, 0] = 0, t[:, n] = x, y[:, n] = ``forward(x, h)`` up to rounding --, for the integrand
+        evaluations of ONE ``forward``: a survival curve on a time grid, a CDF to plot or calibrate.  y[:, i, k] = exp(s_k(h)) *
+        int_0^{t_i} f_k + o_k(h).  ``with_derivative=True`` -> (t, y, dy/dt [B, n+1, n_out]), dy_k/dt = exp(s_k(h)) f_k(t; h).  Rows
+        that share x share their abscissae: a common grid for a batch is x = t_max for every row (descending t for x < 0).  The
+        curve points are as accurate as separate nb_steps-node quadratures to each t_i; values between the nodes are not provided.
+        On GPU tensors under ``torch.no_grad()`` (or when nothing requires grad) this is two launches (``IntegralCurve``); when a
+        gradient can be asked for it runs on ATen under plain autograd, differentiable in x, h and every parameter."""
+        offset, log_scaling = self._offset_log_scaling(h)
+        scaling = torch.exp(log_scaling).unsqueeze(1)
+        t, C, f = IntegralCurve.apply(None, x, self.integrand, None, h, self.nb_steps)
+        y = scaling * C + offset.unsqueeze(1)
+        return (t, y, scaling * f) if with_derivative else (t, y)
+
+    def cumulative_incidence(self, x, h, curve=False):
+        """The cumulative incidence of each of the ``n_out`` competing risks whose cumulative hazards are the outputs,
+        CIF_k(x) = int_0^x hz_k(s) exp(-sum_j H_j(s)) ds with H = ``forward_curve``'s y and hz = its dy/dt, -> [B, n_out]; ``curve=True``
+        -> (t [B, n+1], CIF [B, n+1, n_out]) on ``forward_curve``'s grid, whose last row is that end point.  The inner integrals at
+        the nodes of the outer one are the curve itself, so the nested integral costs one more cumulative-quadrature launch on
+        top of ``forward_curve`` (three launches on GPU tensors) instead of a quadrature per node.  Gradients as in ``forward_curve``."""
+        t, H, hz = self.forward_curve(x, h, with_derivative=True)
+        cif = cumulate(hz * torch.exp(-H.sum(2, keepdim=True)), None, x, self.nb_steps)
+        return (t, cif) if curve else cif[:, -1]

@@ -4,6 +4,10 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
     umnn::cc_forward(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)
     umnn::cc_backward(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_forward_multi(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps, inv_f) -> (F, f_x)        x [B,1]; F, f_x [B, n_out]
+    umnn::cc_forward_multi_nodes(x0?, x, h, W[], b[], hidden_act, out_act, nb_steps) -> (F, f_nodes)    x [B,1]; n_out = 1..16;
+        F [B, n_out], f_nodes [B, nb_steps + 1, n_out]: the integrand at every node, node 0 = x
+    umnn::cc_cumulate(values, x0?, x, nb_steps, ascending=False) -> out       values, out [B, nb_steps + 1, K]; x [B,1]: the integral
+        from x0 up to every node, ascending from the lower limit; ``ascending``: values are stored that way too (else in node order)
     umnn::cc_backward_multi(x0?, x, h, g, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_backward_multi_fx(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
@@ -25,7 +29,8 @@ backward is the matching op -- cc_forward_multi's is cc_backward_multi_fx when a
 when none does; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` -- is differentiable in its x output through cc_backward,
 by the implicit-function theorem; cc_solve_multi -- ``integral.solve_sum`` -- likewise, in t, coef, h and the weights, through
 cc_backward_multi; cc_solve_block -- the same solve for every (row, dimension) in ONE launch, optionally warm-started,
-what the recorded ``invert(method="jacobi")`` sweeps call under no_grad -- has no autograd formula: a backward through it raises;
+what the recorded ``invert(method="jacobi")`` sweeps call under no_grad -- has no autograd formula: a backward through it raises, as
+it does through cc_forward_multi_nodes and cc_cumulate, the evaluation path of the curves (``integral.IntegralCurve`` runs ATen under autograd);
 flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
 flow_ll_block are not.  Registration loads no library and touches no GPU.
 
@@ -62,9 +67,9 @@ def _check_tensor(op, name, t, x, shape, dtypes):
         _req(op, t.shape[i] == n, f"{name} has shape {tuple(t.shape)}; expected {tuple(shape)}")
 
 
-def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS, multi=False):
+def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_FLOATS, multi=False, min_out=2):
     """x [B,d] and h [B,E*d] on one CUDA device, W[] / b[] an integrand MLP the kernels take (the rules of
-    nets._spec_from_sequential) on that device.  ``multi``: the multi-output ops -- a last layer of 2..16 outputs and x [B,1];
+    nets._spec_from_sequential) on that device.  ``multi``: the multi-output ops -- a last layer of ``min_out``..16 outputs and x [B,1];
     every other op takes exactly one output.  -> (B, d)."""
     _req(op, x.device.type == "cuda", f"x is on {x.device}; the HIP kernels need CUDA tensors")
     _req(op, x.dim() == 2, f"x has shape {tuple(x.shape)}; expected [B, d]")
@@ -84,8 +89,8 @@ def _check_net(op, x, h, W, b, hidden_act, out_act, x_dtypes=_FLOATS, h_dtypes=_
         if l + 1 < len(W):
             _req(op, w.shape[0] <= 127, f"hidden layer {l} has {w.shape[0]} units; the kernels take at most 127")
     if multi:
-        _req(op, 2 <= W[-1].shape[0] <= _lib.MAX_OUTPUTS,
-             f"the integrand's last layer has n_out = {W[-1].shape[0]} outputs; expected 2 to {_lib.MAX_OUTPUTS}")
+        _req(op, min_out <= W[-1].shape[0] <= _lib.MAX_OUTPUTS,
+             f"the integrand's last layer has n_out = {W[-1].shape[0]} outputs; expected {min_out} to {_lib.MAX_OUTPUTS}")
         _req(op, x.shape[1] == 1, f"x has shape {tuple(x.shape)}; a multi-output integrand is integrated over x [B, 1]")
     else:
         _req(op, W[-1].shape[0] == 1, f"the integrand's last layer has {W[-1].shape[0]} outputs; expected 1 (n_out = 1)")
@@ -217,6 +222,68 @@ def _(x0, x, h, W, b, hidden_act, out_act, nb_steps, inv_f):
     _check_cc("cc_forward_multi", x0, x, h, W, b, hidden_act, out_act, multi=True)
     shape = (x.shape[0], W[-1].shape[0])
     return x.new_empty(shape), x.new_empty(shape)
+
+
+# ---- curves: the forward that keeps its node values, and the cumulative quadrature of values at the nodes (no autograd formula)
+def _check_nodes(x0, x, h, W, b, hidden_act, out_act, nb_steps):
+    op = "cc_forward_multi_nodes"
+    B, _ = _check_net(op, x, h, W, b, hidden_act, out_act, multi=True, min_out=1)
+    if x0 is not None:
+        _check_tensor(op, "x0", x0, x, (B, 1), _FLOATS)
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+
+
+@torch.library.custom_op("umnn::cc_forward_multi_nodes", mutates_args=(), device_types="cuda")
+def cc_forward_multi_nodes(x0: Optional[Tensor], x: Tensor, h: Tensor, W: List[Tensor], b: List[Tensor], hidden_act: int, out_act: int,
+                           nb_steps: int) -> tuple[Tensor, Tensor]:
+    """``integral.hip_forward_multi_nodes`` for an integrand given as tensors -> (F [B, n_out], f_nodes [B, nb_steps + 1, n_out], node
+    order); for what the library turns away (``integral._curve_kernels_ok``, decided here at run time) ``integral.aten_curve`` on
+    ``pure_mlp``."""
+    _check_nodes(x0, x, h, W, b, hidden_act, out_act, nb_steps)
+    spec = spec_from_tensors(W, b, hidden_act, out_act)
+    if _I._curve_kernels_ok(spec, nb_steps):
+        return _I.hip_forward_multi_nodes(spec, x0, x, h, nb_steps)
+    f, params = pure_mlp(W, b, hidden_act, out_act)
+    with torch.no_grad():
+        xd, hd = x.detach(), h.detach()
+        _, C, fa = _I.aten_curve(lambda t, hh: f(params, t, hh), torch.zeros_like(xd) if x0 is None else x0.detach(), xd, hd, nb_steps)
+        return C[:, -1].contiguous(), fa.flip(1)
+
+
+@cc_forward_multi_nodes.register_fake
+def _(x0, x, h, W, b, hidden_act, out_act, nb_steps):
+    _check_nodes(x0, x, h, W, b, hidden_act, out_act, nb_steps)
+    K = W[-1].shape[0]
+    return x.new_empty((x.shape[0], K)), x.new_empty((x.shape[0], nb_steps + 1, K))
+
+
+def _check_cumulate(values, x0, x, nb_steps):
+    op = "cc_cumulate"
+    _req(op, values.device.type == "cuda", f"values is on {values.device}; the HIP kernels need CUDA tensors")
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+    _req(op, values.dim() == 3, f"values has shape {tuple(values.shape)}; expected [B, nb_steps + 1, K]")
+    _check_tensor(op, "values", values, values, (values.shape[0], nb_steps + 1, values.shape[2]), _FLOATS)
+    _req(op, 1 <= values.shape[2] <= _lib.MAX_OUTPUTS, f"values has K = {values.shape[2]} outputs; expected 1 to {_lib.MAX_OUTPUTS}")
+    _check_tensor(op, "x", x, values, (values.shape[0], 1), _FLOATS)
+    if x0 is not None:
+        _check_tensor(op, "x0", x0, values, (values.shape[0], 1), _FLOATS)
+
+
+@torch.library.custom_op("umnn::cc_cumulate", mutates_args=(), device_types="cuda")
+def cc_cumulate(values: Tensor, x0: Optional[Tensor], x: Tensor, nb_steps: int, ascending: bool = False) -> Tensor:
+    """``integral.hip_cumulate`` -> [B, nb_steps + 1, K] ascending; beyond the kernel's table budget (decided here at run time) the
+    einsum of ``integral.aten_cumulate``."""
+    _check_cumulate(values, x0, x, nb_steps)
+    if _I._cumulate_kernel_ok(values.shape[2], nb_steps):
+        return _I.hip_cumulate(values, x0, x, nb_steps, ascending)
+    with torch.no_grad():
+        return _I.aten_cumulate(values.detach(), x0, x, nb_steps, ascending)
+
+
+@cc_cumulate.register_fake
+def _(values, x0, x, nb_steps, ascending=False):
+    _check_cumulate(values, x0, x, nb_steps)
+    return values.new_empty(values.shape)
 
 
 # The autograd glue of the two forward ops: one ctx layout, one ``need`` rule, one packer of the nine input gradients.
@@ -604,7 +671,7 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
     return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
 
 
-OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_backward_multi", "cc_backward_multi_fx", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_forward_multi_nodes", "cc_cumulate", "cc_backward_multi", "cc_backward_multi_fx", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
 spec_args = _I.spec_args       # MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it
