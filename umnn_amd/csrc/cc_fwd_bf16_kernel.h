@@ -275,8 +275,12 @@ __device__ __forceinline__ void static_for(std::integer_sequence<int, I...>, F&&
 // WPB: waves per workgroup.  Eight for the shapes whose weight images leave room for ONE workgroup per CU (uniform 6..8-tile nets, deep
 // 5-tile ones: 100-wide toy / MonotonicNN integrands stage 98-147 KB): the second wave of every SIMD then comes from the same
 // workgroup and shares its images, instead of the SIMD running one wave with nothing to overlap its vector phases with.
+// Two waves per SIMD are REQUIRED of the node-paired fp16 variant (252 registers): left to the launch bounds alone the compiler lets it
+// grow to 394, one wave per SIMD, which has lost every time it was measured.  Every other instantiation keeps the default (min 1).
 template <int TMAX, int NPARTS, int P, bool EXACT, int NRL, bool PIPE = false, int INV = 0, int TREST = 0, int WPB = UMNN_WAVES_PER_BLOCK>
-__global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args args) {
+__global__ __launch_bounds__(64 * WPB)
+__attribute__((amdgpu_waves_per_eu((PC_F16 && PIPE && EXACT && TMAX == 4 && NRL == 13 && NPARTS == 2) ? 2 : 1)))
+void cc_fwd_bf16_kernel(const FwdBf16Args args) {
     static_assert(TREST == 0 || (EXACT && !PIPE && TREST < TMAX && (TREST & 1) == 0), "wide-first-layer variants: exact, plain loop");
     static_assert(!INV || (P == 1 && !PIPE), "inversion variants: plain loop, one tile per wave");
     constexpr int KSM = TMAX / 2;
@@ -418,9 +422,12 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             static_assert(NLIVE % 4 == 0 || (NLIVE % 4 == 1 && NFULL == 3), "pipelined loop: 13 or 16 live registers");
             using Slots = std::make_integer_sequence<int, NSLOT>;
             u32x4 wf[4][2][2];                                      // [tile][K-step][piece] of the layer in flight
-            u32x4 bf[2][2][2];                                      // [point tile][K-step][piece]
+            // NODE_PAIRS (fp16 pieces, merged layout): two nodes of each point tile in flight, see the ring loop below
+            constexpr bool NODE_PAIRS = PC_F16 && MERGE;
+            constexpr int NBF = NODE_PAIRS ? 4 : 2;
+            u32x4 bf[NBF][2][2];                                    // [point tile (+ 2 x node of the pair)][K-step][piece]
 #pragma unroll
-            for (int pt = 0; pt < 2; ++pt)
+            for (int pt = 0; pt < NBF; ++pt)
 #pragma unroll
                 for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
@@ -434,8 +441,8 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 sel[0] = u32x4{slot < 2 ? v : 0u, slot < 2 ? 0u : v, 0u, 0u};
                 sel[1] = u32x4{0u, 0u, slot < 2 ? v : 0u, slot < 2 ? 0u : v};
             }
-            float rem_a = 0.f;                                      // the single live register of tile 3 (13-register shape)
-            unsigned rem_hi = 0u;
+            struct Rem { float a = 0.f; unsigned hi = 0u; };         // the single live register of tile 3 (13-register shape): one per
+            Rem rem0;                                                // packing stream, a section of the node-paired loop runs two at a time
             // (every image of this shape is 16 fragments: off16[l] = (l - 1) * 8192 -- computed, not fetched from the kernel
             // arguments: a scalar load per layer and the wait behind it)
             auto frag = [&](int l, int t, int ks, int k2) {
@@ -481,7 +488,7 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             // slots   tile 0: act 0-3, hi 4, lo 10     tile 1: act 5-8, hi 9, lo 16     tile 2: act 11-14, hi 15, lo 20
             //         tile 3: act 17-20, hi 21, lo 23  -- or (MERGE: 20 slots), with one live register, split on the VALU in
             //         slots 17, 18 and tile 2's lo in 19
-            auto pack_slot = [&](auto ic, auto first, f32x4 (&z)[4], u32x4 (&bfout)[2][2], float tkv, const f32x4 (&cv)[TMAX]) {
+            auto pack_slot = [&](auto ic, auto first, f32x4 (&z)[4], u32x4 (&bfout)[2][2], float tkv, const f32x4 (&cv)[TMAX], Rem& rem) {
                 constexpr int i = decltype(ic)::value;
                 constexpr int MODE = decltype(first)::value;      // 0: raw MFMA output, 1: layer 1 (fma first), 2: already activated
                 constexpr bool FIRST = MODE == 1, PRE = MODE == 2;
@@ -556,20 +563,20 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 }
                 if constexpr (i == T3A) {                        // tile 3 has one live register: split it on the VALU
                     if constexpr (FIRST) z[3][0] = fmaf(w1x[3][0], tkv, cv[3][0]);
-                    rem_a = PRE ? z[3][0] : hidden_act_f(z[3][0], slope);
-                    const unsigned h = pc_cvt_pk(rem_a, 0.f);
-                    rem_hi = h;
-                    bfout[1][0][3] = rem_hi;                     // k-slots 6,7: (hi, 0)
+                    rem.a = PRE ? z[3][0] : hidden_act_f(z[3][0], slope);
+                    const unsigned h = pc_cvt_pk(rem.a, 0.f);
+                    rem.hi = h;
+                    bfout[1][0][3] = rem.hi;                     // k-slots 6,7: (hi, 0)
                 }
                 if constexpr (i == T3B) {
 #ifdef UMNN_FWD_PIECE_F16
-                    float rr = rem_a;
-                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(rr) : "v"(rem_hi));
+                    float rr = rem.a;
+                    asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(rr) : "v"(rem.hi));
                     const unsigned l = pc_cvt_pk(rr, 0.f);
 #else
-                    const unsigned l = pc_cvt_pk(rem_a - pc_lo_f32(rem_hi), 0.f);
+                    const unsigned l = pc_cvt_pk(rem.a - pc_lo_f32(rem.hi), 0.f);
 #endif
-                    bfout[1][0][2] = rem_hi | (l << 16);      // k-slots 4,5: (hi, lo)
+                    bfout[1][0][2] = rem.hi | (l << 16);      // k-slots 4,5: (hi, lo)
                 }
             };
 
@@ -589,7 +596,156 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
             }
             float cs_cur = a.ccs[k_lo], cw_cur = a.ccw[k_lo];       // node abscissa / weight: fetched one node ahead
             float Fpair = 0.f, fxpair = 0.f, fx0pair = 0.f;          // quadrature sum, f(x), f(x0) of BOTH tiles (cc_fwd_shared.h)
-            for (int k = k_lo; k < k_hi; ++k) {
+            int k = k_lo;
+            // ---- node-paired ring (NODE_PAIRS): nodes k, k+1 of both point tiles run as four tile-nodes X0, Y0, X1, Y1 (X = tile 0,
+            // Y = tile 1, subscript = node of the pair) and every hidden layer as FOUR sections: section j issues the MFMA slots of
+            // tile-node j and, in their shadows, the pack_slot work of tile-node j-1 -- sections A / B of the loop below, extended to
+            // a ring.  A layer's 16 weight fragments then serve four tile-nodes before they are read again: 12 ds_read_b128 per
+            // tile-node instead of 24 (the re-read is the largest vector item of the kernel's energy table, EXPERIMENTS "node pairs").
+            // The two nodes of a point tile share c[pt], w1x, wout and the epilogue state; what the ring adds is two more operand
+            // sets (bf[2], bf[3]) and the scratch of a second packing stream.  Accumulators alternate between two sets (a, b, a, b):
+            // the set tile-node j writes was packed (or summed) one section earlier.  reload_slot sits in the fourth section, behind
+            // the last use of each fragment, a full section ahead of the first use.  Layer 1 (VALU only) of Y0 goes where the loop
+            // below puts it; X1 is prepared next to it and Y1 next to the packing of X0 in the second section (ahead_slot); X0 of the
+            // NEXT pair (or of the leftover node) is prepared in the last section, as znext.  Per tile-node every operation and its
+            // order are those of the loop below, and the output stage runs per node, in node order: the same bits.
+#ifdef UMNN_FWD_PIECE_F16
+            if constexpr (NODE_PAIRS) {
+                constexpr std::integral_constant<int, 1> kPack{};       // shadow work of a ring section: pack tile-node j-1's layer output,
+                constexpr std::integral_constant<int, 2> kDot{};        // or (last hidden layer) its output dot product
+                constexpr std::true_type kYes{};
+                constexpr std::false_type kNo{};
+                // Layer 1 + packing of a tile-node that is prepared AHEAD of its turn, next to another packing stream: pack_slot's
+                // arithmetic per register (fma, activation, leading pieces, exact remainders, second pieces), but one tile after the
+                // other -- four values in flight instead of thirteen, in the sections where all four operand sets are live
+                //   tile T = 0, 1, 2 in slots 5T .. 5T+4: fma + act (two slots), cvt hi, remainders, cvt lo;   tile 3's register in 15, 16
+                struct Ahead { f32x4 z; unsigned h0, h1; Rem rem; };
+                auto ahead_slot = [&](auto ic, Ahead& s, u32x4 (&bfout)[2][2], float tkv, const f32x4 (&cv)[TMAX]) {
+                    constexpr int i = decltype(ic)::value;
+                    if constexpr (i < 15) {
+                        constexpr int T = i / 5, ph = i % 5;
+                        if constexpr (ph < 2) {
+#pragma unroll
+                            for (int r = 2 * ph; r < 2 * ph + 2; ++r) s.z[r] = hidden_act_f(fmaf(w1x[T][r], tkv, cv[T][r]), slope);
+                        }
+                        if constexpr (ph == 2) {
+                            s.h0 = pc_cvt_pk(s.z[0], s.z[1]);
+                            s.h1 = pc_cvt_pk(s.z[2], s.z[3]);
+                            bfout[T / 2][0][2 * (T % 2)] = s.h0;
+                            bfout[T / 2][0][2 * (T % 2) + 1] = s.h1;
+                            if constexpr (T == 2) { bfout[1][1][2] = s.h0; bfout[1][1][3] = s.h1; }      // (closes the last merged K-step)
+                        }
+                        if constexpr (ph == 3) { pc_sub_halves<0>(s.z, s.h0); pc_sub_halves<2>(s.z, s.h1); }
+                        if constexpr (ph == 4) {
+                            bfout[T / 2][1][2 * (T % 2)] = pc_cvt_pk(s.z[0], s.z[1]);
+                            bfout[T / 2][1][2 * (T % 2) + 1] = pc_cvt_pk(s.z[2], s.z[3]);
+                        }
+                    }
+                    if constexpr (i == 15) {
+                        s.rem.a = hidden_act_f(fmaf(w1x[3][0], tkv, cv[3][0]), slope);
+                        s.rem.hi = pc_cvt_pk(s.rem.a, 0.f);
+                        bfout[1][0][3] = s.rem.hi;                     // k-slots 6,7: (hi, 0)
+                    }
+                    if constexpr (i == 16) {
+                        float rr = s.rem.a;
+                        asm("v_fma_mix_f32 %0, %1, -1.0, %0 op_sel_hi:[1,0,0]" : "+v"(rr) : "v"(s.rem.hi));
+                        bfout[1][0][2] = s.rem.hi | (pc_cvt_pk(rr, 0.f) << 16);      // k-slots 4,5: (hi, lo)
+                    }
+                };
+                // one ring section.  MFMA side: bfm -> accm.  Shadow: WORK on (zp -> bfp | sd); AHEAD: ahead_slot (abscissa ta, hoisted
+                // term ca) -> bfa; NEXT0: layer 1 of the next node's first tile -> znext; RELOAD: the fragments of layer lnext
+                auto ring = [&](auto work_c, auto ahead_c, auto next0_c, auto reload_c, const u32x4 (&bfm)[2][2], f32x4 (&accm)[4],
+                                f32x4 (&zp)[4], u32x4 (&bfp)[2][2], float& sd, u32x4 (&bfa)[2][2], float ta, const f32x4 (&ca)[TMAX],
+                                float tkn0, int lnext) {
+                    constexpr int WORK = decltype(work_c)::value;
+                    constexpr bool AHEAD = decltype(ahead_c)::value, NEXT0 = decltype(next0_c)::value, RELOAD = decltype(reload_c)::value;
+                    constexpr std::false_type kLater{};
+                    [[maybe_unused]] Ahead ah;
+                    Rem rp;
+                    static_for(Slots{}, [&](auto ic) {
+                        constexpr int i = decltype(ic)::value;
+                        mfma_slot(ic, bfm, accm);
+                        if constexpr (WORK == 1) pack_slot(ic, kLater, zp, bfp, 0.f, ca, rp);
+                        if constexpr (WORK == 2 && i < NLIVE) sd = fmaf(wout[i / 4][i % 4], hidden_act_f(zp[i / 4][i % 4], slope), sd);
+                        if constexpr (AHEAD) ahead_slot(ic, ah, bfa, ta, ca);
+                        if constexpr (NEXT0 && i >= PRE0) {
+                            constexpr int e = i - PRE0, t = e / 4, r = e % 4;
+                            znext[t][r] = hidden_act_f(fmaf(w1x[t][r], tkn0, c[0][t][r]), slope);
+                        }
+                        if constexpr (RELOAD) reload_slot(ic, lnext);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+                };
+                // Three or more hidden layers (two or more weight images).  A net of two hidden layers keeps the one-node loop below: its
+                // ring has another shape (layer 1 is the last hidden layer as well), and a second pair loop next to this one costs the
+                // kernel 60 spilled registers -- the compiler then holds the loops' copies of the 16 fragments side by side.
+                for (; L > 2 && k + 1 < k_hi; k += 2) {
+                    const int kn = k + 2 <= n ? k + 2 : n;
+                    const float cs_1 = a.ccs[k + 1], cw_1 = a.ccw[k + 1];          // (k + 1 < k_hi <= n + 1)
+                    const float cs_next = a.ccs[kn], cw_next = a.ccw[kn];
+                    const float u0 = cs_cur + 1.f, u1 = cs_1 + 1.f;
+                    const float wk0 = cw_cur, wk1 = cw_1;
+                    cs_cur = cs_next; cw_cur = cw_next;
+                    const float tky0 = k == 0 ? xv[1] : __fadd_rn(x0v[1], __fmul_rn(dxv[1], u0) * 0.5f);
+                    const float tkx1 = __fadd_rn(x0v[0], __fmul_rn(dxv[0], u1) * 0.5f);       // (k + 1 >= 1: never node 0)
+                    const float tky1 = __fadd_rn(x0v[1], __fmul_rn(dxv[1], u1) * 0.5f);
+                    const float tkn0 = __fadd_rn(x0v[0], __fmul_rn(dxv[0], cs_next + 1.f) * 0.5f);
+                    f32x4 acca[4], accb[4];
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) acca[t] = znext[t];
+                    constexpr std::integral_constant<int, 2> kPre{};
+                    float sdx0 = 0.f, sdy0 = 0.f, sdx1 = 0.f, sdy1 = 0.f;
+                    // X0: its layer 1 is already there, only the packing is left -- nothing to hide behind yet
+                    static_for(Slots{}, [&](auto ic) { pack_slot(ic, kPre, acca, bf[0], 0.f, c[0], rem0); });
+                    __builtin_amdgcn_sched_barrier(0);
+                    // layer 1, section 0: X0 on the matrix pipe; layer 1 + packing of Y0 (as in the loop below) and of X1 on the VALU
+                    {
+                        constexpr std::true_type kFirst{};
+                        Ahead ah;
+                        static_for(Slots{}, [&](auto ic) {
+                            mfma_slot(ic, bf[0], acca);
+                            pack_slot(ic, kFirst, accb, bf[1], tky0, c[1], rem0);
+                            ahead_slot(ic, ah, bf[2], tkx1, c[0]);
+                            __builtin_amdgcn_sched_barrier(0);
+                        });
+                    }
+                    {
+                        // layer 1, sections 1-3 (Y1 is prepared next to the packing of X0), then section 0 of layer 2
+                        ring(kPack, kYes, kNo, kNo, bf[1], accb, acca, bf[0], sdx0, bf[3], tky1, c[1], 0.f, 0);
+                        ring(kPack, kNo, kNo, kNo, bf[2], acca, accb, bf[1], sdy0, bf[1], 0.f, c[1], 0.f, 0);
+                        ring(kPack, kNo, kNo, kYes, bf[3], accb, acca, bf[2], sdx1, bf[2], 0.f, c[0], 0.f, 2);
+                        ring(kPack, kNo, kNo, kNo, bf[0], acca, accb, bf[3], sdy1, bf[3], 0.f, c[1], 0.f, 0);
+                        for (int l = 2; l + 1 < L; ++l) {
+                            // sections 1-3 of layer l, section 0 of layer l+1
+                            ring(kPack, kNo, kNo, kNo, bf[1], accb, acca, bf[0], sdx0, bf[0], 0.f, c[0], 0.f, 0);
+                            ring(kPack, kNo, kNo, kNo, bf[2], acca, accb, bf[1], sdy0, bf[1], 0.f, c[1], 0.f, 0);
+                            ring(kPack, kNo, kNo, kYes, bf[3], accb, acca, bf[2], sdx1, bf[2], 0.f, c[0], 0.f, l + 1);
+                            ring(kPack, kNo, kNo, kNo, bf[0], acca, accb, bf[3], sdy1, bf[3], 0.f, c[1], 0.f, 0);
+                        }
+                        // last hidden layer, sections 1 and 2: the outputs of X0 and Y0 go into their output dot products
+                        ring(kDot, kNo, kNo, kNo, bf[1], accb, acca, bf[0], sdx0, bf[0], 0.f, c[0], 0.f, 0);
+                        ring(kDot, kNo, kNo, kNo, bf[2], acca, accb, bf[1], sdy0, bf[1], 0.f, c[1], 0.f, 0);
+                    }
+                    // output stage of node k (group_allreduce_pair: tile 0 in lane groups 0 and 2, tile 1 in groups 1 and 3)
+                    const float f0 = pc_out_act(group_allreduce_pair(sdx0, sdy0), m.out_act);
+                    Fpair = fmaf(wk0, maybe_inverse(f0, a.inv_f), Fpair);
+                    if (k == 0) fxpair = f0;                      // (k < k + 1 <= n: node n is never the first of a pair)
+                    // last section: Y1 on the matrix pipe; the dot product of X1, layer 1 of the next node's first tile, the reload
+                    ring(kDot, kNo, kYes, kYes, bf[3], accb, acca, bf[2], sdx1, bf[2], 0.f, c[0], tkn0, 1);
+#pragma unroll
+                    for (int t = 0; t < 4; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r)
+                            if (4 * t + r < NLIVE) sdy1 = fmaf(wout[t][r], hidden_act_f(accb[t][r], slope), sdy1);
+                    // output stage of node k+1: after node k's, so that the quadrature sum sees the nodes in order
+                    const float f1 = pc_out_act(group_allreduce_pair(sdx1, sdy1), m.out_act);
+                    Fpair = fmaf(wk1, maybe_inverse(f1, a.inv_f), Fpair);
+                    if (k + 1 == n) fx0pair = f1;
+                }
+            }
+#endif
+            // one node per iteration (NODE_PAIRS: the leftover node of an odd range)
+            for (; k < k_hi; ++k) {
                 const int kn = k + 1 <= n ? k + 1 : n;
                 const float cs_next = a.ccs[kn], cw_next = a.ccw[kn];
                 const float u = cs_cur + 1.f;
@@ -605,27 +761,27 @@ __global__ __launch_bounds__(64 * WPB) void cc_fwd_bf16_kernel(const FwdBf16Args
                 constexpr std::false_type kLater{};
                 constexpr std::integral_constant<int, 2> kPre{};
                 // first tile: its layer 1 is already there, only the packing is left -- nothing to hide behind yet
-                static_for(Slots{}, [&](auto ic) { pack_slot(ic, kPre, acc0, bf[0], tk[0], c[0]); });
+                static_for(Slots{}, [&](auto ic) { pack_slot(ic, kPre, acc0, bf[0], tk[0], c[0], rem0); });
                 __builtin_amdgcn_sched_barrier(0);
                 // section A of layer 1: first tile on the matrix pipe, second tile's layer 1 + packing on the VALU
                 static_for(Slots{}, [&](auto ic) {
                     constexpr int i = decltype(ic)::value;
                     mfma_slot(ic, bf[0], acc0);
-                    pack_slot(ic, kFirst, acc1, bf[1], tk[1], c[1]);
+                    pack_slot(ic, kFirst, acc1, bf[1], tk[1], c[1], rem0);
                     __builtin_amdgcn_sched_barrier(0);
                 });
                 for (int l = 1; l + 1 < L; ++l) {
                     // section B of layer l: second tile on the matrix pipe, first tile's output packed for layer l+1
                     static_for(Slots{}, [&](auto ic) {
                         mfma_slot(ic, bf[1], acc1);
-                        pack_slot(ic, kLater, acc0, bf[0], 0.f, c[0]);
+                        pack_slot(ic, kLater, acc0, bf[0], 0.f, c[0], rem0);
                         reload_slot(ic, l + 1);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                     // section A of layer l+1
                     static_for(Slots{}, [&](auto ic) {
                         mfma_slot(ic, bf[0], acc0);
-                        pack_slot(ic, kLater, acc1, bf[1], 0.f, c[1]);
+                        pack_slot(ic, kLater, acc1, bf[1], 0.f, c[1], rem0);
                         __builtin_amdgcn_sched_barrier(0);
                     });
                 }
