@@ -274,6 +274,28 @@ int umnn_cc_forward_multi_nodes(const umnn_mlp* net, const float* x0, const floa
 int umnn_cc_cumulate(const float* Q, const float* values, const float* x0, const float* x, int nb_steps, long long NI, int K,
                      float* out, void* stream);
 
+/* The backward of a curve (cc_multi.hip, cc_cumulate.hip; d = 1, fp32 storage, exact fp32 MFMA, no float atomics: two runs are
+ * bit-identical).
+ * umnn_cc_backward_multi_nodes: the multi-output backward with a cotangent PER NODE, cot_nodes[b][j][k] of f_k(t_j; h_b), [B,
+ * nb_steps + 1, K], k minor, in the node order of f_nodes above (node 0 is x).  K in [1, UMNN_MAX_OUTPUTS], d must be 1.
+ *   dh, dtheta = sum_j VJP_f(t_j, h)[cot_nodes[:, j]]                     (dtheta OVERWRITTEN, flat in parameters() order)
+ *   dx  = sum_j (u_j / 2)     tau_j,    dx0 = sum_j (1 - u_j / 2) tau_j,   tau_j = sum_k cot_nodes[b][j][k] df_k/dt (t_j),
+ * u_j = cc_s[j] + 1: what the limits do through the nodes t_j = x0 + (x - x0) u_j / 2.  There is no quadrature weight, no span
+ * factor and no Leibniz term in it -- the caller owns them -- and no division by x - x0: a row with x == x0 is an ordinary row.
+ * The passes, the finishing kernels and the workspace layout are umnn_cc_backward_multi_fx's (the node-cotangent builds of the same
+ * passes); the workspace size is umnn_cc_backward_multi_nodes_workspace_bytes -- umnn_cc_backward_multi_workspace_bytes's figure,
+ * answered for K = 1 too.  UMNN_EUNSUPPORTED as umnn_cc_backward_multi_fx; B == 0 launches nothing and zeroes dtheta.
+ * umnn_cc_cumulate_adjoint: out[q][j][k] = sum_i Qt[j][i] g[q][i][k], i, j = 0..nb_steps: umnn_cc_cumulate's product alone, with
+ * no span factor and no reversed output index.  With Qt the transpose of the table umnn_cc_cumulate applied -- its rows reversed,
+ * so that g is indexed from the lower limit like that entry's output (umnn_amd.quadrature.device_cumulative_adjoint) -- out is the
+ * cotangent of its `values` up to the factor (x - x0)/2.  Same limits and answers as umnn_cc_cumulate. */
+int umnn_cc_backward_multi_nodes(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* cot_nodes,
+                                 const float* cc_s, int nb_steps, long long B, int d, int E,
+                                 float* dx0, float* dx, float* dh, float* dtheta,
+                                 void* workspace, long long workspace_bytes, void* stream);
+long long umnn_cc_backward_multi_nodes_workspace_bytes(const umnn_mlp* net, long long B, int E);
+int umnn_cc_cumulate_adjoint(const float* Qt, const float* g, int nb_steps, long long NI, int K, float* out, void* stream);
+
 /* Inverse of a weighted sum of the K monotone outputs, for all B rows in ONE launch (cc_multi.hip; MonotonicNN's shape, d = 1): solves
  *     sum_k coef[b,k] * int_0^{x_b} f_k(t; h_b) dt = target[b]        for x_b in [lo, hi]
  * with coef >= 0 and a positive entry per row (not checked) -- the event time of K competing risks, a quantile of a mixture of K

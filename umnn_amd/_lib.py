@@ -93,6 +93,10 @@ SIGNATURES = {
     "umnn_cc_backward_multi_fx": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
                                                  _ll, ctypes.c_int, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
     "umnn_cc_backward_multi_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int, ctypes.c_int]),
+    "umnn_cc_backward_multi_nodes": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int,
+                                                    _ll, ctypes.c_int, ctypes.c_int, _fp, _fp, _fp, _fp, _fp, _ll, _fp]),
+    "umnn_cc_backward_multi_nodes_workspace_bytes": (_ll, [ctypes.POINTER(MlpDesc), _ll, ctypes.c_int]),
+    "umnn_cc_cumulate_adjoint": (ctypes.c_int, [_fp, _fp, ctypes.c_int, _ll, ctypes.c_int, _fp, _fp]),
     "umnn_cc_solve_multi": (ctypes.c_int, [ctypes.POINTER(MlpDesc), _fp, _fp, _fp, _fp, _fp, ctypes.c_int, _ll, ctypes.c_int,
                                            ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_int, _fp, _fp, _fp, _fp, _fp]),
     "umnn_cc_tables_host": (ctypes.c_int, [ctypes.c_int, ctypes.POINTER(ctypes.c_float),

@@ -15,6 +15,11 @@
 // A wave owns one row at a time and strides over the rows; MT = 1, 2, 4 or 8 row tiles of Q (n + 1 <= 16 MT) are template
 // constants, the K-steps (padded to a multiple of four, so that four loads are in flight) a launch argument.  Plain vector loads
 // and stores, no atomics: two runs are bit-identical.
+//
+// The adjoint (umnn_cc_cumulate_adjoint, the ADJ build: the same body with another epilogue) is the product alone,
+//   out[q][j][k] = sum_i Qt[j][i] g[q][i][k]
+// -- no span factor and no reversed index: the host picks the (transposed) table, so that g is taken ascending, as the public
+// outputs are, and out lands where the caller wants it (quadrature.device_cumulative_adjoint).
 #include "cc_host.h"
 
 struct CumulateArgs {
@@ -29,7 +34,7 @@ struct CumulateArgs {
 
 constexpr size_t UMNN_CUMULATE_LDS = 64 * 1024;     // Q's image: MT * KSP * 256 bytes, n + 1 <= 128
 
-template <int MT>
+template <int MT, bool ADJ = false>
 __global__ __launch_bounds__(UMNN_BLOCK) void cc_cumulate_kernel(const CumulateArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const int tid = threadIdx.x, lane = tid & 63;
@@ -65,31 +70,40 @@ __global__ __launch_bounds__(UMNN_BLOCK) void cc_cumulate_kernel(const CumulateA
 #pragma unroll
                 for (int t = 0; t < MT; ++t) acc[t] = mfma16(img[(t * KSP + s0 + c) * 64], b[c], acc[t]);
         }
-        const float dxv = a.x[q] - (a.x0 ? a.x0[q] : 0.f);
         float* __restrict__ oq = a.out + q * row;
+        if (ADJ) {
 #pragma unroll
-        for (int t = 0; t < MT; ++t)
+            for (int t = 0; t < MT; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int i = 16 * t + 4 * g + r;
-                if (i <= n && p < K) oq[(n - i) * K + p] = acc[t][r] * dxv * 0.5f;
-            }
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * t + 4 * g + r;
+                    if (i <= n && p < K) oq[i * K + p] = acc[t][r];
+                }
+        } else {
+            const float dxv = a.x[q] - (a.x0 ? a.x0[q] : 0.f);
+#pragma unroll
+            for (int t = 0; t < MT; ++t)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int i = 16 * t + 4 * g + r;
+                    if (i <= n && p < K) oq[(n - i) * K + p] = acc[t][r] * dxv * 0.5f;
+                }
+        }
     }
 }
 
 typedef void (*cumulate_kernel_t)(const CumulateArgs);
-struct CumulateVariant { int MT; cumulate_kernel_t fn; const char* name; };
-static const CumulateVariant kCumulate[] = {
-    {1, cc_cumulate_kernel<1>, "cc_cumulate<MT=1>"}, {2, cc_cumulate_kernel<2>, "cc_cumulate<MT=2>"},
-    {4, cc_cumulate_kernel<4>, "cc_cumulate<MT=4>"}, {8, cc_cumulate_kernel<8>, "cc_cumulate<MT=8>"},
-};
+// fn / name [1]: the adjoint build (noted as a backward launch: the launch notes class a kernel by the cc_bwd prefix of its name)
+struct CumulateVariant { int MT; cumulate_kernel_t fn[2]; const char* name[2]; };
+#define CUMULATE(MT) { MT, {cc_cumulate_kernel<MT>, cc_cumulate_kernel<MT, true>}, {"cc_cumulate<MT=" #MT ">", "cc_bwd_cumulate_adjoint<MT=" #MT ">"} }
+static const CumulateVariant kCumulate[] = { CUMULATE(1), CUMULATE(2), CUMULATE(4), CUMULATE(8) };
 
-extern "C" int umnn_cc_cumulate(const float* Q, const float* values, const float* x0, const float* x, int nb_steps, long long NI,
-                                int K, float* out, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
-    if (nb_steps < 1) return umnn_fail(UMNN_EINVAL, "cumulate: nb_steps must be >= 1");
-    if (NI < 0) return umnn_fail(UMNN_EINVAL, "cumulate: NI must be >= 0");
-    if (K < 1 || K > UMNN_MAX_OUTPUTS) return umnn_fail(UMNN_EINVAL, "cumulate: K must be between 1 and UMNN_MAX_OUTPUTS");
+static int cumulate_launch(const float* Q, const float* values, const float* x0, const float* x, int nb_steps, long long NI,
+                           int K, float* out, int adj, hipStream_t stream) {
+    if (nb_steps < 1) return umnn_fail(UMNN_EINVAL, adj ? "cumulate_adjoint: nb_steps must be >= 1" : "cumulate: nb_steps must be >= 1");
+    if (NI < 0) return umnn_fail(UMNN_EINVAL, adj ? "cumulate_adjoint: NI must be >= 0" : "cumulate: NI must be >= 0");
+    if (K < 1 || K > UMNN_MAX_OUTPUTS)
+        return umnn_fail(UMNN_EINVAL, adj ? "cumulate_adjoint: K must be between 1 and UMNN_MAX_OUTPUTS" : "cumulate: K must be between 1 and UMNN_MAX_OUTPUTS");
     CumulateArgs a;
     a.n = nb_steps; a.K = K; a.NI = NI;
     a.KSP = (((nb_steps + 1 + 3) / 4) + 3) & ~3;
@@ -97,18 +111,30 @@ extern "C" int umnn_cc_cumulate(const float* Q, const float* values, const float
     for (const CumulateVariant& c : kCumulate)
         if (!v && nb_steps + 1 <= 16 * c.MT) v = &c;
     const size_t lds = v ? (size_t)v->MT * a.KSP * 64 * sizeof(float) : 0;
-    if (!v || lds > UMNN_CUMULATE_LDS) return umnn_fail(UMNN_EUNSUPPORTED, "cumulate: the table of nb_steps > 127 exceeds the 64 KiB LDS budget");
+    if (!v || lds > UMNN_CUMULATE_LDS)
+        return umnn_fail(UMNN_EUNSUPPORTED, adj ? "cumulate_adjoint: the table of nb_steps > 127 exceeds the 64 KiB LDS budget"
+                                                : "cumulate: the table of nb_steps > 127 exceeds the 64 KiB LDS budget");
     if (NI == 0) return 0;
-    if (!Q || !values || !x || !out) return umnn_fail(UMNN_EINVAL, "cumulate: Q, values, x, out must be non-null");
+    if (!Q || !values || (!adj && !x) || !out)
+        return umnn_fail(UMNN_EINVAL, adj ? "cumulate_adjoint: Qt, g, out must be non-null" : "cumulate: Q, values, x, out must be non-null");
     a.Q = Q; a.v = values; a.x0 = x0; a.x = x; a.out = out;
-    if (int rc = umnn_allow_lds((const void*)v->fn, lds)) return rc;
+    if (int rc = umnn_allow_lds((const void*)v->fn[adj], lds)) return rc;
     // a wave strides over the rows: at least eight per wave once there are that many, so that staging Q is a small part of its work
     long long blocks = (NI + 8 * UMNN_WAVES_PER_BLOCK - 1) / (8 * UMNN_WAVES_PER_BLOCK);
     const long long cap = 8LL * umnn_num_cus();
     if (blocks > cap) blocks = cap;
     umnn_prof_begin(stream);
-    hipLaunchKernelGGL(v->fn, dim3((unsigned)blocks), dim3(UMNN_BLOCK), lds, stream, a);
-    umnn_prof_end(stream, 2.0 * (nb_steps + 1) * (nb_steps + 1) * K * (double)NI, UMNN_PROF_FORWARD);
-    umnn_note_launch(v->name);
+    hipLaunchKernelGGL(v->fn[adj], dim3((unsigned)blocks), dim3(UMNN_BLOCK), lds, stream, a);
+    umnn_prof_end(stream, 2.0 * (nb_steps + 1) * (nb_steps + 1) * K * (double)NI, adj ? UMNN_PROF_BACKWARD : UMNN_PROF_FORWARD);
+    umnn_note_launch(v->name[adj]);
     return umnn_check(hipGetLastError(), "cc_cumulate launch");
+}
+
+extern "C" int umnn_cc_cumulate(const float* Q, const float* values, const float* x0, const float* x, int nb_steps, long long NI,
+                                int K, float* out, void* stream) {
+    return cumulate_launch(Q, values, x0, x, nb_steps, NI, K, out, 0, (hipStream_t)stream);
+}
+
+extern "C" int umnn_cc_cumulate_adjoint(const float* Qt, const float* g, int nb_steps, long long NI, int K, float* out, void* stream) {
+    return cumulate_launch(Qt, g, nullptr, nullptr, nb_steps, NI, K, out, 1, (hipStream_t)stream);
 }

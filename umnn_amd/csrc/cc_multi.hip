@@ -68,6 +68,7 @@ struct MultiArgs {
     int w1x_off;                    // backward: float offset of the first layer's x-column, [16 T] in feature order
     int scratch_off, scratch_per_wave, l_lo, n_params;
     int outw;                       // backward: this pass accumulates the output layer's dW_L / db_L (OUTW variants only)
+    const float* cot;               // backward, NC variants only: the cotangent of f_k at every node, [NI][n + 1][K], node 0 is x
 };
 
 // ------------------------------------------------------------------------------------------ forward
@@ -665,7 +666,14 @@ __device__ __forceinline__ void stage_multi_rowmajor(const MultiArgs& a, float* 
 // cotangent alone -- the ordinary node 0 keeps the quadrature's --, because the delta_1 of that walk is what dx needs:
 // sum_k g_fx,k df_k/dx = sum_feature delta_1[feature] W_1[feature, x-column].  No register is held across the node loop for it
 // (g_fx is loaded where it is used, dx is written from inside the walk), and the variants without FX are the kernels they were.
-template <int TMAX, int KSC, int NACC, bool EDGE, bool OUTW, bool FX>
+// NC: the node-cotangent build (umnn_cc_backward_multi_nodes: the backward of a whole curve).  The cotangent of f_k at node j is an
+// input of its own, dout_k = cot[q][j][k] out'(s_k) (a.cot, loaded at the top of the node's iteration so that the forward recompute
+// hides the loads; dead lanes and k >= K give 0): no quadrature weight, no g, no inv_f, and never together with FX.  Its EDGE pass
+// has no Leibniz terms: a node t_j = x0 + (x - x0) u_j / 2 moves with both limits, so dx = sum_j (u_j / 2) tau_j and dx0 =
+// sum_j (1 - u_j / 2) tau_j with tau_j = sum_k cot[j][k] df_k/dt (t_j) = sum_feature delta_1[feature] W_1[feature, x-column], the
+// dot product of the FX build's extra walk, here at every node into two per-lane scalars that are reduced once after the loop.
+// The variants without NC are the kernels they were.
+template <int TMAX, int KSC, int NACC, bool EDGE, bool OUTW, bool FX, bool NC = false>
 __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const MultiArgs a) {
     extern __shared__ __attribute__((aligned(16))) float lds[];
     const MlpDev& m = a.m;
@@ -719,12 +727,16 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
         const float x0v = a.x0 ? a.x0[qq] : 0.f;
         const float dxv = xv - x0v;
         f32x4 gv, cotbase;                             // dead lanes and outputs k >= K contribute nothing
+        if (!NC) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int k = 4 * r + g;
-            gv[r] = (ok && k < K) ? a.g[qq * K + k] : 0.f;
-            cotbase[r] = gv[r] * dxv * 0.5f;
+            for (int r = 0; r < 4; ++r) {
+                const int k = 4 * r + g;
+                gv[r] = (ok && k < K) ? a.g[qq * K + k] : 0.f;
+                cotbase[r] = gv[r] * dxv * 0.5f;
+            }
         }
+        const float* __restrict__ cotq = NC ? a.cot + qq * ((long long)(n + 1) * K) : nullptr;
+        float taux = 0.f, taux0 = 0.f;                 // NC && EDGE: sum_j (u_j / 2) tau_j and sum_j (1 - u_j / 2) tau_j, this lane's part
         const long long bi = qq / d;
         const IoView hb = IoView{a.h, 0} + (bi * ((long long)E * d) + (qq - bi * d));
 
@@ -761,7 +773,15 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
             const bool xtra = FX && EDGE && k > n;
             const int kn = xtra ? 0 : k;
             const float u = a.ccs[kn] + 1.f;
-            const float wk = a.ccw[kn];
+            const float wk = NC ? 0.f : a.ccw[kn];
+            f32x4 cotv;
+            if (NC) {
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int ko = 4 * r + g;
+                    cotv[r] = (ok && ko < K) ? cotq[k * K + ko] : 0.f;
+                }
+            }
             const float tk = kn == 0 ? xv : __fadd_rn(x0v, __fmul_rn(dxv, u) * 0.5f);
             unsigned bits[UMNN_MAX_LINEAR];          // bits[l]: sign bits of hidden layer l's activation
             f32x4 act[TMAX];
@@ -806,8 +826,12 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                 const float fp = out_grad_f(o[r], m.out_act);
                 if (k == 0) fxv[r] = f;
                 if (k == n) fx0v[r] = f;
-                const float invs = a.inv_f ? -__frcp_rn(f * f) : 1.f;
-                dout[r] = cotbase[r] * invs * wk * fp;
+                if (NC) {
+                    dout[r] = cotv[r] * fp;
+                } else {
+                    const float invs = a.inv_f ? -__frcp_rn(f * f) : 1.f;
+                    dout[r] = cotbase[r] * invs * wk * fp;
+                }
                 if (FX && (xtra || (!EDGE && k == 0))) {
                     const int ko = 4 * r + g;
                     const float gf = (ok && ko < K) ? a.gfx[qq * K + ko] : 0.f;
@@ -892,6 +916,16 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                         dcs[t][r] += delta[t][r];
                         dW1x[t][r] = fmaf(delta[t][r], tk, dW1x[t][r]);
                     }
+                if (NC) {
+                    float tau = 0.f;
+#pragma unroll
+                    for (int t = 0; t < TMAX; ++t)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) tau = fmaf(delta[t][r], w1x[16 * t + 4 * r], tau);
+                    const float hu = u * 0.5f;             // (node 0 is x: u = 2; node n is x0: u = 0)
+                    taux = fmaf(hu, tau, taux);
+                    taux0 = fmaf(1.f - hu, tau, taux0);
+                }
             }
             if (xtra) {
                 // dx = sum_k g_k f_k(x) + sum_feature delta_1[feature] W_1[feature, x-column]  (delta_1 of g_fx out' alone)
@@ -918,6 +952,15 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
                         if (f < H1) a.dc[q * H1 + f] = dcs[t][r];
                     }
             }
+            if (NC) {
+                // the limits move the nodes: the tau sums alone (the caller adds what the cotangents of t and of the span give)
+                taux = group_allreduce(taux);
+                taux0 = group_allreduce(taux0);
+                if (ok && g == 0) {
+                    if (a.dx) a.dx[q] = taux;
+                    if (a.dx0) a.dx0[q] = taux0;
+                }
+            } else {
             // Leibniz terms (the convention of cc_backward.hip: f itself, also under inv_f), summed over the K outputs
             float sx = 0.f, sx0 = 0.f;
 #pragma unroll
@@ -927,6 +970,7 @@ __global__ __launch_bounds__(UMNN_BLOCK, 1) void cc_bwd_multi_kernel(const Multi
             if (ok && g == 0) {
                 if (!FX && a.dx) a.dx[q] = sx;
                 if (a.dx0) a.dx0[q] = -sx0;
+            }
             }
         }
     }
@@ -1054,10 +1098,12 @@ static const MultiNodesVariant kMultiNodes[] = {
 };
 
 // the backward passes of a family: the EDGE pass holds `edge_nacc` dW layers, every further pass `rest_nacc`
-// fn / name [1]: the FX build of the pass (a g_fx cotangent was given), [0]: the kernel without it
-struct MultiBwdVariant { int T, KS, nacc, edge, outw; multi_kernel_t fn[2]; const char* name[2]; };
-#define MULTI_BWD(T, KS, N, E, O) { T, KS, N, E, O, {cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, false>, cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, true>}, \
-                                    {"cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ">", "cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ",FX=1>"} }
+// fn / name [1]: the FX build of the pass (a g_fx cotangent was given), [2]: the node-cotangent build (NC), [0]: the kernel without either
+struct MultiBwdVariant { int T, KS, nacc, edge, outw; multi_kernel_t fn[3]; const char* name[3]; };
+#define MULTI_BWD(T, KS, N, E, O) { T, KS, N, E, O, {cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, false>, cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, true>, \
+                                                     cc_bwd_multi_kernel<T, KS, N, (E) != 0, (O) != 0, false, true>}, \
+                                    {"cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ">", "cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ",FX=1>", \
+                                     "cc_bwd_multi<T=" #T ",KS=" #KS ",NACC=" #N ",EDGE=" #E ",OUTW=" #O ",NC=1>"} }
 static const MultiBwdVariant kMultiBwd[] = {
     MULTI_BWD(2, 8, 3, 1, 1), MULTI_BWD(2, 8, 3, 0, 0),
     MULTI_BWD(4, 13, 3, 1, 1), MULTI_BWD(4, 13, 3, 0, 0),
@@ -1267,23 +1313,33 @@ static void multi_workspace(const MultiPlan& pl, long long NI, int E, long long*
     *total = o;
 }
 
-extern "C" long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E) {
+static long long multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E, int min_out) {
     if (B <= 0) return 0;
     MultiPlan pl;
-    if (d < 1 || multi_plan(net, E, &pl)) return -1;
+    if (d < 1 || multi_plan(net, E, &pl, min_out)) return -1;
     if (!pl.bwd_ok) { umnn_fail(UMNN_EUNSUPPORTED, kMultiBwdLdsError); return -1; }
     long long o_dc, o_p0, total;
     multi_workspace(pl, B * (long long)d, E, &o_dc, &o_p0, &total);
     return total;
 }
 
-extern "C" int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
-                                         const float* g_fx, const float* cc_w, const float* cc_s, int nb_steps, long long B, int d,
-                                         int E, int inv_f, float* dx0, float* dx, float* dh, float* dtheta,
-                                         void* workspace, long long workspace_bytes, void* stream_) {
-    hipStream_t stream = (hipStream_t)stream_;
+extern "C" long long umnn_cc_backward_multi_workspace_bytes(const umnn_mlp* net, long long B, int d, int E) {
+    return multi_workspace_bytes(net, B, d, E, 2);
+}
+
+// (the same layout and, for K >= 2, the same figure: the node-cotangent entry takes a single output too)
+extern "C" long long umnn_cc_backward_multi_nodes_workspace_bytes(const umnn_mlp* net, long long B, int E) {
+    return multi_workspace_bytes(net, B, 1, E, 1);
+}
+
+// The backward launches: with g (and g_fx) the quadrature's cotangents, or -- `nodes`: the NC build of every pass, K >= 1, no cc_w --
+// a cotangent per node, cot_nodes.
+static int multi_backward(int nodes, const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
+                          const float* g_fx, const float* cot_nodes, const float* cc_w, const float* cc_s, int nb_steps, long long B,
+                          int d, int E, int inv_f, float* dx0, float* dx, float* dh, float* dtheta,
+                          void* workspace, long long workspace_bytes, hipStream_t stream) {
     MultiPlan pl;
-    if (int rc = multi_plan(net, E, &pl)) return rc;
+    if (int rc = multi_plan(net, E, &pl, nodes ? 1 : 2)) return rc;
     if (B < 0 || d < 1) return umnn_fail(UMNN_EINVAL, "backward_multi: B must be >= 0 and d >= 1");
     if (nb_steps < 1) return umnn_fail(UMNN_EINVAL, "backward_multi: nb_steps must be >= 1");
     if (!pl.bwd_ok) return umnn_fail(UMNN_EUNSUPPORTED, kMultiBwdLdsError);
@@ -1292,7 +1348,9 @@ extern "C" int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, c
         if (dtheta) return umnn_check(hipMemsetAsync(dtheta, 0, (size_t)a.n_params * sizeof(float), stream), "memset");
         return 0;
     }
-    if (!x || !h || !g || !cc_w || !cc_s) return umnn_fail(UMNN_EINVAL, "backward_multi: x, h, g, cc_w, cc_s must be non-null");
+    if (nodes ? (!x || !h || !cot_nodes || !cc_s) : (!x || !h || !g || !cc_w || !cc_s))
+        return umnn_fail(UMNN_EINVAL, nodes ? "backward_multi_nodes: x, h, cot_nodes, cc_s must be non-null"
+                                                : "backward_multi: x, h, g, cc_w, cc_s must be non-null");
     a.NI = B * (long long)d; a.d = d; a.E = E; a.n = nb_steps; a.inv_f = inv_f != 0;
     long long o_dc, o_p0, total;
     multi_workspace(pl, a.NI, E, &o_dc, &o_p0, &total);
@@ -1302,8 +1360,9 @@ extern "C" int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, c
     if (tiles > 0x7fffffffLL) return umnn_fail(UMNN_EUNSUPPORTED, "backward_multi: batch too large");
     a.ngroups = (unsigned)tiles;
     char* ws = (char*)workspace;
-    a.x0 = x0; a.x = x; a.h = h; a.g = g; a.gfx = g_fx; a.ccw = cc_w; a.ccs = cc_s; a.dx0 = dx0; a.dx = dx;
-    const int fx = g_fx != nullptr;     // the FX build of every pass; without a g_fx the kernels of umnn_cc_backward_multi
+    a.x0 = x0; a.x = x; a.h = h; a.g = g; a.gfx = g_fx; a.cot = cot_nodes; a.ccw = cc_w; a.ccs = cc_s; a.dx0 = dx0; a.dx = dx;
+    // the FX build of every pass; without a g_fx the kernels of umnn_cc_backward_multi; with node cotangents the NC build
+    const int fx = nodes ? 2 : g_fx != nullptr;
     a.partials = (float*)ws;
     a.dc = (float*)(ws + o_dc);
     float* p0 = (float*)(ws + o_p0);
@@ -1340,6 +1399,27 @@ extern "C" int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, c
                            a.partials, nslices, a.n_params, p0, nparts0, E, H1, a.poffW[0], a.poffb[0], dtheta);
     }
     return umnn_check(hipGetLastError(), "cc_bwd_multi finishing launch");
+}
+
+extern "C" int umnn_cc_backward_multi_fx(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,
+                                         const float* g_fx, const float* cc_w, const float* cc_s, int nb_steps, long long B, int d,
+                                         int E, int inv_f, float* dx0, float* dx, float* dh, float* dtheta,
+                                         void* workspace, long long workspace_bytes, void* stream) {
+    return multi_backward(0, net, x0, x, h, g, g_fx, nullptr, cc_w, cc_s, nb_steps, B, d, E, inv_f, dx0, dx, dh, dtheta,
+                          workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+// The backward of a curve: cot_nodes [B][n + 1][K] is the cotangent of f_k(t_j; h) at every node, in the kernel's node order (node 0
+// is x).  dx / dx0 receive sum_j (u_j / 2) tau_j and sum_j (1 - u_j / 2) tau_j, tau_j = sum_k cot[j][k] df_k/dt (t_j): what moving a
+// limit does through the nodes (no Leibniz term: the caller owns the span factor).  dh, dtheta, the workspace layout, the passes and
+// the finishing kernels are the multi-output backward's.
+extern "C" int umnn_cc_backward_multi_nodes(const umnn_mlp* net, const float* x0, const float* x, const float* h,
+                                            const float* cot_nodes, const float* cc_s, int nb_steps, long long B, int d, int E,
+                                            float* dx0, float* dx, float* dh, float* dtheta,
+                                            void* workspace, long long workspace_bytes, void* stream) {
+    if (d != 1) return umnn_fail(UMNN_EINVAL, "backward_multi_nodes: d must be 1");
+    return multi_backward(1, net, x0, x, h, nullptr, nullptr, cot_nodes, nullptr, cc_s, nb_steps, B, d, E, 0,
+                          dx0, dx, dh, dtheta, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 extern "C" int umnn_cc_backward_multi(const umnn_mlp* net, const float* x0, const float* x, const float* h, const float* g,

@@ -33,7 +33,7 @@ from torch.autograd.function import once_differentiable
 from . import _lib
 from ._common import _graph_mode, _ptr, _stream, traced_native_call  # noqa: F401  (the names are part of this module)
 from .nets import graph_spec, mlp_spec, n_out_of, require_single
-from .quadrature import compute_cc_weights, device_cumulative_matrix, device_tables
+from .quadrature import compute_cc_weights, device_cumulative_adjoint, device_cumulative_matrix, device_tables
 
 _state = threading.local()           # per-thread: last path taken, force_generic nesting
 _warned = set()                       # fallbacks announced once per process (see _warn_once)
@@ -326,7 +326,81 @@ def hip_cumulate(values, x0, x, nb_steps, ascending=False):
     return _quad_done(rc, "umnn_cc_cumulate", (out,), torch.float32, out_dtype)[0]
 
 
+def hip_cumulate_adjoint(g, nb_steps, ascending=False):
+    """umnn_cc_cumulate_adjoint: g [B, nb_steps + 1, K], the cotangent of ``hip_cumulate``'s (ascending) output -> sum_i Qt[j, i] g[:, i],
+    [B, nb_steps + 1, K] in g's dtype: the cotangent of that call's ``values`` up to the factor (x - x0)/2, which the caller applies --
+    in node order, or -- ``ascending`` -- from the lower limit up, like the values were."""
+    n = int(nb_steps)
+    if g.dim() != 3 or g.shape[1] != n + 1:
+        raise RuntimeError(f"umnn_amd: the cotangent of a cumulative quadrature is [B, nb_steps + 1, K]; got {tuple(g.shape)} at nb_steps = {n}")
+    out_dtype = g.dtype
+    g = _as(g, torch.float32)
+    Qt = device_cumulative_adjoint(n, g.device, ascending)
+    out = torch.empty_like(g)
+    with torch.cuda.device(g.device):
+        rc = _lib.lib().umnn_cc_cumulate_adjoint(_ptr(Qt), _ptr(g), n, g.shape[0], g.shape[2], _ptr(out), _stream(g.device))
+    return _quad_done(rc, "umnn_cc_cumulate_adjoint", (out,), torch.float32, out_dtype, backward=True)[0]
+
+
+def hip_backward_multi_nodes(spec, x0, x, h, cot_nodes, nb_steps, need=(True, True, True, True)):
+    """umnn_cc_backward_multi_nodes: the multi-output backward for a cotangent PER NODE, cot_nodes [B, nb_steps + 1, n_out] of
+    f_k(t_j; h) in node order (node 0 is x), n_out = 1..16 -> (dx0_tau, dx_tau, dh, dtheta_flat), None where ``need`` is False:
+    dh / dtheta = sum_j VJP_f(t_j, h)[cot_nodes[:, j]], dx_tau = sum_j (u_j / 2) tau_j and dx0_tau = sum_j (1 - u_j / 2) tau_j with
+    tau_j = sum_k cot_nodes[:, j, k] df_k/dt (t_j), u = s + 1 -- what the limits do through the nodes; no weight, no span factor
+    and no Leibniz term (``aten_vjp_nodes`` is the same on ATen).  Exact fp32 like every multi-output entry."""
+    lib = _lib.lib()
+    B, d, E, xd, hd, io = _quad_plan(spec, x, h, True)
+    K, n = n_out_of(spec), int(nb_steps)
+    if cot_nodes.shape != (B, n + 1, K):
+        raise RuntimeError(f"umnn_amd: the node cotangents have shape {tuple(cot_nodes.shape)}; expected {(B, n + 1, K)}")
+    x_dtype, h_dtype = x.dtype, h.dtype
+    x, h, x0, cot = _as(x, xd), _as(h, hd), _as(x0, xd), _as(cot_nodes, xd)
+    _, s = device_tables(n, x.device)
+    dx0 = torch.empty_like(x) if need[0] else None
+    dx = torch.empty_like(x) if need[1] else None
+    dh = torch.empty_like(h) if need[2] else None
+    n_params = sum(l.weight.numel() + l.bias.numel() for l in spec.linears)
+    dtheta = torch.empty(n_params, device=x.device, dtype=torch.float32) if need[3] else None
+    desc, keep = _desc(spec)
+    net = ctypes.byref(desc)
+    with torch.cuda.device(x.device):
+        nbytes = int(lib.umnn_cc_backward_multi_nodes_workspace_bytes(net, B, E))
+        if nbytes < 0:
+            _lib.check(_lib.EUNSUPPORTED, "umnn_cc_backward_multi_nodes_workspace_bytes")
+        ws = torch.empty(max(nbytes, 4), device=x.device, dtype=torch.uint8)
+        rc = lib.umnn_cc_backward_multi_nodes(net, _ptr(x0), _ptr(x), _ptr(h), _ptr(cot), _ptr(s), n, B, 1, E, _ptr(dx0), _ptr(dx),
+                                              _ptr(dh), _ptr(dtheta), _ptr(ws), nbytes, _stream(x.device))
+    dx0, dx = _quad_done(rc, "umnn_cc_backward_multi_nodes", (dx0, dx), xd, x_dtype, backward=True)
+    if h_dtype != hd and dh is not None:
+        dh = dh.to(h_dtype)
+    return dx0, dx, dh, dtheta
+
+
 _curve_ok = {}
+_curve_grad_ok = {}
+
+
+def _curve_grad_kernels_ok(spec, nb_steps):
+    """``_curve_kernels_ok`` and the same question for the two entries of the curve's backward, asked with zero rows: False (after a
+    one-time notice) sends a curve that is differentiated to ``aten_curve`` under autograd."""
+    if not _curve_kernels_ok(spec, nb_steps):
+        return False
+    key = (tuple((m.in_features, m.out_features) for m in spec.linears), int(nb_steps))
+
+    def ask(desc):
+        lib = _lib.lib()
+        for name, rc in (("umnn_cc_backward_multi_nodes", lib.umnn_cc_backward_multi_nodes(
+                              desc, None, None, None, None, None, key[1], 0, 1, key[0][0][0] - 1, None, None, None, None, None, 0, None)),
+                         ("umnn_cc_cumulate_adjoint", lib.umnn_cc_cumulate_adjoint(None, None, key[1], 0, key[0][-1][1], None, None))):
+            if rc == _lib.EUNSUPPORTED:
+                return rc
+            _lib.check(rc, name)
+        return 0
+
+    return _kernel_probe(
+        _curve_grad_ok, key, spec, ask, "curve-grad-aten", lambda widths: f"umnn_amd: no HIP curve backward for integrand widths {widths} "
+        f"at nb_steps = {key[1]} ({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): the curve runs on the generic ATen path "
+        "under autograd.") >= 0
 
 
 def _curve_kernels_ok(spec, nb_steps):
@@ -843,14 +917,33 @@ def aten_curve(integrand, x0, x, h, nb_steps):
     return t, C, f
 
 
-def cumulate(values, x0, x, nb_steps):
+def aten_cumulate_adjoint(g, nb_steps, ascending=False):
+    """``hip_cumulate_adjoint`` as one einsum with the adjoint table in g's dtype: any device."""
+    return torch.einsum("ji,bik->bjk", device_cumulative_adjoint(nb_steps, g.device, ascending, g.dtype), g)
+
+
+def _backward_switch(backward):
+    if backward not in ("aten", "hip"):
+        raise ValueError(f"umnn_amd: backward must be 'aten' or 'hip'; got {backward!r}")
+    return backward == "hip"
+
+
+def cumulate(values, x0, x, nb_steps, backward="aten"):
     """Cumulative quadrature of values given at the ascending nodes of [x0, x] (``curve``'s t): [B, n+1, K] -> the integral from x0
     to every node, [B, n+1, K], index 0 exactly 0.  One ``umnn_cc_cumulate`` launch for GPU tensors of K <= 16 outputs when nothing
     asks for a gradient (recorded: ``umnn::cc_cumulate``); ``aten_cumulate`` otherwise -- host tensors, float64, K > 16, nb_steps
-    beyond the kernel's table budget, and whenever an input requires grad."""
+    beyond the kernel's table budget, and, with ``backward="aten"`` (the default), whenever an input requires grad.
+    ``backward="hip"``: the same launch under autograd too (``CumulateFunction``: its backward is one ``umnn_cc_cumulate_adjoint``
+    launch, a, and d values = (x - x0)/2 a, dx = 1/2 sum a values, dx0 = -dx); what the kernel does not take runs ``aten_cumulate``
+    as before, never an error."""
+    hip_grad = _backward_switch(backward)
     wants_graph = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (values, x0, x))
     hip = (values.is_cuda and values.dtype in (torch.float32, torch.bfloat16, torch.float16) and values.dim() == 3
-           and 1 <= values.shape[2] <= _lib.MAX_OUTPUTS and not wants_graph)
+           and 1 <= values.shape[2] <= _lib.MAX_OUTPUTS and not (wants_graph and not hip_grad))
+    if hip and wants_graph:
+        if _graph_mode() or (not getattr(_state, "force_generic", False) and _cumulate_kernel_ok(values.shape[2], nb_steps, adjoint=True)):
+            return CumulateFunction.apply(values, x0, x, int(nb_steps))
+        hip = False
     if hip and _graph_mode():
         return torch.ops.umnn.cc_cumulate(values, x0, x, int(nb_steps), True)
     if hip and not getattr(_state, "force_generic", False) and _cumulate_kernel_ok(values.shape[2], nb_steps):
@@ -860,14 +953,64 @@ def cumulate(values, x0, x, nb_steps):
     return out
 
 
-def _cumulate_kernel_ok(K, nb_steps):
-    rc = _lib.lib().umnn_cc_cumulate(None, None, None, None, int(nb_steps), 0, int(K), None, None)      # (zero rows: launches nothing)
+def _cumulate_kernel_ok(K, nb_steps, adjoint=False):
+    """One zero-row call (it launches nothing) of the entry the caller is about to use: ``adjoint`` on the route that differentiates."""
+    lib = _lib.lib()
+    if adjoint:
+        name, rc = "umnn_cc_cumulate_adjoint", lib.umnn_cc_cumulate_adjoint(None, None, int(nb_steps), 0, int(K), None, None)
+    else:
+        name, rc = "umnn_cc_cumulate", lib.umnn_cc_cumulate(None, None, None, None, int(nb_steps), 0, int(K), None, None)
     if rc == _lib.EUNSUPPORTED:
         _warn_once(("cumulate-aten", int(nb_steps)), f"umnn_amd: no HIP cumulate kernel at nb_steps = {int(nb_steps)} "
                    f"({_lib.lib().umnn_last_error().decode('utf-8', 'replace')}): one einsum on the GPU instead.")
         return False
-    _lib.check(rc, "umnn_cc_cumulate")
+    _lib.check(rc, name)
     return True
+
+
+class CumulateFunction(torch.autograd.Function):
+    """``cumulate(..., backward="hip")`` under autograd: the forward launch, and a backward that is the adjoint launch plus the span
+    factor.  Values ascending, as ``cumulate`` takes them."""
+
+    @staticmethod
+    def forward(ctx, values, x0, x, nb_steps):
+        ctx.nb_steps, ctx.x0_none, ctx.graph = int(nb_steps), x0 is None, _graph_mode()
+        if ctx.graph:
+            out = torch.ops.umnn.cc_cumulate(values, x0, x, ctx.nb_steps, True)
+        else:
+            out = hip_cumulate(values, x0, x, ctx.nb_steps, ascending=True)
+        ctx.save_for_backward(values, x, *(() if x0 is None else (x0,)))
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g):
+        values, x, *lims = ctx.saved_tensors
+        nig = ctx.needs_input_grad
+        g32 = g.float().contiguous()
+        a = torch.ops.umnn.cc_cumulate_adjoint(g32, ctx.nb_steps, True) if ctx.graph else hip_cumulate_adjoint(g32, ctx.nb_steps, True)
+        span = x.float() if ctx.x0_none else x.float() - lims[0].float()
+        dv = (a * (span / 2).unsqueeze(2)).to(values.dtype) if nig[0] else None
+        dx = dx0 = None
+        if nig[1] or nig[2]:
+            dx = (a * values.float()).sum((1, 2)).unsqueeze(1) / 2
+            dx0 = (-dx).to(lims[0].dtype) if (nig[1] and not ctx.x0_none) else None
+            dx = dx.to(x.dtype) if nig[2] else None
+        return dv, dx0, dx, None
+
+
+def _curve_launches(spec, x0, x, h, nb_steps):
+    """The two launches of a curve on fp32 copies of the inputs -> (t, C, f_nodes, x0 or None, x, h): t and C ascending, f_nodes in
+    node order; recorded as the two ops.  (bf16 / fp16 callers: fp32 from end to end -- the node values are rounded once, outside.)"""
+    x0z = torch.zeros_like(x) if x0 is None else x0
+    x0, x0z, x, h = (None if x0 is None else x0.float()), x0z.float(), x.float(), h.float()
+    if _graph_mode():
+        _, f_nodes = torch.ops.umnn.cc_forward_multi_nodes(x0, x, h, *spec_args(spec), int(nb_steps))
+        C = torch.ops.umnn.cc_cumulate(f_nodes, x0, x, int(nb_steps), False)
+    else:
+        _, f_nodes = hip_forward_multi_nodes(spec, x0, x, h, nb_steps)
+        C = hip_cumulate(f_nodes, x0, x, nb_steps)
+    return _curve_abscissae(x0z, x, nb_steps), C, f_nodes, x0, x, h
 
 
 def curve(spec, integrand, x0, x, h, nb_steps):
@@ -878,47 +1021,170 @@ def curve(spec, integrand, x0, x, h, nb_steps):
     ``umnn_cc_cumulate`` (recorded: ``umnn::cc_forward_multi_nodes`` and ``umnn::cc_cumulate``) -- unless the library answers
     UMNN_EUNSUPPORTED (announced once), which runs ``aten_curve`` like ``spec`` None does: CPU tensors, float64, n_out > 16,
     integrands ``mlp_spec`` does not recognise.  The kernels record no autograd graph: callers that need gradients pass ``spec``
-    None (``IntegralCurve`` decides)."""
-    x0z = torch.zeros_like(x) if x0 is None else x0
+    None, or go through ``CurveFunction`` (``IntegralCurve`` decides)."""
     if spec is None or not (_graph_mode() or _curve_kernels_ok(spec, nb_steps)):
-        return aten_curve(integrand, x0z, x, h, nb_steps)
+        return aten_curve(integrand, torch.zeros_like(x) if x0 is None else x0, x, h, nb_steps)
     with torch.no_grad():
-        out_dtype = x.dtype       # (bf16 / fp16 callers: fp32 from end to end, theirs outside -- the node values are rounded once)
-        x0, x0z, x, h = (None if x0 is None else x0.float()), x0z.float(), x.float(), h.float()
-        if _graph_mode():
-            _, f_nodes = torch.ops.umnn.cc_forward_multi_nodes(x0, x, h, *spec_args(spec), int(nb_steps))
-            C = torch.ops.umnn.cc_cumulate(f_nodes, x0, x, int(nb_steps), False)
+        out_dtype = x.dtype
+        t, C, f_nodes = _curve_launches(spec, x0, x, h, nb_steps)[:3]
+        return tuple(v.to(out_dtype) for v in (t, C, f_nodes.flip(1)))
+
+
+def aten_vjp_nodes(integrand, x0, x, h, cot_nodes, nb_steps):
+    """``hip_backward_multi_nodes`` on ATen -> (dx0_tau, dx_tau, dh, dtheta): the VJP of f at the nodes t_j = x0 + (x - x0) u_j / 2
+    (node 0 is x itself) for the cotangent cot_nodes [B, n+1, K] in node order, in node chunks, through ``torch.func.vjp`` over the
+    pure form of the integrand like ``aten_vjp``; the cotangent tau_j of t_j that the same VJP returns is handed to the limits,
+    dx_tau = sum_j (u_j / 2) tau_j and dx0_tau = sum_j (1 - u_j / 2) tau_j.  dtheta is flat, in parameters() order, None for an
+    integrand without parameters.  Any device and dtype."""
+    f, params = _pure(integrand)
+    _, s = device_tables(nb_steps, x.device)
+    u = s.to(x.dtype) + 1
+    with torch.no_grad():
+        B = x.shape[0]
+        _check_multi_x(cot_nodes.shape[2], x)
+        span = x - x0
+        d_params = [torch.zeros_like(p) for p in params]
+        dh, dx, dx0 = torch.zeros_like(h), torch.zeros_like(x), torch.zeros_like(x)
+        for a, e in _node_chunks(nb_steps, B, h.shape[1] + 1):
+            t, h_rep = _eval_chunk(None, x0, span, h, u[a:e])
+            if a == 0:
+                t = torch.cat((x, t[B:]), 0)                 # node 0 is x itself, as in the kernels
+            val, vjp = torch.func.vjp(f, params, t, h_rep)
+            gp, gt, gh = vjp(cot_nodes[:, a:e].transpose(0, 1).reshape(val.shape))
+            for acc, gr in zip(d_params, gp):
+                acc += gr
+            dh += gh.view(e - a, B, -1).sum(0)
+            tau, hu = gt.view(e - a, B, 1), (u[a:e] / 2).view(-1, 1, 1)
+            dx += (tau * hu).sum(0)
+            dx0 += (tau * (1 - hu)).sum(0)
+    _state.path = _last_backward["path"] = "aten"
+    return dx0, dx, dh, (_flatten(d_params) if d_params else None)
+
+
+def curve_vjp(x0, x, f_nodes, gt, gC, gf, nb_steps, need, adjoint, vjp_nodes):
+    """The backward of a curve from its pieces -> (dx0, dx, dh, dtheta_flat), None where ``need`` says so.  gt [B, n+1], gC and gf
+    [B, n+1, K] are the cotangents of (t, C, f), ascending like them; f_nodes the saved node values in NODE order; x0 None: zeros.
+    ``adjoint(gC)`` -> a in node order (the adjoint cumulate without its span factor), ``vjp_nodes(cot)`` -> (dx0_tau, dx_tau, dh,
+    dtheta) (``hip_backward_multi_nodes`` / ``aten_vjp_nodes``).  With span = x - x0 and u ascending from 0 to 2:
+
+        cot = span/2 a + gf          S = 1/2 sum_jk a f          dx  = dx_tau  + sum_j gt_j u_j/2       + S
+                                                                 dx0 = dx0_tau + sum_j gt_j (1 - u_j/2) - S
+
+    the exact gradient of the DISCRETISED curve (every node moves with both limits), which is what autograd gives through
+    ``aten_curve`` -- not the Leibniz convention dF/dx = f(x) of the scalar quadrature operators.  No division by span: a row with
+    x == x0 is an ordinary row."""
+    span = x if x0 is None else x - x0
+    a = adjoint(gC.contiguous())
+    cot = torch.addcmul(gf.flip(1), a, (span / 2).unsqueeze(2))
+    dx0, dx, dh, dtheta = vjp_nodes(cot)
+    if need[0] or need[1]:
+        _, s = device_tables(nb_steps, x.device)
+        hu = ((s.to(x.dtype) + 1) / 2).flip(0).view(1, -1)
+        S = (a * f_nodes).sum((1, 2)).unsqueeze(1) / 2
+        dx = dx + (gt * hu).sum(1, keepdim=True) + S if need[1] else None
+        dx0 = dx0 + (gt * (1 - hu)).sum(1, keepdim=True) - S if need[0] else None
+    return (dx0 if need[0] else None, dx if need[1] else None, dh if need[2] else None, dtheta if need[3] else None)
+
+
+class CurveFunction(torch.autograd.Function):
+    """The curve on the HIP kernels under autograd (``IntegralCurve.apply(..., backward="hip")``): forward the two evaluation launches,
+    bit for bit; backward one ``umnn_cc_cumulate_adjoint`` launch, the elementwise glue of ``curve_vjp`` in torch ops and the
+    passes of ``umnn_cc_backward_multi_nodes``.  Recorded: ``umnn::cc_cumulate_adjoint`` and ``umnn::cc_backward_multi_nodes``,
+    which make the HIP / ATen choice when they run.  ``flat_params`` receives d_theta, as in ``ParallelNeuralIntegral``."""
+
+    @staticmethod
+    def forward(ctx, x0, x, integrand, flat_params, h, nb_steps):
+        spec = _hip_spec(integrand, x, multi=True, who="IntegralCurve")
+        ctx.nb_steps, ctx.x0_none = int(nb_steps), x0 is None
+        ctx.dtypes = (None if x0 is None else x0.dtype, x.dtype, h.dtype)
+        t, C, f_nodes, x0f, xf, hf = _curve_launches(spec, x0, x, h, nb_steps)
+        lims = () if x0 is None else (x0f,)
+        if not _graph_mode():       # clones: callers may write their limits in place after the call (as ``_quad_forward`` assumes)
+            lims, xf = tuple(v.clone() if v is x0 else v for v in lims), (xf.clone() if xf is x else xf)
+        _save(ctx, spec, integrand, *lims, xf, hf, f_nodes)
+        return tuple(v.to(x.dtype) for v in (t, C, f_nodes.flip(1)))
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, gt, gC, gf):
+        nig = ctx.needs_input_grad
+        n = 3 if ctx.x0_none else 4
+        tensors, net = _saved(ctx, n)
+        x0, (x, h, f_nodes) = (None if ctx.x0_none else tensors[0]), tensors[n - 3:n]
+        need = [bool(nig[0]) and x0 is not None, bool(nig[1]), bool(nig[4]), bool(nig[3])]
+        steps = ctx.nb_steps
+        if net:
+            def adjoint(g):
+                return torch.ops.umnn.cc_cumulate_adjoint(g, steps, False)
+
+            def vjp_nodes(cot):
+                return torch.ops.umnn.cc_backward_multi_nodes(x0, x, h, cot, *net, steps, need)
         else:
-            _, f_nodes = hip_forward_multi_nodes(spec, x0, x, h, nb_steps)
-            C = hip_cumulate(f_nodes, x0, x, nb_steps)
-        return tuple(t.to(out_dtype) for t in (_curve_abscissae(x0z, x, nb_steps), C, f_nodes.flip(1)))
+            spec = ctx.spec
+
+            def adjoint(g):
+                return hip_cumulate_adjoint(g, steps)
+
+            def vjp_nodes(cot):
+                return hip_backward_multi_nodes(spec, x0, x, h, cot, steps, need)
+        dx0, dx, dh, dtheta = curve_vjp(x0, x, f_nodes, gt.float(), gC.float(), gf.float(), steps, need, adjoint, vjp_nodes)
+        d0, d1, d2 = ctx.dtypes
+        return (None if dx0 is None else dx0.to(d0), None if dx is None else dx.to(d1), None, dtheta,
+                None if dh is None else dh.to(d2), None)
+
+
+def _note_aten_backward(grad):
+    _last_backward["path"] = "aten"
 
 
 class IntegralCurve:
     """(t, C, f) = the curve of int_{x0}^{t} f(s; h) ds at the n + 1 quadrature nodes of [x0, x] (``curve``):
 
-        IntegralCurve.apply(x0, x, integrand, flat_params, h, nb_steps=20) -> (t [B, n+1], C [B, n+1, K], f [B, n+1, K])
+        IntegralCurve.apply(x0, x, integrand, flat_params, h, nb_steps=20, backward="aten") -> (t [B, n+1], C [B, n+1, K], f [B, n+1, K])
 
-    x [B,1]; x0 [B,1] or None (zeros); the calling convention of the quadrature operators (``flat_params`` is accepted for parity
-    and not read).  The HIP kernels are the evaluation path: they run when grad mode is off or nothing -- x0, x, h, a parameter of the
-    integrand -- requires grad.  Otherwise the curve runs on ``aten_curve`` under plain autograd on the tensors' device, announced
-    once: a backward kernel with per-node cotangents does not exist yet."""
+    x [B,1]; x0 [B,1] or None (zeros); the calling convention of the quadrature operators.  The HIP kernels evaluate the curve when
+    grad mode is off or nothing -- x0, x, h, a parameter of the integrand -- requires grad.  When something does:
+
+      * ``backward="aten"`` (the default): ``aten_curve`` under plain autograd on the tensors' device, announced once; ``flat_params``
+        is accepted for parity and not read.
+      * ``backward="hip"``: ``CurveFunction`` -- the same two launches forward (t, C, f bit for bit those of the ``no_grad`` call), and
+        a once-differentiable backward on the kernels, one adjoint-cumulate launch and the passes of the multi-output backward with a
+        cotangent per node.  ``flat_params`` (``_flatten(integrand.parameters())``) receives d_theta, as in ``ParallelNeuralIntegral``:
+        an integrand with trainable parameters and no ``flat_params`` that requires grad stays on ATen.  CPU tensors, float64,
+        n_out > 16, nb_steps > 127 and nets beyond the LDS run ``aten_curve`` under autograd exactly as with ``"aten"``, with the
+        usual one-time notice, never an error.
+
+    ``backward_path_taken()`` reports the route of the most recent curve backward, "hip" or "aten" (on the ATen route through a
+    hook on the outputs that leaves their gradients alone).  Both give the exact gradient of the DISCRETISED curve (``curve_vjp``): every node moves with both limits.  That is deliberately
+    not the Leibniz convention dF/dx = f(x) of the scalar quadrature operators."""
 
     @staticmethod
-    def apply(x0, x, integrand, flat_params, h, nb_steps=20):
+    def apply(x0, x, integrand, flat_params, h, nb_steps=20, backward="aten"):
+        hip_grad = _backward_switch(backward)
         if x.dim() != 2 or x.shape[1] != 1:
             raise RuntimeError(f"umnn_amd: a curve is integrated over x of shape [B, 1]; got {tuple(x.shape)}")
-        wants_graph = torch.is_grad_enabled() and (
-            any(t is not None and t.requires_grad for t in (x0, x, h))
-            or (isinstance(integrand, torch.nn.Module) and any(p.requires_grad for p in integrand.parameters())))
+        trainable = isinstance(integrand, torch.nn.Module) and any(p.requires_grad for p in integrand.parameters())
+        wants_graph = torch.is_grad_enabled() and (any(t is not None and t.requires_grad for t in (x0, x, h)) or trainable)
         spec = _hip_spec(integrand, x, multi=True, who="IntegralCurve")
         if spec is not None and wants_graph:
-            if not _graph_mode():
+            if hip_grad and trainable and (flat_params is None or not flat_params.requires_grad):
+                _warn_once("curve-grad-flat", "umnn_amd: IntegralCurve(backward='hip') hands the parameters' gradient to flat_params; "
+                                              "without one that requires grad the curve runs on the generic ATen path under autograd.")
+            elif hip_grad and (_graph_mode() or _curve_grad_kernels_ok(spec, nb_steps)):
+                return CurveFunction.apply(x0, x, integrand, flat_params, h, int(nb_steps))
+            elif not hip_grad and not _graph_mode():
                 _warn_once("curve-grad", "umnn_amd: a curve whose inputs require grad runs on the generic ATen path under autograd "
                                          "(the HIP curve kernels are the evaluation path; use torch.no_grad() for them).")
             spec = None
         with torch.set_grad_enabled(wants_graph):
-            return curve(spec, integrand, x0, x, h, nb_steps)
+            out = curve(spec, integrand, x0, x, h, nb_steps)
+        # plain autograd runs this backward: a hook on each output (a loss may use any one of them) lets ``backward_path_taken()``
+        # report it; the hooks return nothing, so the gradients are autograd's own
+        if wants_graph and not _graph_mode():
+            for v in out:
+                if v.requires_grad:
+                    v.register_hook(_note_aten_backward)
+        return out
 
 
 def _pure(integrand):

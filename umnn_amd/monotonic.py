@@ -158,7 +158,7 @@ class MonotonicNN(nn.Module):
         return InverseIntegralSum.apply(t, coef, self.integrand, _flatten(self.integrand.parameters()), h, self.nb_steps,
                                         x_range, tol, max_iter, return_info)
 
-    def forward_curve(self, x, h, with_derivative=False):
+    def forward_curve(self, x, h, with_derivative=False, backward="aten"):
         """(t [B, n+1], y [B, n+1, n_out]) with n = nb_steps: ``forward(t, h)`` on the whole grid t[b] of the n + 1 quadrature nodes
         of [0, x_b], ascending -- t[:, 0] = 0, t[:, n] = x, y[:, n] = ``forward(x, h)`` up to rounding --, for the integrand
         evaluations of ONE ``forward``: a survival curve on a time grid, a CDF to plot or calibrate.  y[:, i, k] = exp(s_k(h)) *
@@ -166,19 +166,26 @@ class MonotonicNN(nn.Module):
         that share x share their abscissae: a common grid for a batch is x = t_max for every row (descending t for x < 0).  The
         curve points are as accurate as separate nb_steps-node quadratures to each t_i; values between the nodes are not provided.
         On GPU tensors under ``torch.no_grad()`` (or when nothing requires grad) this is two launches (``IntegralCurve``); when a
-        gradient can be asked for it runs on ATen under plain autograd, differentiable in x, h and every parameter."""
+        gradient can be asked for it runs on ATen under plain autograd, differentiable in x, h and every parameter -- or, with
+        ``backward="hip"``, on the same two launches with a backward on the kernels (one adjoint-cumulate launch and the passes of
+        the multi-output backward with a cotangent per node; what they do not take falls back to ATen with a notice, never an
+        error).  Either way the gradient is the exact one of the DISCRETISED curve: every node t_i = x u_i / 2 moves with x, so
+        d y[:, i] / dx is not f at a single point -- deliberately not the Leibniz convention dF/dx = f(x) of ``forward``."""
         offset, log_scaling = self._offset_log_scaling(h)
         scaling = torch.exp(log_scaling).unsqueeze(1)
-        t, C, f = IntegralCurve.apply(None, x, self.integrand, None, h, self.nb_steps)
+        # (d_theta of the HIP backward arrives through flat_params; nothing else reads it, so no other call builds it)
+        flat = _flatten(self.integrand.parameters()) if backward == "hip" and torch.is_grad_enabled() else None
+        t, C, f = IntegralCurve.apply(None, x, self.integrand, flat, h, self.nb_steps, backward)
         y = scaling * C + offset.unsqueeze(1)
         return (t, y, scaling * f) if with_derivative else (t, y)
 
-    def cumulative_incidence(self, x, h, curve=False):
+    def cumulative_incidence(self, x, h, curve=False, backward="aten"):
         """The cumulative incidence of each of the ``n_out`` competing risks whose cumulative hazards are the outputs,
         CIF_k(x) = int_0^x hz_k(s) exp(-sum_j H_j(s)) ds with H = ``forward_curve``'s y and hz = its dy/dt, -> [B, n_out]; ``curve=True``
         -> (t [B, n+1], CIF [B, n+1, n_out]) on ``forward_curve``'s grid, whose last row is that end point.  The inner integrals at
         the nodes of the outer one are the curve itself, so the nested integral costs one more cumulative-quadrature launch on
-        top of ``forward_curve`` (three launches on GPU tensors) instead of a quadrature per node.  Gradients as in ``forward_curve``."""
-        t, H, hz = self.forward_curve(x, h, with_derivative=True)
-        cif = cumulate(hz * torch.exp(-H.sum(2, keepdim=True)), None, x, self.nb_steps)
+        top of ``forward_curve`` (three launches on GPU tensors) instead of a quadrature per node.  Gradients as in ``forward_curve``;
+        ``backward="hip"`` keeps the third launch under autograd too (its backward is one more adjoint-cumulate launch)."""
+        t, H, hz = self.forward_curve(x, h, with_derivative=True, backward=backward)
+        cif = cumulate(hz * torch.exp(-H.sum(2, keepdim=True)), None, x, self.nb_steps, backward)
         return (t, cif) if curve else cif[:, -1]

@@ -8,6 +8,10 @@ torch.jit.trace record instead of the ctypes calls they cannot see.
         F [B, n_out], f_nodes [B, nb_steps + 1, n_out]: the integrand at every node, node 0 = x
     umnn::cc_cumulate(values, x0?, x, nb_steps, ascending=False) -> out       values, out [B, nb_steps + 1, K]; x [B,1]: the integral
         from x0 up to every node, ascending from the lower limit; ``ascending``: values are stored that way too (else in node order)
+    umnn::cc_backward_multi_nodes(x0?, x, h, cot_nodes, W[], b[], hidden_act, out_act, nb_steps, need[4]) -> (dx0_tau, dx_tau, dh, dtheta)
+        x [B,1]; n_out = 1..16; cot_nodes [B, nb_steps + 1, n_out]: a cotangent per node, node 0 = x (``integral.hip_backward_multi_nodes``)
+    umnn::cc_cumulate_adjoint(g, nb_steps, ascending=False) -> out       g, out [B, nb_steps + 1, K]: the adjoint of cc_cumulate without
+        its span factor; out in node order, or -- ``ascending`` -- from the lower limit up
     umnn::cc_backward_multi(x0?, x, h, g, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_backward_multi_fx(x0?, x, h, g, g_fx?, W[], b[], hidden_act, out_act, nb_steps, need[4], inv_f) -> (dx0, dx, dh, dtheta)
     umnn::cc_solve(t, h, W[], b[], hidden_act, out_act, nb_steps, lo, hi, tol, max_iter) -> (x, f_x, status)
@@ -30,7 +34,9 @@ when none does; cc_solve -- x with int_0^x f = t, ``integral.solve_integral`` --
 by the implicit-function theorem; cc_solve_multi -- ``integral.solve_sum`` -- likewise, in t, coef, h and the weights, through
 cc_backward_multi; cc_solve_block -- the same solve for every (row, dimension) in ONE launch, optionally warm-started,
 what the recorded ``invert(method="jacobi")`` sweeps call under no_grad -- has no autograd formula: a backward through it raises, as
-it does through cc_forward_multi_nodes and cc_cumulate, the evaluation path of the curves (``integral.IntegralCurve`` runs ATen under autograd);
+it does through cc_forward_multi_nodes and cc_cumulate, the launches of the curves (``integral.CurveFunction`` /
+``integral.CumulateFunction`` own their backward and record it as cc_cumulate_adjoint and cc_backward_multi_nodes; otherwise
+``integral.IntegralCurve`` runs ATen under autograd);
 flow_block's f_x output is not differentiable and its ``scaling`` must be frozen); the backward ops and
 flow_ll_block are not.  Registration loads no library and touches no GPU.
 
@@ -284,6 +290,73 @@ def cc_cumulate(values: Tensor, x0: Optional[Tensor], x: Tensor, nb_steps: int, 
 def _(values, x0, x, nb_steps, ascending=False):
     _check_cumulate(values, x0, x, nb_steps)
     return values.new_empty(values.shape)
+
+
+# ---- the backward of the curves: the adjoint of cc_cumulate and the multi-output backward with a cotangent per node
+def _check_cumulate_adjoint(g, nb_steps):
+    op = "cc_cumulate_adjoint"
+    _req(op, g.device.type == "cuda", f"g is on {g.device}; the HIP kernels need CUDA tensors")
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+    _req(op, g.dim() == 3, f"g has shape {tuple(g.shape)}; expected [B, nb_steps + 1, K]")
+    _check_tensor(op, "g", g, g, (g.shape[0], nb_steps + 1, g.shape[2]), _FLOATS)
+    _req(op, 1 <= g.shape[2] <= _lib.MAX_OUTPUTS, f"g has K = {g.shape[2]} outputs; expected 1 to {_lib.MAX_OUTPUTS}")
+
+
+@torch.library.custom_op("umnn::cc_cumulate_adjoint", mutates_args=(), device_types="cuda")
+def cc_cumulate_adjoint(g: Tensor, nb_steps: int, ascending: bool = False) -> Tensor:
+    """``integral.hip_cumulate_adjoint`` -> [B, nb_steps + 1, K]; beyond the kernel's table budget (decided here at run time) the
+    einsum of ``integral.aten_cumulate_adjoint``."""
+    _check_cumulate_adjoint(g, nb_steps)
+    if _I._cumulate_kernel_ok(g.shape[2], nb_steps, adjoint=True):
+        return _I.hip_cumulate_adjoint(g, nb_steps, ascending)
+    with torch.no_grad():
+        return _I.aten_cumulate_adjoint(g.detach(), nb_steps, ascending).contiguous()
+
+
+@cc_cumulate_adjoint.register_fake
+def _(g, nb_steps, ascending=False):
+    _check_cumulate_adjoint(g, nb_steps)
+    return g.new_empty(g.shape)
+
+
+def _check_backward_nodes(x0, x, h, cot_nodes, W, b, hidden_act, out_act, nb_steps, need):
+    op = "cc_backward_multi_nodes"
+    B, _ = _check_net(op, x, h, W, b, hidden_act, out_act, multi=True, min_out=1)
+    if x0 is not None:
+        _check_tensor(op, "x0", x0, x, (B, 1), _FLOATS)
+    _req(op, nb_steps >= 1, f"nb_steps is {nb_steps}; expected >= 1")
+    _check_tensor(op, "cot_nodes", cot_nodes, x, (B, nb_steps + 1, W[-1].shape[0]), _FLOATS)
+    _check_need(op, need, 4)
+
+
+@torch.library.custom_op("umnn::cc_backward_multi_nodes", mutates_args=(), device_types="cuda")
+def cc_backward_multi_nodes(x0: Optional[Tensor], x: Tensor, h: Tensor, cot_nodes: Tensor, W: List[Tensor], b: List[Tensor],
+                            hidden_act: int, out_act: int, nb_steps: int, need: List[bool]) -> tuple[Tensor, Tensor, Tensor, Tensor]:
+    """``integral.hip_backward_multi_nodes`` for an integrand given as tensors -> (dx0_tau, dx_tau, dh, dtheta), empty where not
+    needed; for what the library turns away (``integral._curve_grad_kernels_ok``, decided here at run time) ``integral.aten_vjp_nodes``
+    on ``pure_mlp``."""
+    _check_backward_nodes(x0, x, h, cot_nodes, W, b, hidden_act, out_act, nb_steps, need)
+    need = [bool(need[0]) and x0 is not None] + [bool(n) for n in need[1:]]
+    spec = spec_from_tensors(W, b, hidden_act, out_act)
+    if _I._curve_grad_kernels_ok(spec, nb_steps):
+        out = _I.hip_backward_multi_nodes(spec, x0, x, h, cot_nodes, nb_steps, need)
+    else:
+        xd, hd = x.detach().float(), h.detach().float()
+        out = _I.aten_vjp_nodes(pure_mlp(W, b, hidden_act, out_act), torch.zeros_like(xd) if x0 is None else x0.detach().float(), xd, hd,
+                                cot_nodes.detach().float(), nb_steps)
+        out = (out[0].to(x.dtype), out[1].to(x.dtype), out[2].to(h.dtype), out[3])
+    like = (x, x, h, W[0])
+    return tuple(t.contiguous() if (n and t is not None) else _empty(l, torch.float32 if i == 3 else None)
+                 for i, (t, n, l) in enumerate(zip(out, need, like)))
+
+
+@cc_backward_multi_nodes.register_fake
+def _(x0, x, h, cot_nodes, W, b, hidden_act, out_act, nb_steps, need):
+    _check_backward_nodes(x0, x, h, cot_nodes, W, b, hidden_act, out_act, nb_steps, need)
+    return (x.new_empty(x.shape) if (need[0] and x0 is not None) else _empty(x),
+            x.new_empty(x.shape) if need[1] else _empty(x),
+            h.new_empty(h.shape) if need[2] else _empty(h),
+            W[0].new_empty((_n_params(W, b),), dtype=torch.float32) if need[3] else _empty(W[0], torch.float32))
 
 
 # The autograd glue of the two forward ops: one ctx layout, one ``need`` rule, one packer of the nine input gradients.
@@ -671,7 +744,7 @@ def _(x, h, scaling, W, b, hidden_act, out_act, nb_steps, reverse_z, first, last
     return x.new_empty(x.shape), x.new_empty((x.shape[0],), dtype=torch.float32)
 
 
-OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_forward_multi_nodes", "cc_cumulate", "cc_backward_multi", "cc_backward_multi_fx", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
+OPS = ("cc_forward", "cc_backward", "cc_forward_multi", "cc_forward_multi_nodes", "cc_cumulate", "cc_cumulate_adjoint", "cc_backward_multi_nodes", "cc_backward_multi", "cc_backward_multi_fx", "cc_solve", "cc_solve_block", "flow_block", "flow_block_backward", "flow_ll", "flow_ll_backward", "flow_ll_block")
 
 
 spec_args = _I.spec_args       # MlpSpec -> (W[], b[], hidden_act, out_act): the integrand as the ops take it

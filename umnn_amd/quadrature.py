@@ -110,3 +110,22 @@ def device_cumulative_matrix(nb_steps, device, ascending=False, dtype=torch.floa
         Q = np.array(Q[:, ::-1] if ascending else Q)       # (a writable, contiguous copy)
         hit = _cumulative_device_cache[key] = torch.from_numpy(Q).to(dtype).contiguous().to(device)
     return hit
+
+
+_adjoint_device_cache = {}
+
+
+def device_cumulative_adjoint(nb_steps, device, ascending=False, dtype=torch.float32):
+    """[n+1, n+1] table of the ADJOINT of the cumulative quadrature on ``device``, uploaded once per (n, device, ascending, dtype):
+    Qt[j, i] = Q[n - i, j] with Q = ``device_cumulative_matrix(nb_steps, device, ascending)``'s entries -- that table transposed,
+    its row index counted from the lower limit, as the cumulative quadrature's ascending output is.  For a cotangent g [B, n+1, K] of
+    that output, sum_i Qt[j, i] g[:, i] is the cotangent of the values at node j up to the factor (x - x0)/2: in node order (node 0
+    = x), or -- ``ascending`` -- from the lower limit up, like the values ``cumulate`` takes."""
+    device = torch.device(device)
+    key = (int(nb_steps), device.type, device.index, bool(ascending), dtype)
+    hit = _adjoint_device_cache.get(key)
+    if hit is None:
+        Q = cc_cumulative_matrix(nb_steps)
+        Q = Q[::-1, ::-1] if ascending else Q[::-1, :]
+        hit = _adjoint_device_cache[key] = torch.from_numpy(np.array(Q.T)).to(dtype).contiguous().to(device)
+    return hit
